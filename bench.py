@@ -2,6 +2,7 @@
 """Benchmark of the Relation-DETR hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--queries 900] [--batch 4] [--config r50|focalnet]
+                    [--dump-outputs DIR] [--full]
 
 --config focalnet = BASELINE.json configs[4] per rank: relation_detr_focalnet_large_lrf_fl4_1200_2000, padded image
 1216x2016, 5-level pyramid (304,504)(152,252)(76,126)(38,63)(19,32), S = 204,098 tokens, 900 queries, 2 images per GPU.
@@ -23,9 +24,15 @@ Multi-GPU: images are independent, so ranks take disjoint image blocks (weak sca
 with no data-path collective; the only exchange is the eval all-gather of the [B,300,6] detections over RCCL,
 done once per step.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel = encoder-shape
-MSDA gather; algorithmic bytes from BASELINE.md section 4 / SURVEY.md section 8d) and `cpu_baseline` (the same
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times the K steps and
+prints the headline (`value` in images/s, `ms_per_step`).  `--full` adds everything that takes runs of its own: `roofline`
+(dominant kernel = encoder-shape MSDA gather; algorithmic bytes from BASELINE.md section 4 / SURVEY.md section 8d), the
+300-query / two-batches-in-flight / fp32 side runs with the bf16-vs-fp32 detection drift, and `cpu_baseline` (the same
 stack with the oracle's PyTorch-CPU operators on the host cores, bounded sample).
+
+`--dump-outputs DIR` writes what the timed path returned in its last step, the detections [B,300,6] =
+(x1,y1,x2,y2,score,label) of rank 0's images, to DIR/detections.npy (float32).  Inputs and weights are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -481,6 +488,13 @@ def timed_loop(run, inputs, steps, warmup):
     return time.perf_counter() - t0, out
 
 
+def dump_outputs(out_dir, dets):
+    """The timed path's last result as DIR/detections.npy: [B,300,6] float32 (x1,y1,x2,y2,score,label), 7.2 KB per image."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "detections.npy"), dets.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -491,10 +505,14 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: 4 for r50, 2 for focalnet)")
     ap.add_argument("--config", default="r50", choices=sorted(CONFIGS), help="r50 = BASELINE.json configs[1] (default); "
                     "focalnet = configs[4] per rank (5 levels, 1200x2000)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every kernel from Python instead of replaying a HIP graph")
-    ap.add_argument("--no-extras", action="store_true", help="skip the 300-query / fp32 / drift side measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the 300-query / fp32 / drift side measurements")
     ap.add_argument("--dump-dets", default=None, help="save the last step's detections [B,300,6] to this file (torch.save)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's detections [B,300,6] to DIR/detections.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run the side measurements: roofline / per-kernel timings, "
+                    "300-query, two-batches-in-flight and fp32 variants, CPU baseline (a plain run times the headline only)")
     ap.add_argument("--dry-run", action="store_true", help="launcher + gloo collectives only, no GPU work (CPU rehearsal)")
     args = ap.parse_args()
     if args.gpus < 1:
@@ -606,6 +624,34 @@ def main():
         dist.all_gather_into_tensor(allt, t)
         per_rank = allt.tolist()
         el = max(per_rank)                                  # MAX over ranks
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, dets_main)
+
+    S = int(sum(h * w for h, w in cfg["shapes"]))
+    res = {
+        "metric": cfg["metric"],
+        "value": world * B * args.steps / el, "unit": "images/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "setup_replays": SETUP_REPLAYS, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
+        "world_size_seen": dist.get_world_size() if use_dist else 1,
+        "per_rank_images_per_s": [B * args.steps / t for t in per_rank],
+        "config": {"workload": f"{cfg['name']} transformer stack from feature pyramids: 6 encoder "
+                               f"layers (MSDA self-attn, S={S}, {L} levels) + two-stage top-k + 6 decoder layers (relation-biased "
+                               "self-attn + MSDA cross-attn + box refinement) + top-300 detections; backbone/neck excluded",
+                   "batch_per_gpu": B, "global_batch": B * world, "queries": Nq,
+                   "weights": "random init (seeded); MSDA offset / attention projections N(0, .02) / N(0, .05), class heads x3, "
+                              "last box-head layers N(0, .01), tgt_embed rows equal -- see build_network",
+                   "levels": L, "launch": launch, "streams": nstreams, "gemm_tuning": tuned,
+                   "parallelism": f"image-parallel x{world}"},
+    }
+    if not args.full:                                       # the headline only: side measurements are --full
+        if rank == 0 and args.dump_dets:
+            torch.save(dets_main.detach().float().cpu(), args.dump_dets)
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if use_dist:
+            dist.destroy_process_group()
+        return
 
     note(f"timed loop done: {world * B * args.steps / el:.1f} images/s; dominant kernel")
     def busy():                                             # ~50 ms of the stack itself, enqueued without a host sync
@@ -741,28 +787,13 @@ def main():
     if rank == 0 and args.dump_dets:
         torch.save(dets_main.detach().float().cpu(), args.dump_dets)
     if rank == 0:
-        res = {
-            "metric": cfg["metric"],
-            "value": world * B * args.steps / el, "unit": "images/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "setup_replays": SETUP_REPLAYS, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            "value_300_queries": value_300, "value_gemm_tuned": value_tuned, "value_two_batches_in_flight": value_two_in_flight,
-            "world_size_seen": dist.get_world_size() if use_dist else 1,
-            "per_rank_images_per_s": [B * args.steps / t for t in per_rank],
-            "config": {"workload": f"{cfg['name']} transformer stack from feature pyramids: 6 encoder "
-                                   f"layers (MSDA self-attn, S={S}, {L} levels) + two-stage top-k + 6 decoder layers (relation-biased "
-                                   "self-attn + MSDA cross-attn + box refinement) + top-300 detections; backbone/neck excluded",
-                       "batch_per_gpu": B, "global_batch": B * world, "queries": Nq,
-                       "queries_note": "value: 900 two-stage queries (what the reference config runs), 300 detections kept; "
-                                       "value_300_queries: 300 two-stage queries (BASELINE.json's wording); "
-                                       "value_two_batches_in_flight: the same batches with two of them in flight on two streams "
-                                       "(serving throughput, a batch's latency doubles) -- informational, never `value`",
-                       "weights": "random init (seeded); MSDA offset / attention projections N(0, .02) / N(0, .05), class heads x3, "
-                                  "last box-head layers N(0, .01), tgt_embed rows equal -- see build_network",
-                       "levels": L, "fp32_images_per_s": fp32_ips, "bf16_vs_fp32_detections": drift,
-                       "launch": launch, "streams": nstreams,
-                       "gemm_tuning": tuned,
-                       "parallelism": f"image-parallel x{world}"},
+        res.update({"value_300_queries": value_300, "value_gemm_tuned": value_tuned, "value_two_batches_in_flight": value_two_in_flight})
+        res["config"].update({"queries_note": "value: 900 two-stage queries (what the reference config runs), 300 detections kept; "
+                                              "value_300_queries: 300 two-stage queries (BASELINE.json's wording); "
+                                              "value_two_batches_in_flight: the same batches with two of them in flight on two streams "
+                                              "(serving throughput, a batch's latency doubles) -- informational, never `value`",
+                              "fp32_images_per_s": fp32_ips, "bf16_vs_fp32_detections": drift})
+        res.update({
             "roofline": {"bound": "hbm", "kernel": (ROOFLINE_KERNEL % (gather_kernel_name(B, S, L, False, cfg["shapes"]), B)) if args.dtype == "bf16" else "msda_fwd_qrun_kernel<float, L=%d> (encoder shape, B=%d)" % (L, B),
                          "achieved": alg / t_kernel / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
                          "frac": alg / t_kernel / HBM_PEAK, **pmc_traffic(args.dtype, B, args.config),
@@ -789,7 +820,7 @@ def main():
                          "reference_operator_layout_ms": t_kernel_bshd * 1e3 if t_kernel_bshd else None,
                          "reference_operator_layout_note": "same operator on value [B,S,H,D] (the _C contract): LDS-window MFMA "
                                                            "kernel msda_fwd_win_kernel, algo = auto"},
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             note("cpu baseline")
             res["cpu_baseline"] = cpu_baseline(Nq, cfg=cfg)

@@ -10,13 +10,13 @@ mkdir -p $O
 python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1 || { tail -30 $O/gpu_tests.log; exit 1; }
 tail -2 $O/gpu_tests.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-python3 bench.py > $O/bench_default_bf16.json.log 2>$O/bench_default_bf16.err
+python3 bench.py --full > $O/bench_default_bf16.json.log 2>$O/bench_default_bf16.err
 tail -1 $O/bench_default_bf16.json.log | cut -c1-300
-python3 bench.py --dtype fp32 --no-cpu-baseline > $O/bench_fp32.json.log 2>/dev/null
+python3 bench.py --full --dtype fp32 --no-cpu-baseline > $O/bench_fp32.json.log 2>/dev/null
 tail -1 $O/bench_fp32.json.log | cut -c1-200
-RDETR_BENCH_STREAMS=1 python3 bench.py --no-cpu-baseline --no-extras > $O/bench_bf16_one_stream.json.log 2>/dev/null
-RDETR_BENCH_FORCE_DIST=1 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_bf16_one_rank_rccl.json.log 2>/dev/null
-python3 bench.py --config focalnet --steps 10 --warmup 3 > $O/bench_focalnet_bf16.json.log 2>$O/bench_focalnet_bf16.err
+RDETR_BENCH_STREAMS=1 python3 bench.py --full --no-cpu-baseline --no-extras > $O/bench_bf16_one_stream.json.log 2>/dev/null
+RDETR_BENCH_FORCE_DIST=1 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras > $O/bench_bf16_one_rank_rccl.json.log 2>/dev/null
+python3 bench.py --full --config focalnet --steps 10 --warmup 3 > $O/bench_focalnet_bf16.json.log 2>$O/bench_focalnet_bf16.err
 tail -1 $O/bench_focalnet_bf16.json.log | cut -c1-200
 tail -1 $O/bench_bf16_one_rank_rccl.json.log | cut -c1-200
 tail -1 $O/bench_bf16_one_stream.json.log | cut -c1-200
