@@ -239,6 +239,31 @@ int rdetr_msda_backward_det_f32(const float *value, const int64_t *spatial_shape
                                 int L, int Nq, int P, void *workspace, long long workspace_bytes, float *grad_value,
                                 float *grad_sampling_loc, float *grad_attn_weight, void *stream);
 
+/* Fused-producer backward: the gradients of rdetr_msda_forward_fused_* with respect to its own inputs (training mode of the
+ * fused path).  Replaces  MultiScaleDeformableAttnFunction.backward            models/bricks/ms_deform_attn.py:35-84
+ *           + autograd through the softmax and the sampling-location arithmetic  ms_deform_attn.py:322-370
+ *           (_C.ms_deform_attn_backward, ms_deform_attn_cuda.cu:75-145).
+ *   value [B,S,H,D], sampling_offsets [B,Nq,H,L,P,2], attn_logits [B,Nq,H,L*P], grad_out [B,Nq,H*D]: value's dtype (fp32 | bf16)
+ *   reference_points [B,Nq,L,ref_dim] fp32, ref_dim 2 or 4
+ *   grad_value [B,S,H,D] fp32; grad_offsets / grad_logits: the shapes of their inputs, value's dtype;
+ *   grad_ref_partial [B,Nq,H,L,ref_dim] fp32 (nullable): one partial per head, the caller sums over H.
+ * The softmax weights and locations are recomputed with the forward kernel's arithmetic for the dtype, so the backward
+ * differentiates what the forward used.  Points outside their level or at NaN locations contribute nothing.
+ * workspace NULL: atomic mode, grad_value accumulated with float atomics and MUST be zero-filled by the caller.  Otherwise
+ * deterministic mode: rdetr_msda_backward_det_workspace_bytes() bytes (16-byte aligned), grad_value OVERWRITTEN (every row).
+ * grad_offsets / grad_logits / grad_ref_partial are fixed-order sums: the same bits in both modes.  B = 0 or Nq = 0: nothing is
+ * written.  H = 8, D = 32, P = 4, L <= 8 only (RDETR_ERR_UNSUPPORTED otherwise). */
+int rdetr_msda_backward_fused_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                  const float *sampling_offsets, const float *attn_logits, const float *reference_points, int ref_dim,
+                                  const float *grad_out, int B, int S, int H, int D, int L, int Nq, int P, void *workspace,
+                                  long long workspace_bytes, float *grad_value, float *grad_offsets, float *grad_logits,
+                                  float *grad_ref_partial, void *stream);
+int rdetr_msda_backward_fused_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                   const uint16_t *sampling_offsets, const uint16_t *attn_logits, const float *reference_points,
+                                   int ref_dim, const uint16_t *grad_out, int B, int S, int H, int D, int L, int Nq, int P,
+                                   void *workspace, long long workspace_bytes, float *grad_value, uint16_t *grad_offsets,
+                                   uint16_t *grad_logits, float *grad_ref_partial, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Position-relation bias.
  * Replaces  PositionRelationEmbedding.forward  models/bricks/relation_transformer.py:520-532

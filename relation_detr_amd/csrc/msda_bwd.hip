@@ -1,4 +1,4 @@
-// Multi-scale deformable attention, backward (fp32) -- hand-written for gfx950 (MI355X).
+// Multi-scale deformable attention, backward (fp32; fused-producer form fp32 and bf16) -- hand-written for gfx950 (MI355X).
 //
 // Replaces ms_deformable_col2im_cuda and, for head_dim 32, its kernel
 // ms_deformable_col2im_gpu_kernel_shm_blocksize_aware_reduce_v1<T,32>
@@ -173,12 +173,218 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_wave_kernel(
     }
 }
 
+__device__ __forceinline__ float ld_f32(const float *p) { return *p; }
+__device__ __forceinline__ float ld_f32(const uint16_t *p) { return bf16_bits_to_f32(*p); }
+__device__ __forceinline__ f32x2 ld_f32x2(const float *p) { return *reinterpret_cast<const f32x2 *>(p); }
+__device__ __forceinline__ f32x2 ld_f32x2(const uint16_t *p)
+{
+    const unsigned u = *reinterpret_cast<const unsigned *>(p);
+    return f32x2{__builtin_bit_cast(float, u << 16), __builtin_bit_cast(float, u & 0xffff0000u)};
+}
+__device__ __forceinline__ void st_val(float *p, float v) { *p = v; }
+__device__ __forceinline__ void st_val(uint16_t *p, float v) { *p = (uint16_t)f32_to_bf16_bits(v); }
+__device__ __forceinline__ void st_val2(float *p, float x, float y) { *reinterpret_cast<f32x2 *>(p) = f32x2{x, y}; }
+__device__ __forceinline__ void st_val2(uint16_t *p, float x, float y) { *reinterpret_cast<unsigned *>(p) = pack_bf16x2(x, y); }
+
+// Fused-producer backward (rdetr_msda_backward_fused_*): the inputs of the fused forward (raw offsets and logits in value's dtype,
+// reference points) instead of materialised locations / weights.  The work shape of msda_bwd_wave_kernel -- one wave = one head x
+// two queries, one channel per lane, the four corner rows re-gathered, fp32 atomics covering two full 128-byte grad_value head
+// rows per wave instruction -- with three changes:
+//   * set-up: lane (pair, c) recomputes the soft-maxed weight and the sampling location of point c (L*P <= 32: both queries in 64
+//     lanes, lanes c >= L*P are -inf padding slots) with the arithmetic of the forward kernel for that dtype (msda_fwd.hip: fp32
+//     expf and divisions; bf16 the hardware exp2 and products with reciprocals), max and sum by xor-shuffles, so the backward
+//     differentiates the weights and locations the forward used;
+//   * bf16 value rows (64 bytes per head) are loaded two bytes per lane and converted to fp32; grad_value stays fp32;
+//   * closing step, in the set-up layout (coalesced rows): softmax backward grad_logit_k = w_k (s_k - sum_j w_j s_j) with
+//     s_k = <grad_out, sample_k>, the location chain rule onto the offsets, and per-level sums onto the reference point.
+// Every sum except grad_value's is a fixed shuffle tree: grad_offsets / grad_logits / grad_ref are the same bits in both modes.
+template <typename T, bool DET>
+__global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
+    const T *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ level_start,
+    const T *__restrict__ offsets, const T *__restrict__ logits, const float *__restrict__ ref, int ref_dim,
+    const T *__restrict__ grad_out, int S, int L, int Nq, int tiles_per_image, int nblk, float *__restrict__ grad_value,
+    T *__restrict__ grad_offsets, T *__restrict__ grad_logits, float *__restrict__ grad_ref, unsigned *__restrict__ rec_key,
+    unsigned *__restrict__ rec_id, float *__restrict__ rec_w)
+{
+    constexpr bool kBf16 = sizeof(T) == 2;
+    const int LP = L * kBP;
+    __shared__ BwdLevels lvl;
+    __shared__ u32x4 st_off[kBWaves][kBMaxL * kBP * 2];
+    __shared__ f32x4 st_frac[kBWaves][kBMaxL * kBP * 2];
+    __shared__ f32x4 st_misc[kBWaves][kBMaxL * kBP * 2];
+
+    const int tid = threadIdx.x;
+    if (tid < L) {
+        lvl.h[tid] = (int)shapes[2 * tid];
+        lvl.w[tid] = (int)shapes[2 * tid + 1];
+        lvl.start[tid] = (int)level_start[tid];
+    }
+    __syncthreads();
+
+    const int logical = xcd_contiguous_block(blockIdx.x, nblk);
+    const int bm = logical / tiles_per_image;
+    const int tile = logical - bm * tiles_per_image;
+    const int b = bm / kBH, m = bm - b * kBH;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, pair = lane >> 5, c = lane & 31;
+    const int q = (tile * kBWaves + wave) * 2 + pair;
+    const bool qok = q < Nq;
+
+    // grad_value: fp32 [B,S,H,D], 1 KiB per pixel; value: T, sizeof(T) * 256 bytes per pixel -- the staged corner offsets are
+    // grad_value byte offsets, shifted right by one for a bf16 value (the invalid offset 0x80000000 stays out of range)
+    const size_t plane = (size_t)b * S * (kBH * kBD) + (size_t)m * kBD;
+    const unsigned nrec = (unsigned)S * kBPixelBytes - (unsigned)m * kBHeadBytes;
+    const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(value) + plane, 0,
+                                                                          kBf16 ? nrec / 2 : nrec, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(grad_value + plane, 0, nrec, 0x00020000);
+    const unsigned lane_off = (unsigned)c * 4u, lane_off_v = (unsigned)c * (unsigned)sizeof(T);
+    auto load_v = [&](unsigned off) {
+        if constexpr (kBf16)
+            return bf16_bits_to_f32(__builtin_amdgcn_raw_buffer_load_b16(rs_v, (off >> 1) + lane_off_v, 0, 0));
+        else
+            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_v, off + lane_off_v, 0, 0));
+    };
+
+    const size_t row = (size_t)b * Nq + (qok ? q : 0);
+    const size_t hrow = (row * kBH + m) * (size_t)LP;
+    u32x4 *soff = st_off[wave];
+    f32x4 *sfrac = st_frac[wave];
+    f32x4 *smisc = st_misc[wave];
+
+    // ---- set-up: lane (pair, c) = point c of its query; softmax over the 32 lanes of the pair -------------------------------
+    const bool pok = c < LP;
+    const int l = pok ? c / kBP : 0;
+    const int h = lvl.h[l], w = lvl.w[l];
+    const float lg = pok ? ld_f32(logits + hrow + c) : -__builtin_inff();
+    const f32x2 off = pok ? ld_f32x2(offsets + (hrow + c) * 2) : f32x2{0.f, 0.f};
+    float mx = lg;
+#pragma unroll
+    for (int o = 1; o < 32; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    const float e = kBf16 ? __builtin_amdgcn_exp2f((lg - mx) * 1.44269504088896341f) : expf(lg - mx);    // 0 for padding
+    const float sum = sum32(e);
+    const float wk = kBf16 ? e * (1.0f / sum) : e / sum;
+    const float *rp = ref + (row * L + l) * (size_t)ref_dim;
+    const f32x4 rc = ref_dim == 2 ? f32x4{rp[0], rp[1], 0.f, 0.f} : f32x4{rp[0], rp[1], rp[2], rp[3]};
+    f32x2 xy;
+    if (ref_dim == 2) {
+        if (kBf16 && (L == 4 || L == 5)) {             // the forward's 4- and 5-level bf16 kernels multiply by reciprocals
+            xy.x = rc.x + off.x * (1.0f / (float)w);
+            xy.y = rc.y + off.y * (1.0f / (float)h);
+        } else {
+            xy.x = rc.x + off.x / (float)w;
+            xy.y = rc.y + off.y / (float)h;
+        }
+    } else {
+        xy.x = rc.x + off.x * (1.0f / kBP) * rc.z * 0.5f;
+        xy.y = rc.y + off.y * (1.0f / kBP) * rc.w * 0.5f;
+    }
+    const float x = xy.x * (float)w - 0.5f, y = xy.y * (float)h - 0.5f;
+    const bool inside = pok && qok && (y > -1.f) && (x > -1.f) && (y < (float)h) && (x < (float)w);    // false for NaN
+    if (pok) {
+        const float xf = floorf(x), yf = floorf(y);
+        const int x0 = inside ? (int)xf : 0, y0 = inside ? (int)yf : 0;
+        const float lx = inside ? x - xf : 0.f, ly = inside ? y - yf : 0.f;
+        const bool okx0 = inside && x0 >= 0, okx1 = inside && x0 + 1 <= w - 1;
+        const bool oky0 = y0 >= 0, oky1 = y0 + 1 <= h - 1;
+        const unsigned base = (unsigned)(lvl.start[l] + y0 * w + x0) * kBPixelBytes;
+        const unsigned rowb = (unsigned)w * kBPixelBytes;
+        u32x4 o;
+        o.x = (okx0 && oky0) ? base : kBInvalid;
+        o.y = (okx1 && oky0) ? base + kBPixelBytes : kBInvalid;
+        o.z = (okx0 && oky1) ? base + rowb : kBInvalid;
+        o.w = (okx1 && oky1) ? base + rowb + kBPixelBytes : kBInvalid;
+        const float a = inside ? wk : 0.f;
+        soff[c * 2 + pair] = o;
+        sfrac[c * 2 + pair] = f32x4{1.f - ly, 1.f - lx, ly, lx};
+        smisc[c * 2 + pair] = f32x4{a, (float)w, (float)h, inside ? 1.f : 0.f};
+        if constexpr (DET) {
+            if (qok) {                                   // the records of msda_bwd_wave_kernel<true>
+                const unsigned rbase = (unsigned)((size_t)b * S) * kBH + (unsigned)m;
+                const float hy = 1.f - ly, hx = 1.f - lx;
+                auto key = [&](unsigned ob) { return ob == kBInvalid ? 0xffffffffu : rbase + (ob / kBPixelBytes) * kBH; };
+                const size_t rec = (hrow + c) * 4;
+                *reinterpret_cast<u32x4 *>(rec_key + rec) = u32x4{key(o.x), key(o.y), key(o.z), key(o.w)};
+                *reinterpret_cast<u32x4 *>(rec_id + rec) = u32x4{(unsigned)rec, (unsigned)rec + 1u, (unsigned)rec + 2u, (unsigned)rec + 3u};
+                *reinterpret_cast<f32x4 *>(rec_w + rec) = f32x4{(hy * hx) * a, (hy * lx) * a, (ly * hx) * a, (ly * lx) * a};
+            }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    const float g = ld_f32(grad_out + row * (kBH * kBD) + m * kBD + c);
+    float my_s = 0.f, my_gx = 0.f, my_gy = 0.f;                   // results of point `c`, kept by lane c of the pair
+
+#pragma unroll 2
+    for (int pt = 0; pt < LP; ++pt) {
+        const u32x4 o = soff[pt * 2 + pair];
+        const f32x4 fr = sfrac[pt * 2 + pair];      // hy, hx, ly, lx
+        const f32x4 mi = smisc[pt * 2 + pair];      // weight (0 if outside), W, H, inside
+        const float v00 = load_v(o.x), v01 = load_v(o.y), v10 = load_v(o.z), v11 = load_v(o.w);
+        const float hy = fr.x, hx = fr.y, ly = fr.z, lx = fr.w;
+        const float ga = g * mi.x;
+        if constexpr (!DET) {
+            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((hy * hx) * ga, rs_g, o.x + lane_off, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((hy * lx) * ga, rs_g, o.y + lane_off, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((ly * hx) * ga, rs_g, o.z + lane_off, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((ly * lx) * ga, rs_g, o.w + lane_off, 0, 0);
+        }
+        const float dxs = hy * (v01 - v00) + ly * (v11 - v10);
+        const float dys = hx * (v10 - v00) + lx * (v11 - v01);
+        const float smp = (hy * hx) * v00 + (hy * lx) * v01 + (ly * hx) * v10 + (ly * lx) * v11;
+        const float s = sum32(g * smp) * mi.w;                       // d loss / d weight_k
+        const float gx = sum32(ga * dxs) * mi.y;                     // d loss / d loc_k (normalised x), * W_l
+        const float gy = sum32(ga * dys) * mi.z;                     // ... y, * H_l
+        if (c == pt) {
+            my_s = s;
+            my_gx = gx;
+            my_gy = gy;
+        }
+    }
+
+    // ---- closing step, lane = point: softmax backward, offsets, reference-point partials ------------------------------------
+    const float tot = sum32(wk * my_s);                               // padding lanes: 0 * 0
+    const float g_logit = wk * (my_s - tot);
+    float gox, goy, rz = 0.f, rw = 0.f;
+    if (ref_dim == 2) {
+        gox = my_gx / (float)w;
+        goy = my_gy / (float)h;
+    } else {
+        gox = my_gx * rc.z * (0.5f / kBP);
+        goy = my_gy * rc.w * (0.5f / kBP);
+        rz = inside ? my_gx * off.x * (0.5f / kBP) : 0.f;             // NaN offsets of outside points contribute nothing
+        rw = inside ? my_gy * off.y * (0.5f / kBP) : 0.f;
+    }
+    // sum over the P = 4 points of a level (lanes 4l .. 4l+3)
+    float rx = my_gx, ry = my_gy;
+#pragma unroll
+    for (int o = 1; o < kBP; o <<= 1) {
+        rx += __shfl_xor(rx, o, 64);
+        ry += __shfl_xor(ry, o, 64);
+        rz += __shfl_xor(rz, o, 64);
+        rw += __shfl_xor(rw, o, 64);
+    }
+    if (qok && pok) {
+        st_val(grad_logits + hrow + c, g_logit);
+        st_val2(grad_offsets + (hrow + c) * 2, gox, goy);
+        if (grad_ref && (c & (kBP - 1)) == 0) {
+            float *gr = grad_ref + ((row * kBH + m) * L + l) * (size_t)ref_dim;
+            if (ref_dim == 2)
+                *reinterpret_cast<f32x2 *>(gr) = f32x2{rx, ry};
+            else
+                *reinterpret_cast<f32x4 *>(gr) = f32x4{rx, ry, rz, rw};
+        }
+    }
+}
+
 // Deterministic mode, second half: grad_value row r = (image, pixel, head) is the sum of ITS records in sorted order.  Half a wave
 // per row (lane = channel); the segment [lo, hi) of the sorted keys by binary search (uniform per half wave); the record gives the
-// weight and, through its position, the (image, query, head) row of grad_out.  Every row is written (empty segment: zeros), so
-// grad_value needs no zero-initialisation in this mode.
+// weight and, through its position, the (image, query, head) row of grad_out (fp32, or bf16 for the fused bf16 backward).  Every
+// row is written (empty segment: zeros), so grad_value needs no zero-initialisation in this mode.
+template <typename G>
 __global__ __launch_bounds__(256) void msda_bwd_segment_sum_kernel(const unsigned *__restrict__ skey, const unsigned *__restrict__ sid,
-                                                                  const float *__restrict__ rec_w, const float *__restrict__ grad_out,
+                                                                  const float *__restrict__ rec_w, const G *__restrict__ grad_out,
                                                                   long long nrec, long long nrows, int LP, float *__restrict__ grad_value)
 {
     const long long r = (long long)blockIdx.x * 8 + (threadIdx.x >> 5);
@@ -197,7 +403,7 @@ __global__ __launch_bounds__(256) void msda_bwd_segment_sum_kernel(const unsigne
     for (long long i = lo; i < hi; ++i) {
         const unsigned id = sid[i];
         const unsigned rowhm = (id >> 2) / (unsigned)LP;                       // (image * Nq + query) * 8 + head
-        acc = __builtin_fmaf(rec_w[id], grad_out[(size_t)rowhm * kBD + c], acc);
+        acc = __builtin_fmaf(rec_w[id], ld_f32(grad_out + (size_t)rowhm * kBD + c), acc);
     }
     grad_value[(size_t)r * kBD + c] = acc;
 }
@@ -334,7 +540,7 @@ extern "C" int rdetr_msda_backward_det_f32(const float *value, const int64_t *sp
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (B == 0 || S == 0) return RDETR_OK;
     if (Nq == 0) {                                                              // no records: every row of grad_value is zero
-        hipLaunchKernelGGL(msda_bwd_segment_sum_kernel, dim3((unsigned)(((long long)B * S * kBH + 7) / 8)), dim3(256), 0, st, nullptr, nullptr,
+        hipLaunchKernelGGL(msda_bwd_segment_sum_kernel<float>, dim3((unsigned)(((long long)B * S * kBH + 7) / 8)), dim3(256), 0, st, nullptr, nullptr,
                            nullptr, nullptr, 0ll, (long long)B * S * kBH, L * kBP, grad_value);
         return launch_status();
     }
@@ -362,7 +568,82 @@ extern "C" int rdetr_msda_backward_det_f32(const float *value, const int64_t *sp
     size_t tmp = d.tmp_bytes;
     if (hipcub::DeviceRadixSort::SortPairs(ws + d.off_tmp, tmp, rec_key, skey, rec_id, sid, (int)d.nrec, 0, d.key_bits, st) != hipSuccess)
         return RDETR_ERR_LAUNCH;
-    hipLaunchKernelGGL(msda_bwd_segment_sum_kernel, dim3((unsigned)((d.nrows + 7) / 8)), dim3(256), 0, st, skey, sid, rec_w, grad_out, d.nrec,
+    hipLaunchKernelGGL(msda_bwd_segment_sum_kernel<float>, dim3((unsigned)((d.nrows + 7) / 8)), dim3(256), 0, st, skey, sid, rec_w, grad_out, d.nrec,
                        d.nrows, L * kBP, grad_value);
     return launch_status();
+}
+
+// ---- fused-producer backward ---------------------------------------------------------------------------------------------------
+template <typename T>
+static int msda_backward_fused(const T *value, const int64_t *shapes, const int64_t *level_start, const T *offsets, const T *logits,
+                               const float *ref, int ref_dim, const T *grad_out, int B, int S, int H, int D, int L, int Nq, int P,
+                               void *workspace, long long workspace_bytes, float *grad_value, T *grad_offsets, T *grad_logits,
+                               float *grad_ref_partial, hipStream_t st)
+{
+    if (B < 0 || S < 0 || Nq < 0 || H <= 0 || D <= 0 || L <= 0 || P <= 0 || workspace_bytes < 0) return RDETR_ERR_INVALID_ARG;
+    if (ref_dim != 2 && ref_dim != 4) return RDETR_ERR_INVALID_ARG;
+    if (B == 0 || Nq == 0) return RDETR_OK;
+    if (!value || !shapes || !level_start || !offsets || !logits || !ref || !grad_out || !grad_value || !grad_offsets || !grad_logits ||
+        S == 0)
+        return RDETR_ERR_INVALID_ARG;
+    if (H != kBH || D != kBD || P != kBP || L > kBMaxL) return RDETR_ERR_UNSUPPORTED;
+    auto al = [](const void *p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
+    if (!(al(value, 16) && al(grad_value, 16) && al(grad_out, sizeof(T)) && al(offsets, 2 * sizeof(T)) && al(logits, sizeof(T)) &&
+          al(grad_offsets, 2 * sizeof(T)) && al(grad_logits, sizeof(T)) && al(ref, 16) && al(grad_ref_partial, 16) &&
+          (!workspace || al(workspace, 16))))
+        return RDETR_ERR_INVALID_ARG;
+    if ((long long)S * kBPixelBytes >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
+    const int tiles = (Nq + 2 * kBWaves - 1) / (2 * kBWaves);
+    const long long nblk = (long long)B * kBH * tiles;
+    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!workspace) {
+        hipLaunchKernelGGL((msda_bwd_fused_kernel<T, false>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes,
+                           level_start, offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, (int)nblk, grad_value, grad_offsets,
+                           grad_logits, grad_ref_partial, nullptr, nullptr, nullptr);
+        return launch_status();
+    }
+    // deterministic mode: the workspace of rdetr_msda_backward_det_f32 (same record count).  Records + sorted copies are 20 bytes
+    // per sample corner: a workspace below that is refused before hipCUB is asked for its temporary storage
+    const long long ncorner = (long long)B * Nq * kBH * L * kBP * 4;
+    if (ncorner >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
+    if (workspace_bytes < ncorner * 20) return RDETR_ERR_INVALID_ARG;
+    DetLayout d;
+    if (!det_layout(B, S, L, Nq, d)) return RDETR_ERR_UNSUPPORTED;
+    if (workspace_bytes < (long long)d.total) return RDETR_ERR_INVALID_ARG;
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    unsigned *rec_key = reinterpret_cast<unsigned *>(ws + d.off_key), *rec_id = reinterpret_cast<unsigned *>(ws + d.off_id);
+    float *rec_w = reinterpret_cast<float *>(ws + d.off_w);
+    unsigned *skey = reinterpret_cast<unsigned *>(ws + d.off_skey), *sid = reinterpret_cast<unsigned *>(ws + d.off_sid);
+    hipLaunchKernelGGL((msda_bwd_fused_kernel<T, true>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes, level_start,
+                       offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, (int)nblk, grad_value, grad_offsets, grad_logits,
+                       grad_ref_partial, rec_key, rec_id, rec_w);
+    if (launch_status() != RDETR_OK) return RDETR_ERR_LAUNCH;
+    size_t tmp = d.tmp_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(ws + d.off_tmp, tmp, rec_key, skey, rec_id, sid, (int)d.nrec, 0, d.key_bits, st) != hipSuccess)
+        return RDETR_ERR_LAUNCH;
+    hipLaunchKernelGGL(msda_bwd_segment_sum_kernel<T>, dim3((unsigned)((d.nrows + 7) / 8)), dim3(256), 0, st, skey, sid, rec_w, grad_out,
+                       d.nrec, d.nrows, L * kBP, grad_value);
+    return launch_status();
+}
+
+extern "C" int rdetr_msda_backward_fused_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                             const float *sampling_offsets, const float *attn_logits, const float *reference_points,
+                                             int ref_dim, const float *grad_out, int B, int S, int H, int D, int L, int Nq, int P,
+                                             void *workspace, long long workspace_bytes, float *grad_value, float *grad_offsets,
+                                             float *grad_logits, float *grad_ref_partial, void *stream)
+{
+    return msda_backward_fused<float>(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, ref_dim,
+                                      grad_out, B, S, H, D, L, Nq, P, workspace, workspace_bytes, grad_value, grad_offsets, grad_logits,
+                                      grad_ref_partial, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rdetr_msda_backward_fused_bf16(const uint16_t *value, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                              const uint16_t *sampling_offsets, const uint16_t *attn_logits, const float *reference_points,
+                                              int ref_dim, const uint16_t *grad_out, int B, int S, int H, int D, int L, int Nq, int P,
+                                              void *workspace, long long workspace_bytes, float *grad_value, uint16_t *grad_offsets,
+                                              uint16_t *grad_logits, float *grad_ref_partial, void *stream)
+{
+    return msda_backward_fused<uint16_t>(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
+                                         ref_dim, grad_out, B, S, H, D, L, Nq, P, workspace, workspace_bytes, grad_value, grad_offsets,
+                                         grad_logits, grad_ref_partial, static_cast<hipStream_t>(stream));
 }

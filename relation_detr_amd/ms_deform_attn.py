@@ -213,6 +213,12 @@ class MultiScaleDeformableAttention(nn.Module):
             core = ops.ms_deform_attn_forward_fused(
                 v.to(core_dtype).contiguous(), spatial_shapes, level_start_index, offsets.to(core_dtype).contiguous(),
                 logits.to(core_dtype).contiguous(), reference_points.float().contiguous())
+        elif (needs_grad and self.options.msda_train_fused and v.is_cuda and core_dtype in (torch.float32, torch.bfloat16)
+                and ops.msda_fast_path(self.num_heads, self.embed_dim // self.num_heads, self.num_levels, self.num_points)):
+            # training on the fused path: softmax + locations inside the gather kernel and its backward, nothing materialised
+            core = ops.MultiScaleDeformableAttnFusedFunction.apply(
+                v.to(core_dtype).contiguous(), spatial_shapes, level_start_index, offsets.to(core_dtype).contiguous(),
+                logits.to(core_dtype).contiguous(), reference_points.float().contiguous())
         else:
             weights = logits.softmax(-1).view(*offsets.shape[:5])
             loc = sampling_locations(reference_points, offsets, spatial_shapes, self.num_points)

@@ -316,7 +316,7 @@ def ms_deform_attn_forward_fused(value: torch.Tensor, spatial_shapes: torch.Tens
         raise ValueError("algo must be 'auto', 'direct', 'window' or 'resident'")
     if value.dtype not in (torch.float32, torch.bfloat16):
         raise _lib.RdetrError(f"value dtype {value.dtype} not supported (float32 or bfloat16)")
-    if value.dtype == torch.float32 and (value_layout != "bshd" or algo != "auto"):
+    if value.dtype == torch.float32 and (value_layout != "bshd" or algo not in ("auto", "direct")):    # fp32: the direct kernel only
         raise _lib.RdetrError("value_layout / algo options exist for bfloat16 value only")
     check_levels(spatial_shapes, level_start_index, S)
     lib = _lib.load()
@@ -437,6 +437,86 @@ class MultiScaleDeformableAttnFunction(torch.autograd.Function):
         gv, gl, ga = ms_deform_attn_backward(value.float(), shapes, starts, loc, attn, grad_output.float(),
                                              ctx.im2col_step)
         return gv.to(value.dtype), None, None, gl, ga, None
+
+
+def ms_deform_attn_backward_fused(value: torch.Tensor, spatial_shapes: torch.Tensor, level_start_index: torch.Tensor,
+                                  sampling_offsets: torch.Tensor, attn_logits: torch.Tensor, reference_points: torch.Tensor,
+                                  grad_output: torch.Tensor, deterministic: Optional[bool] = None, need_ref_grad: bool = False):
+    """Gradients of ``ms_deform_attn_forward_fused`` with respect to its own inputs (csrc/msda_bwd.hip, fused-producer backward)
+    -> [grad_value (fp32), grad_offsets, grad_logits (value's dtype), grad_reference_points (fp32, summed over heads) or None].
+    value [B,S,8,32] fp32|bf16, sampling_offsets [B,Nq,8,L,4,2] and attn_logits [B,Nq,8,L*4] in value's dtype, reference_points
+    [B,Nq,L,2|4] fp32, grad_output [B,Nq,256].  ``deterministic`` (default ``torch.are_deterministic_algorithms_enabled()``):
+    grad_value through sorted per-row sums instead of float atomics; the other gradients are the same bits either way."""
+    _require_device(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, grad_output)
+    if value.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.RdetrError(f"value dtype {value.dtype} not supported (float32 or bfloat16)")
+    if value.dim() != 4 or sampling_offsets.dim() != 6 or reference_points.dim() != 4:
+        raise _lib.RdetrError("expected value [B,S,H,D], sampling_offsets [B,Nq,H,L,P,2], reference_points [B,Nq,L,2|4]")
+    B, S, H, D = value.shape
+    _, Nq, H2, L, P, two = sampling_offsets.shape
+    ref_dim = reference_points.shape[-1]
+    if (H2, two) != (H, 2) or sampling_offsets.shape[0] != B or tuple(attn_logits.shape) != (B, Nq, H, L * P):
+        raise _lib.RdetrError("sampling_offsets / attn_logits shapes do not match value")
+    if tuple(reference_points.shape[:3]) != (B, Nq, L) or ref_dim not in (2, 4):
+        raise _lib.RdetrError("reference_points must be [B, Nq, L, 2|4]")
+    if tuple(grad_output.shape) != (B, Nq, H * D):
+        raise _lib.RdetrError("grad_output must be [B, Nq, H*D]")
+    if (sampling_offsets.dtype != value.dtype or attn_logits.dtype != value.dtype or grad_output.dtype != value.dtype
+            or reference_points.dtype != torch.float32):
+        raise _lib.RdetrError("sampling_offsets / attn_logits / grad_output must have value's dtype, reference_points float32")
+    if spatial_shapes.shape[0] != L:
+        raise _lib.RdetrError("spatial_shapes has a different number of levels than sampling_offsets")
+    if not msda_fast_path(H, D, L, P):
+        raise _lib.RdetrError("ms_deform_attn_backward_fused: H = 8, D = 32, P = 4, L <= 8 only")
+    grad_output = grad_output.contiguous()
+    _require_contiguous(value=value, spatial_shapes=spatial_shapes, level_start_index=level_start_index,
+                        sampling_offsets=sampling_offsets, attn_logits=attn_logits, reference_points=reference_points)
+    check_levels(spatial_shapes, level_start_index, S)
+    if deterministic is None:
+        deterministic = torch.are_deterministic_algorithms_enabled()
+    lib = _lib.load()
+    ws, nbytes = None, 0
+    if deterministic and B * Nq > 0:
+        nbytes = int(lib.rdetr_msda_backward_det_workspace_bytes(B, S, H, D, L, Nq, P))
+        if nbytes <= 0:
+            raise _lib.RdetrError("deterministic ms_deform_attn_backward_fused: fewer than 2^31 sample corners only")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
+    # atomic mode adds into grad_value; the deterministic mode writes every row (nothing runs when B * Nq == 0)
+    grad_value = torch.empty(value.shape, dtype=torch.float32, device=value.device) if ws is not None else \
+        torch.zeros(value.shape, dtype=torch.float32, device=value.device)
+    grad_off = torch.empty_like(sampling_offsets)
+    grad_lg = torch.empty_like(attn_logits)
+    grad_ref = torch.empty(B, Nq, H, L, ref_dim, dtype=torch.float32, device=value.device) if need_ref_grad else None
+    fn = lib.rdetr_msda_backward_fused_bf16 if value.dtype == torch.bfloat16 else lib.rdetr_msda_backward_fused_f32
+    st = fn(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_offsets.data_ptr(),
+            attn_logits.data_ptr(), reference_points.data_ptr(), ref_dim, grad_output.data_ptr(), B, S, H, D, L, Nq, P,
+            None if ws is None else ws.data_ptr(), nbytes, grad_value.data_ptr(), grad_off.data_ptr(), grad_lg.data_ptr(),
+            None if grad_ref is None else grad_ref.data_ptr(), _stream_ptr(value))
+    _lib.check(st, "rdetr_msda_backward_fused")
+    return [grad_value, grad_off, grad_lg, None if grad_ref is None else grad_ref.sum(2)]
+
+
+class MultiScaleDeformableAttnFusedFunction(torch.autograd.Function):
+    """Differentiable fused-producer MSDA core (training mode of the fused path): forward = ``ms_deform_attn_forward_fused`` on
+    the direct kernel (the eval path's bits), backward = ``ms_deform_attn_backward_fused``.  Inputs: value [B,S,8,32] fp32|bf16,
+    the level tables, raw sampling_offsets / attn_logits in value's dtype, reference_points fp32 (ms_deform_attn.py:322-370)."""
+
+    @staticmethod
+    def forward(ctx, value, value_spatial_shapes, value_level_start_index, sampling_offsets, attn_logits, reference_points):
+        out = ms_deform_attn_forward_fused(value, value_spatial_shapes, value_level_start_index, sampling_offsets, attn_logits,
+                                           reference_points, value_layout="bshd", algo="direct")
+        ctx.save_for_backward(value, value_spatial_shapes, value_level_start_index, sampling_offsets, attn_logits,
+                              reference_points)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_output):
+        value, shapes, starts, offsets, logits, ref = ctx.saved_tensors
+        gv, go, gl, gr = ms_deform_attn_backward_fused(value, shapes, starts, offsets, logits, ref, grad_output.to(value.dtype),
+                                                       need_ref_grad=ctx.needs_input_grad[5])
+        return (gv.to(value.dtype) if ctx.needs_input_grad[0] else None, None, None, go if ctx.needs_input_grad[3] else None,
+                gl if ctx.needs_input_grad[4] else None, gr)
 
 
 def relation_bias(src_boxes: torch.Tensor, tgt_boxes: torch.Tensor, proj_weight: torch.Tensor,

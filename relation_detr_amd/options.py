@@ -43,6 +43,9 @@ class Options:
     merged_proj: bool = True         # sampling_offsets + attention_weights as one GEMM
     proj_ln: bool = True             # output_proj + residual + LayerNorm in one kernel
     encoder_proj: bool = True        # value_proj (head-major) + the merged query projection of an encoder layer in one kernel
+    msda_train_fused: bool = False   # training: softmax + locations inside the gather and its backward (MultiScaleDeformableAttnFusedFunction)
+                                     # instead of the torch producer + MultiScaleDeformableAttnFunction (opt-in; core fwd + bwd 0.57-0.97x
+                                     # the old route's time at every measured shape, profiles/r05/msda_train_fused_ab.txt)
 
     @classmethod
     def from_env(cls, env: Mapping[str, str] = os.environ) -> "Options":
