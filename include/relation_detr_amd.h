@@ -331,6 +331,31 @@ int rdetr_relation_attention_bf16(const uint16_t *q, const uint16_t *k, const ui
                                   const float *bias, const uint8_t *bool_mask, int B, int H, int D, int N, int M,
                                   float scale, uint16_t *out, int ldo, void *stream);
 
+/* Training forward: the same kernel and the same out bits as rdetr_relation_attention_bf16, plus the per-row log-sum-exp
+ *   lse   fp32 [B*H, N], LOG2 domain: lse[bh * N + n] = log2(sum_m exp2((s * scale + bias) * log2(e))) (-inf for a fully masked
+ *         row); natural log = lse * ln(2).  rdetr_relation_attention_backward_bf16 takes it as written.
+ * B, H, N, M > 0, row strides >= H * D (RDETR_ERR_INVALID_ARG otherwise); D = 32 only. */
+int rdetr_relation_attention_train_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                        const float *bias, const uint8_t *bool_mask, int B, int H, int D, int N, int M,
+                                        float scale, uint16_t *out, int ldo, float *lse, void *stream);
+
+/* Backward of the training forward (csrc/attn_bwd.hip, FlashAttention-2 shaped, deterministic: no float atomics).
+ *   q, k, v, ld*, bias, bool_mask, B, H, D, N, M, scale   as given to the forward;  out / ldo and lse what it wrote
+ *   dout  bf16 [B, N, ..] with row stride lddo (16-byte aligned, lddo % 8 == 0)
+ *   workspace   rdetr_relation_attention_backward_workspace_bytes(B, H, N) bytes, 16-byte aligned (Di = rowsum(dout o out))
+ *   dq [B, N, ..], dk / dv [B, M, ..]   bf16, written with row strides lddq / lddk / lddv (every row, head columns only): dq and
+ *         dk may be the two halves of one packed [B, N, 2C] buffer (ld = 2C, dk = dq + C) when N == M
+ *   dbias fp32 [B*H, N, M] or NULL: the gradient of the attention logits (= of the bias), every element written once;
+ *         0 at -inf bias entries and masked keys
+ * A fully masked row contributes nothing to dk / dv; its own dq row and dbias row are 0.  B, H, N, M > 0, row strides
+ * >= H * D, a large enough workspace (RDETR_ERR_INVALID_ARG otherwise); D = 32 only. */
+long long rdetr_relation_attention_backward_workspace_bytes(int B, int H, int N);
+int rdetr_relation_attention_backward_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                           const uint16_t *out, int ldo, const float *lse, const uint16_t *dout, int lddo,
+                                           const float *bias, const uint8_t *bool_mask, int B, int H, int D, int N, int M,
+                                           float scale, void *workspace, long long workspace_bytes, uint16_t *dq, int lddq,
+                                           uint16_t *dk, int lddk, uint16_t *dv, int lddv, float *dbias, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The same attention with the relation bias GENERATED INSIDE the kernel from the boxes (SURVEY.md section 8 f1 as written):
  *   out = softmax(Q K^T * attn_scale + relu(W . sine(box_rel_encoding(src_boxes, tgt_boxes)) + b) [, bool mask]) V

@@ -7,12 +7,14 @@ from .ms_deform_attn import MultiScaleDeformableAttention
 from .relation import PositionRelationEmbedding, PositionRelationEncoder, box_rel_encoding
 from .self_attn import RelationSelfAttention
 from .transformer import RelationTransformer, build_relation_transformer, select_detections
-from .ops import (MultiScaleDeformableAttnFunction, MultiScaleDeformableAttnFusedFunction, bias_softmax_, ms_deform_attn_backward,
-                  ms_deform_attn_backward_fused, ms_deform_attn_forward, ms_deform_attn_forward_fused, relation_bias)
+from .ops import (MultiScaleDeformableAttnFunction, MultiScaleDeformableAttnFusedFunction, RelationAttentionFunction, bias_softmax_,
+                  ms_deform_attn_backward, ms_deform_attn_backward_fused, ms_deform_attn_forward, ms_deform_attn_forward_fused,
+                  relation_attention_backward, relation_attention_train, relation_bias)
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
     "RelationSelfAttention", "RelationTransformer", "build_relation_transformer", "select_detections",
     "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttnFusedFunction", "ms_deform_attn_forward",
     "ms_deform_attn_forward_fused", "ms_deform_attn_backward", "ms_deform_attn_backward_fused", "relation_bias", "bias_softmax_",
+    "RelationAttentionFunction", "relation_attention_train", "relation_attention_backward",
 ]

@@ -41,11 +41,14 @@ constexpr int kAtAhead = 4;              // chunks of bias a wave keeps in fligh
 // and the bias of its next chunks already in flight; the four partial results are merged through LDS at the end.
 // (The first version gave each wave 16 queries and ALL keys: at the decoder's size -- 900 keys = 15 chunks -- every wave ran a serial
 // chain of 15 x ~2.6 us whatever the occupancy, and the kernel took 40-50 us with the chip nearly idle.)
-template <int S>          // S = waves that share 16 queries and split their keys (1, 2, 4): more for fewer queries in the launch
+// kLse (training forward): also write the row's log-sum-exp in the log2 domain, lse2[bh * N + q] = log2(sum_key exp2(z)) with
+// z = (s * scale + bias) * log2(e) as below (-inf for a fully masked row); everything before that store is the same code.
+template <int S,          // S = waves that share 16 queries and split their keys (1, 2, 4): more for fewer queries in the launch
+          bool kLse = false>
 __global__ __launch_bounds__(kAtWaves *kWave) void relation_attention_kernel(
     const uint16_t *__restrict__ q, const uint16_t *__restrict__ k, const uint16_t *__restrict__ v, int ldq, int ldk, int ldv,
     const float *__restrict__ bias, const unsigned char *__restrict__ mask, int H, int N, int M, float scale_log2e,
-    uint16_t *__restrict__ out, int ldo)
+    uint16_t *__restrict__ out, int ldo, float *__restrict__ lse2)
 {
     __shared__ __attribute__((aligned(16))) unsigned char at_lds[kAtWaves * kAtWaveLds];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -253,8 +256,38 @@ __global__ __launch_bounds__(kAtWaves *kWave) void relation_attention_kernel(
             uint16_t *o = out + ((size_t)b * N + qi) * ldo + h * kAtD + 4 * g;
             *reinterpret_cast<u32x2 *>(o) = u32x2{pack_bf16x2(o0.x * inv, o0.y * inv), pack_bf16x2(o0.z * inv, o0.w * inv)};
             *reinterpret_cast<u32x2 *>(o + 16) = u32x2{pack_bf16x2(o1.x * inv, o1.y * inv), pack_bf16x2(o1.z * inv, o1.w * inv)};
+            if constexpr (kLse) {
+                if (g == 0) lse2[(size_t)bh * N + qi] = m_all + log2f(l);     // l = 0: -inf, like m_all of a fully masked row
+            }
         }
     }
+}
+
+// Launch of the kernel above for the inference (kLse = false) and training (kLse = true) entry points; arguments checked by the
+// callers.
+template <bool kLse>
+static int launch_relation_attention(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                     const float *bias, const uint8_t *bool_mask, int B, int H, int N, int M, float scale,
+                                     uint16_t *out, int ldo, float *lse2, void *stream)
+{
+    const long long bh = (long long)B * H;
+    // waves per 16 queries: the fewer queries the launch has, the more ways their keys are split (a wave's pass over 64 keys is a
+    // ~2.6-us latency chain: 900 keys in one wave are 40 us however idle the chip is)
+    const long long groups = ((long long)N + kAtTileQ - 1) / kAtTileQ, total = groups * bh;
+    const int split = total <= 512 ? 4 : (total <= 1024 ? 2 : 1);       // measured at N = M = 900: B = 2 (912
+                                                                // groups): 40.8 / 26.3 / 28.3 us for 1 / 2 / 4; B = 4: 46.4 / 49.1 / 52.4
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float sl = scale * 1.4426950408889634f;
+    if (split == 4)
+        hipLaunchKernelGGL((relation_attention_kernel<4, kLse>), dim3((unsigned)groups, (unsigned)bh), dim3(kAtWaves * kWave), 0, st, q,
+                           k, v, ldq, ldk, ldv, bias, bool_mask, H, N, M, sl, out, ldo, lse2);
+    else if (split == 2)
+        hipLaunchKernelGGL((relation_attention_kernel<2, kLse>), dim3((unsigned)((groups + 1) / 2), (unsigned)bh),
+                           dim3(kAtWaves * kWave), 0, st, q, k, v, ldq, ldk, ldv, bias, bool_mask, H, N, M, sl, out, ldo, lse2);
+    else
+        hipLaunchKernelGGL((relation_attention_kernel<1, kLse>), dim3((unsigned)((groups + 3) / 4), (unsigned)bh),
+                           dim3(kAtWaves * kWave), 0, st, q, k, v, ldq, ldk, ldv, bias, bool_mask, H, N, M, sl, out, ldo, lse2);
+    return launch_status();
 }
 
 }  // namespace rdetr
@@ -272,23 +305,24 @@ extern "C" int rdetr_relation_attention_bf16(const uint16_t *q, const uint16_t *
     auto al = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
     if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(out, 8) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || (bias && !al(bias, 4)))
         return RDETR_ERR_UNSUPPORTED;
-    const long long bh = (long long)B * H;
-    if (bh > 65535) return RDETR_ERR_UNSUPPORTED;
-    // waves per 16 queries: the fewer queries the launch has, the more ways their keys are split (a wave's pass over 64 keys is a
-    // ~2.6-us latency chain: 900 keys in one wave are 40 us however idle the chip is)
-    const long long groups = ((long long)N + kAtTileQ - 1) / kAtTileQ, total = groups * bh;
-    const int split = total <= 512 ? 4 : (total <= 1024 ? 2 : 1);       // measured at N = M = 900: B = 2 (912
-                                                                // groups): 40.8 / 26.3 / 28.3 us for 1 / 2 / 4; B = 4: 46.4 / 49.1 / 52.4
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const float sl = scale * 1.4426950408889634f;
-    if (split == 4)
-        hipLaunchKernelGGL(relation_attention_kernel<4>, dim3((unsigned)groups, (unsigned)bh), dim3(kAtWaves * kWave), 0, st, q, k, v, ldq,
-                           ldk, ldv, bias, bool_mask, H, N, M, sl, out, ldo);
-    else if (split == 2)
-        hipLaunchKernelGGL(relation_attention_kernel<2>, dim3((unsigned)((groups + 1) / 2), (unsigned)bh), dim3(kAtWaves * kWave), 0, st, q,
-                           k, v, ldq, ldk, ldv, bias, bool_mask, H, N, M, sl, out, ldo);
-    else
-        hipLaunchKernelGGL(relation_attention_kernel<1>, dim3((unsigned)((groups + 3) / 4), (unsigned)bh), dim3(kAtWaves * kWave), 0, st, q,
-                           k, v, ldq, ldk, ldv, bias, bool_mask, H, N, M, sl, out, ldo);
-    return launch_status();
+    if ((long long)B * H > 65535) return RDETR_ERR_UNSUPPORTED;
+    return launch_relation_attention<false>(q, k, v, ldq, ldk, ldv, bias, bool_mask, B, H, N, M, scale, out, ldo, nullptr, stream);
+}
+
+extern "C" int rdetr_relation_attention_train_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk,
+                                                   int ldv, const float *bias, const uint8_t *bool_mask, int B, int H, int D,
+                                                   int N, int M, float scale, uint16_t *out, int ldo, float *lse, void *stream)
+{
+    using namespace rdetr;
+    if (B <= 0 || H <= 0 || N <= 0 || M <= 0) return RDETR_ERR_INVALID_ARG;
+    if (!q || !k || !v || !out || !lse) return RDETR_ERR_INVALID_ARG;
+    if (D != kAtD) return RDETR_ERR_UNSUPPORTED;
+    const long long span = (long long)H * D;
+    if (ldq < span || ldk < span || ldv < span || ldo < span) return RDETR_ERR_INVALID_ARG;
+    auto al = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
+    if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(out, 8) || !al(lse, 4) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 ||
+        (bias && !al(bias, 4)))
+        return RDETR_ERR_UNSUPPORTED;
+    if ((long long)B * H > 65535) return RDETR_ERR_UNSUPPORTED;
+    return launch_relation_attention<true>(q, k, v, ldq, ldk, ldv, bias, bool_mask, B, H, N, M, scale, out, ldo, lse, stream);
 }

@@ -698,6 +698,157 @@ def relation_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_he
     return out
 
 
+_LN2 = 0.6931471805599453
+
+
+def _attention_rows(t: torch.Tensor, n: int):
+    """(tensor, row stride) of a [B, n, C] bf16 operand: a row-strided view as it is, otherwise a contiguous copy."""
+    if (t.stride(2) != 1 or t.stride(1) < t.shape[2] or (t.shape[0] > 1 and t.stride(0) != n * t.stride(1)) or t.stride(1) % 8
+            or t.data_ptr() % 16):
+        t = t.contiguous()
+    return t, t.stride(1)
+
+
+def _attention_train_args(name: str, q, k, v, num_heads: int, bias, mask):
+    _require_device(q, k, v, bias, mask)
+    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
+        raise _lib.RdetrError(f"{name}: q, k, v must be bfloat16")
+    if q.dim() != 3 or k.dim() != 3:
+        raise _lib.RdetrError(f"{name}: q [B,N,C], k / v [B,M,C] expected")
+    B, N, C = q.shape
+    M = k.shape[1]
+    if C % num_heads or k.shape != (B, M, C) or v.shape != (B, M, C):
+        raise _lib.RdetrError(f"{name}: q [B,N,C], k / v [B,M,C] expected")
+    if bias is not None and (bias.dtype != torch.float32 or bias.numel() != B * num_heads * N * M
+                             or bias.dim() not in (3, 4) or tuple(bias.shape[-2:]) != (N, M)):
+        raise _lib.RdetrError(f"{name}: bias must be float32 [B*H, N, M]")
+    if mask is not None and (mask.dtype != torch.bool or tuple(mask.shape) != (N, M)):
+        raise _lib.RdetrError(f"{name}: mask must be bool [N, M]")
+    return B, N, M, C, C // num_heads
+
+
+def _relation_attention_train(q, k, v, num_heads: int, bias=None, mask=None, scale=None):
+    """-> (out [B,N,C] bf16, lse2 fp32 [B*H, N] in the kernel's log2 domain)."""
+    B, N, M, C, D = _attention_train_args("relation_attention_train", q, k, v, num_heads, bias, mask)
+    out = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
+    lse2 = torch.empty(B * num_heads, N, dtype=torch.float32, device=q.device)
+    if B * N == 0:
+        return out, lse2
+    if M == 0:
+        raise _lib.RdetrError("relation_attention_train: no keys")
+    (q, ldq), (k, ldk), (v, ldv) = _attention_rows(q, N), _attention_rows(k, M), _attention_rows(v, M)
+    bias = None if bias is None else bias.contiguous()
+    mask_u8 = None if mask is None else mask.to(torch.uint8).contiguous()
+    st = _lib.load().rdetr_relation_attention_train_bf16(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), ldq, ldk, ldv, None if bias is None else bias.data_ptr(),
+        None if mask_u8 is None else mask_u8.data_ptr(), B, num_heads, D, N, M,
+        float(scale if scale is not None else D ** -0.5), out.data_ptr(), C, lse2.data_ptr(), _stream_ptr(q))
+    _lib.check(st, "rdetr_relation_attention_train_bf16")
+    return out, lse2
+
+
+def relation_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, bias: Optional[torch.Tensor] = None,
+                             mask: Optional[torch.Tensor] = None, scale: Optional[float] = None):
+    """Training forward of ``relation_attention``: the same kernel and output bits, plus the row log-sum-exp of the logits
+    ``Q K^T * scale + bias`` (natural log, fp32 [B*H, N]; -inf for a fully masked row) -> (out [B,N,C] bf16, lse).
+    Same arguments and strided views as ``relation_attention``."""
+    out, lse2 = _relation_attention_train(q, k, v, num_heads, bias, mask, scale)
+    return out, lse2 * _LN2
+
+
+def _relation_attention_backward(q, k, v, out, lse2, dout, num_heads: int, bias=None, mask=None, scale=None,
+                                 need_dbias: bool = False, packed_qk: bool = False):
+    """Backward from the log2-domain lse2 of ``_relation_attention_train`` -> (dq, dk, dv, dbias | None, the packed [B,N,2C]
+    buffer that holds dq and dk | None)."""
+    B, N, M, C, D = _attention_train_args("relation_attention_backward", q, k, v, num_heads, bias, mask)
+    _require_device(out, lse2, dout)
+    if out.shape != (B, N, C) or dout.shape != (B, N, C) or out.dtype != torch.bfloat16:
+        raise _lib.RdetrError("relation_attention_backward: out / dout must be [B, N, C], out bf16")
+    if lse2.dtype != torch.float32 or lse2.numel() != B * num_heads * N:
+        raise _lib.RdetrError("relation_attention_backward: lse must be float32 [B*H, N]")
+    if packed_qk and N != M:
+        raise _lib.RdetrError("relation_attention_backward: packed dq / dk needs N == M")
+    dev = q.device
+    if packed_qk:
+        dqk = torch.empty(B, N, 2 * C, dtype=torch.bfloat16, device=dev)
+        dq, dk, lddq, lddk = dqk[..., :C], dqk[..., C:], 2 * C, 2 * C
+    else:
+        dqk = None
+        dq, dk, lddq, lddk = (torch.empty(B, N, C, dtype=torch.bfloat16, device=dev), torch.empty(B, M, C, dtype=torch.bfloat16, device=dev),
+                              C, C)
+    dv = torch.empty(B, M, C, dtype=torch.bfloat16, device=dev)
+    dbias = torch.empty(B * num_heads, N, M, dtype=torch.float32, device=dev) if need_dbias else None
+    if B * N == 0 or M == 0:
+        for t in (dq, dk, dv, dbias):
+            if t is not None:
+                t.zero_()
+        return dq, dk, dv, dbias, dqk
+    (q, ldq), (k, ldk), (v, ldv) = _attention_rows(q, N), _attention_rows(k, M), _attention_rows(v, M)
+    (out, ldo), (dout, lddo) = _attention_rows(out, N), _attention_rows(dout.to(torch.bfloat16), N)
+    lse2 = lse2.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    mask_u8 = None if mask is None else mask.to(torch.uint8).contiguous()
+    lib = _lib.load()
+    nbytes = int(lib.rdetr_relation_attention_backward_workspace_bytes(B, num_heads, N))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    st = lib.rdetr_relation_attention_backward_bf16(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), ldq, ldk, ldv, out.data_ptr(), ldo, lse2.data_ptr(), dout.data_ptr(), lddo,
+        None if bias is None else bias.data_ptr(), None if mask_u8 is None else mask_u8.data_ptr(), B, num_heads, D, N, M,
+        float(scale if scale is not None else D ** -0.5), ws.data_ptr(), nbytes, dq.data_ptr(), lddq, dk.data_ptr(), lddk,
+        dv.data_ptr(), C, None if dbias is None else dbias.data_ptr(), _stream_ptr(q))
+    _lib.check(st, "rdetr_relation_attention_backward_bf16")
+    return dq, dk, dv, dbias, dqk
+
+
+def relation_attention_backward(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, lse: torch.Tensor,
+                                dout: torch.Tensor, num_heads: int, bias: Optional[torch.Tensor] = None,
+                                mask: Optional[torch.Tensor] = None, scale: Optional[float] = None, need_dbias: bool = False,
+                                packed_qk: bool = False):
+    """Gradients of ``relation_attention_train`` (csrc/attn_bwd.hip; deterministic, no float atomics) from its inputs, its
+    ``out`` and natural-log ``lse`` and the upstream ``dout`` [B,N,C] -> (dq, dk, dv bf16, dbias fp32 [B*H,N,M] or None).
+    ``need_dbias``: also the gradient of the logits (= of the bias).  ``packed_qk`` (N == M): dq and dk are the two halves of
+    one [B, N, 2C] buffer -- the gradient of a packed q / k projection without a concatenation."""
+    _require_device(lse)
+    return _relation_attention_backward(q, k, v, out, lse.float() * (1.0 / _LN2), dout, num_heads, bias, mask, scale, need_dbias,
+                                        packed_qk)[:4]
+
+
+class RelationAttentionFunction(torch.autograd.Function):
+    """Differentiable fused decoder self-attention (bf16, head dim 32): forward = ``relation_attention_train`` (the inference
+    kernel's output bits), backward = ``relation_attention_backward``.  Saves q, k, v, bias, mask, out and the row
+    log-sum-exp -- no [B*H, N, M] tensor of its own.  ``apply(q, k, v, bias, mask, num_heads, scale)``; ``k = None``: q is the
+    packed [B, N, 2C] q / k projection (q = columns :C, k = C:), whose gradient is then produced in one buffer."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, mask, num_heads, scale):
+        packed = k is None
+        if packed:
+            C = q.shape[-1] // 2
+            qq, kk = q[..., :C], q[..., C:]
+        else:
+            qq, kk = q, k
+        out, lse2 = _relation_attention_train(qq, kk, v, num_heads, bias, mask, scale)
+        ctx.save_for_backward(q, k, v, bias, mask, out, lse2)
+        ctx.num_heads, ctx.scale, ctx.packed = num_heads, scale, packed
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        q, k, v, bias, mask, out, lse2 = ctx.saved_tensors
+        if ctx.packed:
+            C = q.shape[-1] // 2
+            qq, kk = q[..., :C], q[..., C:]
+        else:
+            qq, kk = q, k
+        need_dbias = bias is not None and ctx.needs_input_grad[3]
+        dq, dk, dv, dbias, dqk = _relation_attention_backward(qq, kk, v, out, lse2, grad_out, ctx.num_heads, bias, mask, ctx.scale,
+                                                              need_dbias=need_dbias, packed_qk=ctx.packed)
+        if ctx.packed:
+            return dqk, None, dv, dbias, None, None, None
+        return dq, dk, dv, dbias, None, None, None
+
+
 def relation_attention_boxes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, src_boxes: torch.Tensor,
                              tgt_boxes: torch.Tensor, proj_weight: torch.Tensor, proj_bias: Optional[torch.Tensor],
                              mask: Optional[torch.Tensor] = None, scale: Optional[float] = None, num_pos_feats: int = 16,

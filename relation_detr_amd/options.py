@@ -46,6 +46,10 @@ class Options:
     msda_train_fused: bool = False   # training: softmax + locations inside the gather and its backward (MultiScaleDeformableAttnFusedFunction)
                                      # instead of the torch producer + MultiScaleDeformableAttnFunction (opt-in; core fwd + bwd 0.57-0.97x
                                      # the old route's time at every measured shape, profiles/r05/msda_train_fused_ab.txt)
+    # --- self_attn.py ---------------------------------------------------------------------------------------------------
+    attn_train_fused: bool = False   # training, bf16, head dim 32: the decoder self-attention core as the flash-style forward + its
+                                     # backward (RelationAttentionFunction, csrc/attn.hip + csrc/attn_bwd.hip) instead of the GEMM +
+                                     # bias-softmax chain; no [B*H, N, M] probabilities kept for backward (opt-in; profiles/r06/)
 
     @classmethod
     def from_env(cls, env: Mapping[str, str] = os.environ) -> "Options":

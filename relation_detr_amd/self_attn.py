@@ -18,7 +18,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
-from . import ops
+from . import ops, options
 from .relation import DeferredRelationBias
 
 
@@ -58,6 +58,7 @@ class RelationSelfAttention(nn.Module):
         self.out_proj = nn.Linear(embed_dim, embed_dim)
         nn.init.xavier_uniform_(self.in_proj_weight)
         nn.init.zeros_(self.out_proj.bias)
+        self.options = options.get()
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, attn_mask: Optional[Tensor] = None,
                 need_weights: bool = False, key_padding_mask: Optional[Tensor] = None):
@@ -87,6 +88,19 @@ class RelationSelfAttention(nn.Module):
                                                    rel.module.scale)
                 return self.out_proj(ctx), None
             attn_mask = rel.materialize()
+        if (needs_grad and self.options.attn_train_fused and q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16
+                and v.dtype == torch.bfloat16 and d == 32 and (self.dropout == 0.0 or not self.training)
+                and (attn_mask is None or attn_mask.dtype == torch.bool and tuple(attn_mask.shape) == (N, M)
+                     or attn_mask.dtype != torch.bool and attn_mask.numel() == B * H * N * M)):
+            # training, bf16: flash-style forward that keeps only the row log-sum-exp, and its backward (csrc/attn_bwd.hip)
+            is_bool = attn_mask is not None and attn_mask.dtype == torch.bool
+            bias = None if attn_mask is None or is_bool else attn_mask.float().reshape(B * H, N, M)
+            mask = attn_mask if is_bool else None
+            if key is query:                               # q / k as one packed projection: its gradient comes back in one buffer
+                ctx = ops.RelationAttentionFunction.apply(qk, None, v, bias, mask, H, 1.0 / math.sqrt(d))
+            else:
+                ctx = ops.RelationAttentionFunction.apply(q, k, v, bias, mask, H, 1.0 / math.sqrt(d))
+            return self.out_proj(ctx), None
         if (q.is_cuda and q.dtype == torch.bfloat16 and d == 32 and not needs_grad
                 and (attn_mask is None or attn_mask.dtype == torch.bool and attn_mask.dim() == 2
                      or attn_mask.dtype != torch.bool and attn_mask.numel() == B * H * N * M)):
