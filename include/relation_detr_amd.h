@@ -374,6 +374,46 @@ int rdetr_relation_attention_boxes_bf16(const uint16_t *q, const uint16_t *k, co
                                         int N, int M, int F, float rel_scale, float temperature, float eps, float attn_scale,
                                         uint16_t *out, int ldo, void *stream);
 
+/* Training forward of the kernel above: the same out bits as rdetr_relation_attention_boxes_bf16, plus the per-row
+ * log-sum-exp of the logits  Q K^T * attn_scale + relu(bias)  [, mask]
+ *   lse   fp32 [B*H, N], LOG2 domain (as rdetr_relation_attention_train_bf16 writes it; -inf for a fully masked row), 4-byte
+ *         aligned; rdetr_relation_attention_boxes_backward_bf16 takes it as written.
+ * Replaces, for bf16 training, rdetr_relation_bias_f32 + the masked_fill_ of the denoising mask (relation_transformer.py:369-374)
+ * + rdetr_relation_attention_train_bf16: neither the [B, H, N, M] bias nor its ReLU mask exists in HBM.  Refusals as the
+ * inference entry; a NULL lse and B, N or M = 0 are RDETR_ERR_INVALID_ARG. */
+int rdetr_relation_attention_boxes_train_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                              const float *src_boxes, const float *tgt_boxes, const float *proj_weight,
+                                              const float *proj_bias, const uint8_t *bool_mask, int B, int H, int D,
+                                              int N, int M, int F, float rel_scale, float temperature, float eps, float attn_scale,
+                                              uint16_t *out, int ldo, float *lse, void *stream);
+
+/* Backward of that forward (csrc/attn_rel_bwd.hip; deterministic: no float atomics, every output element written once).
+ * Replaces rdetr_relation_attention_backward_bf16 with a dbias output followed by rdetr_relation_bias_backward_f32 (autograd of
+ * relation_transformer.py:520-532 and :452-461): the bias is regenerated from the boxes with the forward kernel's arithmetic,
+ * so the ReLU's active set is the forward's, and the gradient of the 1x1 projection is reduced inside the kernels -- no
+ * [B*H, N, M]-sized tensor (bias, ReLU mask, dbias) is read or written.  Boxes carry no gradient (:527-529).
+ *   q, k, v, ld*, src_boxes, tgt_boxes, proj_weight, proj_bias, bool_mask, B .. attn_scale   as given to the forward;
+ *         out / ldo and lse what it wrote
+ *   dout  bf16 [B, N, ..] with row stride lddo (16-byte aligned, lddo % 8 == 0)
+ *   workspace   rdetr_relation_attention_boxes_backward_workspace_bytes(B, H, N, M) bytes, 16-byte aligned (Di, one
+ *         520-float partial record per image and 16 queries, and from N = 241 on four fp32 [B, M, 2 H D] partials of dk / dv:
+ *         linear in N and M); 0 bytes for an empty problem
+ *   dq [B, N, ..], dk / dv [B, M, ..]   bf16 with row strides lddq / lddk / lddv, 8-byte aligned, ld % 4 == 0: dq and dk may
+ *         be the two halves of one packed [B, N, 2C] buffer (ld = 2C, dk = dq + C) when N == M
+ *   grad_weight fp32 [H, 4F], grad_bias fp32 [H] or NULL   overwritten (no zero-fill by the caller), natural units
+ * A fully masked row contributes nothing to dk / dv / grad_weight / grad_bias; its dq row is 0.
+ * RDETR_ERR_INVALID_ARG: a NULL required pointer, B, H, D, N, M or F <= 0, a row stride below H * D, a short workspace.
+ * RDETR_ERR_UNSUPPORTED: H != 8, D != 32, F != 16, a missed alignment.  All checks precede any HIP call. */
+long long rdetr_relation_attention_boxes_backward_workspace_bytes(int B, int H, int N, int M);
+int rdetr_relation_attention_boxes_backward_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                                 const uint16_t *out, int ldo, const float *lse, const uint16_t *dout, int lddo,
+                                                 const float *src_boxes, const float *tgt_boxes, const float *proj_weight,
+                                                 const float *proj_bias, const uint8_t *bool_mask, int B, int H, int D, int N, int M,
+                                                 int F, float rel_scale, float temperature, float eps, float attn_scale,
+                                                 void *workspace, long long workspace_bytes, uint16_t *dq, int lddq, uint16_t *dk,
+                                                 int lddk, uint16_t *dv, int lddv, float *grad_weight, float *grad_bias,
+                                                 void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Residual add + LayerNorm over the last dimension, one pass (callers either side of the hot path).
  * Replaces the pairs  x + sublayer(x) -> nn.LayerNorm  of the encoder / decoder layers

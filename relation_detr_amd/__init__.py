@@ -10,6 +10,7 @@ from .transformer import RelationTransformer, build_relation_transformer, select
 from .ops import (MultiScaleDeformableAttnFunction, MultiScaleDeformableAttnFusedFunction, RelationAttentionFunction, bias_softmax_,
                   ms_deform_attn_backward, ms_deform_attn_backward_fused, ms_deform_attn_forward, ms_deform_attn_forward_fused,
                   relation_attention_backward, relation_attention_train, relation_bias)
+from .attn_rel_train import RelationAttentionBoxesFunction, relation_attention_boxes_backward, relation_attention_boxes_train
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -17,4 +18,5 @@ __all__ = [
     "MultiScaleDeformableAttnFunction", "MultiScaleDeformableAttnFusedFunction", "ms_deform_attn_forward",
     "ms_deform_attn_forward_fused", "ms_deform_attn_backward", "ms_deform_attn_backward_fused", "relation_bias", "bias_softmax_",
     "RelationAttentionFunction", "relation_attention_train", "relation_attention_backward",
+    "RelationAttentionBoxesFunction", "relation_attention_boxes_train", "relation_attention_boxes_backward",
 ]

@@ -28,8 +28,9 @@
 //   numerics  = the features / table entries are rounded to bf16 (2^-9) for the projection, the weights are not (hi + lo split);
 //               the angles use the hardware log2 / sin / cos (|angle| < 256 revolutions for any box of size >= 1e-5).  This is the
 //               bf16 inference path: its results are held to the same 2^-7 bound against the fp32 oracle as the materialised-bias
-//               attention kernel.  fp32 runs and training keep rdetr_relation_bias_f32 (reference op order, IEEE division,
-//               Cody-Waite sin / cos).
+//               attention kernel.  bf16 training can take the same route (kLse below + csrc/attn_rel_bwd.hip,
+//               Options.rel_train_fused); fp32 runs and training by default keep rdetr_relation_bias_f32 (reference op order,
+//               IEEE division, Cody-Waite sin / cos).
 //   cost      = VALU-bound (one wave-instruction per clock and CU): ~50 issue slots per pair set, 36 of them the quarter-rate
 //               log2 / sin / cos, + ~160 per head and chunk for the soft-max
 #include <type_traits>
@@ -56,11 +57,14 @@ struct RelFreq {
     float cf[8];        // ln 2 * scale / (temperature^(2k/F) * 2 pi): log2 of the encoding -> revolutions
 };
 
+// kLse (training forward): also write the row's log-sum-exp in the log2 domain, lse2[(b * 8 + head) * N + q] = log2(sum_key exp2(z))
+// (-inf for a fully masked row) -- what csrc/attn_rel_bwd.hip differentiates from.  Same out bits either way.
+template <bool kLse = false>
 __global__ __launch_bounds__(kArWaves *kWave) void relation_attention_boxes_kernel(
     const uint16_t *__restrict__ q, const uint16_t *__restrict__ k, const uint16_t *__restrict__ v, int ldq, int ldk, int ldv,
     const float *__restrict__ src, const float *__restrict__ tgt,
     const float *__restrict__ Wp, const float *__restrict__ bp, const unsigned char *__restrict__ mask, int N, int M,
-    float scale_log2e, float eps, RelFreq fr, uint16_t *__restrict__ out, int ldo, int dbg_arg)
+    float scale_log2e, float eps, RelFreq fr, uint16_t *__restrict__ out, int ldo, int dbg_arg, float *__restrict__ lse2)
 {
 #ifdef RDETR_DEV
     const int dbg = dbg_arg;                 // development builds: component-timing mask (tools/attn_rel_components.py)
@@ -339,6 +343,9 @@ __global__ __launch_bounds__(kArWaves *kWave) void relation_attention_boxes_kern
         uint16_t *o = out + ((size_t)b * N + qi) * ldo + h * kArD + 4 * g;
         *reinterpret_cast<u32x2 *>(o) = u32x2{pack_bf16x2(oacc[0].x * inv, oacc[0].y * inv), pack_bf16x2(oacc[0].z * inv, oacc[0].w * inv)};
         *reinterpret_cast<u32x2 *>(o + 16) = u32x2{pack_bf16x2(oacc[1].x * inv, oacc[1].y * inv), pack_bf16x2(oacc[1].z * inv, oacc[1].w * inv)};
+        if constexpr (kLse) {
+            if (g == 0) lse2[((size_t)b * kArH + h) * N + qi] = m_run + log2f(l_run);     // l = 0: -inf, like m_run of a fully masked row
+        }
     }
 }
 
@@ -353,21 +360,27 @@ extern "C" void rdetr_dev_set_attn_rel_dbg(int v) { g_ar_dbg = v; }
 #define RDETR_AR_DBG 0
 #endif
 
-extern "C" int rdetr_relation_attention_boxes_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
-                                                   const float *src_boxes, const float *tgt_boxes, const float *proj_weight,
-                                                   const float *proj_bias, const uint8_t *bool_mask, int B, int H,
-                                                   int D, int N, int M, int F, float rel_scale, float temperature, float eps,
-                                                   float attn_scale, uint16_t *out, int ldo, void *stream)
+// Launch of the kernel above for the inference (kLse = false) and training (kLse = true) entry points
+template <bool kLse>
+static int launch_relation_attention_boxes(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                           const float *src_boxes, const float *tgt_boxes, const float *proj_weight,
+                                           const float *proj_bias, const uint8_t *bool_mask, int B, int H, int D, int N, int M, int F,
+                                           float rel_scale, float temperature, float eps, float attn_scale, uint16_t *out, int ldo,
+                                           float *lse, void *stream)
 {
     using namespace rdetr;
     if (B < 0 || H <= 0 || N < 0 || M < 0 || F <= 0) return RDETR_ERR_INVALID_ARG;
+    if (kLse) {                                     // the training entries take no empty problem and check the row strides
+        const long long span = (long long)H * D;
+        if (B == 0 || N == 0 || M == 0 || D <= 0 || ldq < span || ldk < span || ldv < span || ldo < span) return RDETR_ERR_INVALID_ARG;
+    }
     if (D != kArD || H != kArH || F != kArF) return RDETR_ERR_UNSUPPORTED;
     if (B == 0 || N == 0) return RDETR_OK;
     if (M == 0) return RDETR_ERR_INVALID_ARG;
-    if (!q || !k || !v || !out || !src_boxes || !tgt_boxes || !proj_weight) return RDETR_ERR_INVALID_ARG;
+    if (!q || !k || !v || !out || !src_boxes || !tgt_boxes || !proj_weight || (kLse && !lse)) return RDETR_ERR_INVALID_ARG;
     auto al = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
     if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(out, 8) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || !al(src_boxes, 16) ||
-        !al(tgt_boxes, 16))
+        !al(tgt_boxes, 16) || (kLse && !al(lse, 4)))
         return RDETR_ERR_UNSUPPORTED;
     if (B > 65535 || (long long)M * (ldk > ldv ? ldk : ldv) * 2 >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -376,11 +389,32 @@ extern "C" int rdetr_relation_attention_boxes_bf16(const uint16_t *q, const uint
         const double dim_t = (double)powf(temperature, (float)i * 2.0f / (float)F);       // get_dim_t, position_encoding.py:101-105
         fr.cf[i] = (float)(0.6931471805599453 * (double)rel_scale / (dim_t * 6.283185307179586));
     }
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(relation_attention_boxes_kernel),
+    // a function-local static of a function template: one per instantiation, so each kernel gets its own attribute call
+    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(relation_attention_boxes_kernel<kLse>),
                                                        hipFuncAttributeMaxDynamicSharedMemorySize, kArLdsBytes);
     if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
-    hipLaunchKernelGGL(relation_attention_boxes_kernel, dim3((unsigned)((N + kArTileQ - 1) / kArTileQ), (unsigned)B),
+    hipLaunchKernelGGL(relation_attention_boxes_kernel<kLse>, dim3((unsigned)((N + kArTileQ - 1) / kArTileQ), (unsigned)B),
                        dim3(kArWaves * kWave), kArLdsBytes, st, q, k, v, ldq, ldk, ldv, src_boxes, tgt_boxes,
-                       proj_weight, proj_bias, bool_mask, N, M, attn_scale * 1.4426950408889634f, eps, fr, out, ldo, RDETR_AR_DBG);
+                       proj_weight, proj_bias, bool_mask, N, M, attn_scale * 1.4426950408889634f, eps, fr, out, ldo, RDETR_AR_DBG, lse);
     return launch_status();
+}
+
+extern "C" int rdetr_relation_attention_boxes_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                                   const float *src_boxes, const float *tgt_boxes, const float *proj_weight,
+                                                   const float *proj_bias, const uint8_t *bool_mask, int B, int H,
+                                                   int D, int N, int M, int F, float rel_scale, float temperature, float eps,
+                                                   float attn_scale, uint16_t *out, int ldo, void *stream)
+{
+    return launch_relation_attention_boxes<false>(q, k, v, ldq, ldk, ldv, src_boxes, tgt_boxes, proj_weight, proj_bias, bool_mask, B, H, D,
+                                                  N, M, F, rel_scale, temperature, eps, attn_scale, out, ldo, nullptr, stream);
+}
+
+extern "C" int rdetr_relation_attention_boxes_train_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk,
+                                                         int ldv, const float *src_boxes, const float *tgt_boxes,
+                                                         const float *proj_weight, const float *proj_bias, const uint8_t *bool_mask,
+                                                         int B, int H, int D, int N, int M, int F, float rel_scale, float temperature,
+                                                         float eps, float attn_scale, uint16_t *out, int ldo, float *lse, void *stream)
+{
+    return launch_relation_attention_boxes<true>(q, k, v, ldq, ldk, ldv, src_boxes, tgt_boxes, proj_weight, proj_bias, bool_mask, B, H, D,
+                                                 N, M, F, rel_scale, temperature, eps, attn_scale, out, ldo, lse, stream);
 }

@@ -50,6 +50,10 @@ class Options:
     attn_train_fused: bool = False   # training, bf16, head dim 32: the decoder self-attention core as the flash-style forward + its
                                      # backward (RelationAttentionFunction, csrc/attn.hip + csrc/attn_bwd.hip) instead of the GEMM +
                                      # bias-softmax chain; no [B*H, N, M] probabilities kept for backward (opt-in; profiles/r06/)
+    rel_train_fused: bool = False    # training, bf16, 8 heads of 32: the relation bias generated inside the attention forward AND its
+                                     # backward, pos_proj's gradient reduced there too (RelationAttentionBoxesFunction, csrc/attn_rel.hip +
+                                     # csrc/attn_rel_bwd.hip) instead of bias kernel + masked_fill + RelationAttentionFunction + bias
+                                     # backward; no [B*H, N, M] bias / ReLU mask / dbias in HBM (opt-in; profiles/r08/)
 
     @classmethod
     def from_env(cls, env: Mapping[str, str] = os.environ) -> "Options":

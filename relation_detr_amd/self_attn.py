@@ -19,6 +19,7 @@ from torch import Tensor, nn
 from torch.nn import functional as F
 
 from . import ops, options
+from .attn_rel_train import RelationAttentionBoxesFunction
 from .relation import DeferredRelationBias
 
 
@@ -86,6 +87,18 @@ class RelationSelfAttention(nn.Module):
                 ctx = ops.relation_attention_boxes(q, k, v, H, rel.src_boxes, rel.tgt_boxes, conv.weight, conv.bias, rel.attn_mask,
                                                    1.0 / math.sqrt(d), rel.module.num_pos_feats, rel.module.temperature,
                                                    rel.module.scale)
+                return self.out_proj(ctx), None
+            if (self.options.rel_train_fused and torch.is_grad_enabled() and (needs_grad or conv.weight.requires_grad)
+                    and q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16
+                    and d == 32 and H == 8 and rel.module.num_pos_feats == 16 and (self.dropout == 0.0 or not self.training)
+                    and tuple(rel.src_boxes.shape) == (B, N, 4) and tuple(rel.tgt_boxes.shape) == (B, M, 4)
+                    and (rel.attn_mask is None or rel.attn_mask.dtype == torch.bool and tuple(rel.attn_mask.shape) == (N, M))):
+                # training, bf16, opt-in: the bias is generated inside the attention forward and regenerated inside its backward,
+                # which also reduces pos_proj's gradient (csrc/attn_rel_bwd.hip): no [B*H, N, M] tensor on either pass
+                packed = key is query
+                ctx = RelationAttentionBoxesFunction.apply(
+                    qk if packed else q, None if packed else k, v, rel.src_boxes, rel.tgt_boxes, conv.weight, conv.bias, rel.attn_mask,
+                    H, 1.0 / math.sqrt(d), rel.module.num_pos_feats, rel.module.temperature, rel.module.scale)
                 return self.out_proj(ctx), None
             attn_mask = rel.materialize()
         if (needs_grad and self.options.attn_train_fused and q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16

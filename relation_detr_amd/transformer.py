@@ -365,6 +365,11 @@ class RelationTransformerDecoder(nn.Module):
                         and hasattr(self.position_relation_embedding, "deferred") and self.options.rel_fused):
                     # bf16 inference: hand the next layer the recipe; its attention kernel generates the bias (csrc/attn_rel.hip)
                     pos_relation = self.position_relation_embedding.deferred(src_boxes, tgt_boxes, attn_mask)
+                elif (query.is_cuda and query.dtype == torch.bfloat16 and torch.is_grad_enabled()
+                        and hasattr(self.position_relation_embedding, "deferred") and self.options.rel_train_fused):
+                    # bf16 training, opt-in: the recipe again; the attention forward AND backward generate the bias
+                    # (csrc/attn_rel_bwd.hip), or the layer materialises it when its shape conditions are not met
+                    pos_relation = self.position_relation_embedding.deferred(src_boxes, tgt_boxes, attn_mask)
                 else:
                     pos_relation = self.position_relation_embedding(src_boxes, tgt_boxes).flatten(0, 1)
                     if attn_mask is not None:
