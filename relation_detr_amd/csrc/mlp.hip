@@ -5,26 +5,43 @@
 // next layer's reference points) -- i.e. six library GEMMs of 1,800 rows and two refine launches of the decoder's dependency chain
 // (~8 us each whatever their size) in one launch.
 //
-//   workgroup  512 threads = 8 waves x 32 rows; rows [0, M) are input A, [M, 2M) input B
-//   layers     chained INSIDE the wave: with the output permutation of csrc/ffn.hip a lane (row, g) ends a tile pair u holding
-//              outputs 32 u + 8 g .. + 7 of its row, which -- biased, ReLU'd, rounded to bf16 as the unfused path stores them --
-//              ARE the B operand of the next layer's k-step u.  Nothing changes lanes, nothing goes through LDS.
-//   weights    W1, W2 packed in fragment order (rdetr_linear_pack_k256_bf16), streamed L2 -> LDS by LDS-DMA in two 64-KiB halves
-//              (output tiles 0-7 / 8-15): W2's halves overwrite W1's as soon as every wave is done with them, behind the other
-//              half's MFMAs.  W3 [4, 256] is turned into one zero-padded tile of fragments by the kernel itself.
-//   last layer one 16 x 16 tile; lanes g == 0 hold the row's 4 outputs, add the bias, round to bf16 (as the library GEMM stores
-//              them), refine against the fp32 reference box and store fp32.
+//   workgroup  8 waves x (16 kMlpNB) rows of the concatenated row space: rows [0, M) are input A, [M, 2M) input B (source and
+//              output pointer are chosen per row, so a block may straddle the seam).  The waves split the OUTPUT COLUMNS of the
+//              hidden layers: wave w owns tile pair w (columns 32 w .. 32 w + 31) for all the workgroup's rows.
+//   weights    W1, W2 packed in fragment order (rdetr_linear_pack_k256_bf16).  A fragment is needed by exactly one wave of the
+//              workgroup and goes global -> registers -> MFMA (no LDS staging, no LDS-DMA, no barrier around it): both layers'
+//              16 fragments per wave are requested at the top of the kernel, W2's land behind layer 1.
+//   layers     with the output permutation of csrc/ffn.hip a lane (row, g) ends tile pair u holding outputs 32 u + 8 g .. + 7 of
+//              its row, which -- biased, ReLU'd, rounded to bf16 as the unfused path stores them -- ARE the lane's B operand of
+//              the next layer's k-step u: each wave writes its pair to an LDS image [row block][u][lane] (1-KiB rows,
+//              conflict-free), one __syncthreads(), every wave reads all 8 k-steps.  One image per hidden layer, each written
+//              once per launch, so nothing can be overwritten under a reader.
+//   last layer W3 [4, 256] as one zero-padded tile of fragments built in registers by wave 0, which runs it over the 8 k-steps
+//              of the second image; lanes g == 0 hold the row's 4 outputs, add the bias, round to bf16 (as the library GEMM
+//              stores them), refine against the fp32 reference box and store fp32.
+//   arithmetic every output accumulates the same v_mfma_f32_16x16x32_bf16 products in the same k-step order (s = 0 .. 7) with
+//              the same rounding points as the row-split kernel this replaces: results are bit-identical to it.
+//   history    the previous kernel gave every wave 32 rows and ALL 256 columns: 15 workgroups for 2 x 1,800 rows, both weights
+//              through LDS-DMA into 128 KiB of LDS and read from there by all 8 waves; 22.7 us per call in the stack.
+//   measured   (tools/time_box_head.py, graph replay, us per call; profiles/r09/time_chain_kernels.txt) two-stage call 1 x 1,800
+//              rows 9.1; decoder layer 2 x 600 / 2 x 1,800 / 2 x 3,600 rows 10.0 / 10.1 / 10.4; the row-split kernel in the same
+//              call 19.9 and 20.8 / 21.1 / 21.2; the unfused sequence 19.3 and 29.2 / 29.9 / 34.1.  In the step together with
+//              csrc/qpos.hip: 3.90-3.95 -> 3.76-3.79 ms (ab_stack_chain_kernels.txt).
+//   resources  (hipcc -Rpass-analysis=kernel-resource-usage) 224 VGPRs, no AGPRs, no scratch, no spills, 32 KiB static LDS (was
+//              138 KiB dynamic), 2 waves per SIMD = one 8-wave workgroup per CU.
+//   dropped    16 rows per workgroup (kMlpNB = 1, 180 VGPRs, 225 workgroups at 2 x 1,800 rows): 6.5 and 6.9 / 7.1 / 12.7 us
+//              isolated -- faster while one launch has the chip to itself, slower than 32 rows once the workgroups outnumber
+//              the CUs, which is the stack's situation (both image groups' launches coincide) -- and the step does not tell them
+//              apart (1036-1063 vs 1055-1063 images/s, ab_candidates.txt); 32 rows moves half the weight bytes from L2.
 #include "common.h"
 
 namespace rdetr {
 
 typedef __bf16 mlp_bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kMlpThreads = 512, kMlpWaves = 8, kMlpRows = 32;
-constexpr int kMlpHalf = 8 * 8 * 64 * 16;                 // 64 KiB: 8 tiles x 8 k-steps of 1-KiB fragments
-constexpr int kMlpLdsW3 = 2 * kMlpHalf;                    // 8 KiB: the last layer's single tile
-constexpr int kMlpLdsBias = kMlpLdsW3 + 8 * 64 * 16;       // b1 | b2 (fp32, 256 each) | b3 (4)
-constexpr int kMlpLdsBytes = kMlpLdsBias + (2 * 256 + 4) * 4;
+constexpr int kMlpWaves = 8, kMlpThreads = kMlpWaves * 64;
+constexpr int kMlpNB = 2, kMlpRows = 16 * kMlpNB;         // 16-row N blocks per workgroup (they share every A fragment): 113 workgroups at 2 x 1,800 rows
+constexpr int kMlpImg = kMlpNB * 8 * 64;                  // one exchange image in u32x4: [row block][u][lane]
 
 __global__ __launch_bounds__(kMlpThreads) void box_head_k256_kernel(
     const uint16_t *__restrict__ xa, long long lda, const uint16_t *__restrict__ xb, long long ldb, const uint16_t *__restrict__ pw1,
@@ -32,107 +49,117 @@ __global__ __launch_bounds__(kMlpThreads) void box_head_k256_kernel(
     const uint16_t *__restrict__ b3, const float *__restrict__ ref, int ref_is_logit, float eps, long long M,
     float *__restrict__ out_a, float *__restrict__ out_b)
 {
-    extern __shared__ __attribute__((aligned(16))) unsigned char mlp_lds[];
-    const u32x4 *wl = reinterpret_cast<const u32x4 *>(mlp_lds);
-    u32x4 *w3l = reinterpret_cast<u32x4 *>(mlp_lds + kMlpLdsW3);
-    float *bl = reinterpret_cast<float *>(mlp_lds + kMlpLdsBias);
+    __shared__ __attribute__((aligned(16))) u32x4 img[2 * kMlpImg];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, g = lane >> 4;
     const long long total = xb ? 2 * M : M;
+    const long long row0 = (long long)blockIdx.x * kMlpRows + col;
 
-    // half h (0 | 1) of a packed [256, 256] weight -> LDS half h: 64 fragments, 8 per wave
-    auto issue_half = [&](const uint16_t *packed, int h) {
-        const unsigned lane_off = (unsigned)lane * 16u;
+    u32x4 x[kMlpNB][8];                                                       // the layer's input: B operand, k-step s
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int f = wave * 8 + i;                                       // uniform
-            const unsigned m0v = (unsigned)(h * kMlpHalf + f * 1024);
-            const unsigned char *src = reinterpret_cast<const unsigned char *>(packed) + (size_t)h * kMlpHalf + f * 1024;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(m0v), "v"(lane_off), "s"(src) : "memory", "m0");
-        }
-    };
-    issue_half(pw1, 0);
-    issue_half(pw1, 1);
-    {   // last layer's tile: fragment (k-step s, lane (m, kb)) = W3[m][32 s + 8 kb ..] for m < 4, zeros otherwise
-        const int s = tid >> 6, m = lane & 15, kb = lane >> 4;
-        w3l[tid] = m < 4 ? *reinterpret_cast<const u32x4 *>(w3 + m * 256 + 32 * s + 8 * kb) : u32x4{0u, 0u, 0u, 0u};
-    }
-    if (tid < 256) {
-        bl[tid] = bf16_bits_to_f32(b1[tid]);
-        bl[256 + tid] = bf16_bits_to_f32(b2[tid]);
-    }
-    if (tid < 4) bl[512 + tid] = bf16_bits_to_f32(b3[tid]);
-
-    const long long row0 = ((long long)blockIdx.x * kMlpWaves + wave) * kMlpRows + col;
-    u32x4 x[2][8];                                                            // the layer's input: B operand, k-step s
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-        const long long r = row0 + 16 * cb;
+    for (int cb = 0; cb < kMlpNB; ++cb) {
+        // rows >= total read the last row instead (unconditional loads); a row of the MFMA's N dimension never reaches another
+        // row's outputs, and they store nothing
+        const long long r = row0 + 16 * cb < total ? row0 + 16 * cb : total - 1;
         const uint16_t *p = r < M ? xa + r * lda : xb + (r - M) * ldb;
 #pragma unroll
-        for (int s = 0; s < 8; ++s) x[cb][s] = r < total ? *reinterpret_cast<const u32x4 *>(p + 32 * s + 8 * g) : u32x4{0u, 0u, 0u, 0u};
+        for (int s = 0; s < 8; ++s) x[cb][s] = *reinterpret_cast<const u32x4 *>(p + 32 * s + 8 * g);
     }
+    // this wave's 16 fragments of a packed [256, 256] weight (tiles 2 w, 2 w + 1), in the order the MFMAs take them: k-step s, tile e
+    struct Frags { u32x4 f[16]; };
+    auto fetch = [&](const uint16_t *packed, Frags &w) {
+        const u32x4 *p = reinterpret_cast<const u32x4 *>(packed) + (size_t)wave * 16 * 64 + lane;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w.f[i] = p[((i & 1) * 8 + (i >> 1)) * 64];
+        __builtin_amdgcn_sched_barrier(0);                                    // the loads are issued HERE, not sunk to their MFMAs
+    };
+    Frags w1, w2;
+    fetch(pw1, w1);
+    fetch(pw2, w2);
+    // the 8 bias values of the lane's outputs of pair `wave`, as bf16 pairs (2-byte loads: a bias needs no alignment)
+    auto bias_of = [&](const uint16_t *bias) {
+        const uint16_t *p = bias + 32 * wave + 8 * g;
+        return u32x4{p[0] | (unsigned)p[1] << 16, p[2] | (unsigned)p[3] << 16, p[4] | (unsigned)p[5] << 16, p[6] | (unsigned)p[7] << 16};
+    };
+    const u32x4 bb1 = bias_of(b1), bb2 = bias_of(b2);
+    // the last layer's operands, requested now so that they are there when wave 0 gets to it: W3 [4, 256] as one zero-padded tile,
+    // fragment (k-step s, lane (m, kb)) = W3[m][32 s + 8 kb ..] for m < 4, zeros otherwise (m = col, kb = g); the reference boxes
+    u32x4 w3f[8];
+    f32x4 rf[kMlpNB];
+    {
+        const uint16_t *w3row = w3 + (col < 4 ? col : 0) * 256 + 8 * g;
+#pragma unroll
+        for (int s = 0; s < 8; ++s) w3f[s] = *reinterpret_cast<const u32x4 *>(w3row + 32 * s);
+#pragma unroll
+        for (int cb = 0; cb < kMlpNB; ++cb) {
+            const long long r = row0 + 16 * cb < total ? row0 + 16 * cb : total - 1;
+            rf[cb] = *reinterpret_cast<const f32x4 *>(ref + (r < M ? r : r - M) * 4);
+        }
+    }
+    const f32x4 bb3 = {bf16_bits_to_f32(b3[0]), bf16_bits_to_f32(b3[1]), bf16_bits_to_f32(b3[2]), bf16_bits_to_f32(b3[3])};
+    __builtin_amdgcn_sched_barrier(0);
 
     auto mm = [&](const u32x4 &a, const u32x4 &bq, const f32x4 &c) {
         return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(mlp_bf16x8, a), __builtin_bit_cast(mlp_bf16x8, bq), c, 0, 0, 0);
     };
-    // one hidden layer, tile pairs u0 .. u0 + 3 (one weight half): y[cb][u] = relu(W x + b) as the next layer's operand
-    auto half_layer = [&](int h, const float *bias, const u32x4 (&xin)[2][8], u32x4 (&y)[2][8]) {
+    // one hidden layer, this wave's tile pair: relu(W x + b) rounded to bf16 into the layer's exchange image
+    auto hidden = [&](const Frags &w, const u32x4 &bb, const u32x4 (&xin)[kMlpNB][8], u32x4 *out) {
+        f32x4 acc[2][kMlpNB];
 #pragma unroll
-        for (int uu = 0; uu < 4; ++uu) {
-            const int u = 4 * h + uu;
-            f32x4 acc[2][2] = {{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}};
+        for (int e = 0; e < 2; ++e)
 #pragma unroll
-            for (int s = 0; s < 8; ++s)
+            for (int cb = 0; cb < kMlpNB; ++cb) acc[e][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                for (int e = 0; e < 2; ++e) {
-                    const u32x4 a = wl[((2 * u + e) * 8 + s) * 64 + lane];
-                    acc[e][0] = mm(a, xin[0][s], acc[e][0]);
-                    acc[e][1] = mm(a, xin[1][s], acc[e][1]);
-                }
-            const f32x4 blo = *reinterpret_cast<const f32x4 *>(bias + 32 * u + 8 * g), bhi = *reinterpret_cast<const f32x4 *>(bias + 32 * u + 8 * g + 4);
+        for (int i = 0; i < 16; ++i)
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                const f32x4 lo = acc[0][cb] + blo, hi = acc[1][cb] + bhi;
-                y[cb][u] = u32x4{relu_bf16x2(pack_bf16x2(lo.x, lo.y)), relu_bf16x2(pack_bf16x2(lo.z, lo.w)),
-                                 relu_bf16x2(pack_bf16x2(hi.x, hi.y)), relu_bf16x2(pack_bf16x2(hi.z, hi.w))};
-            }
+            for (int cb = 0; cb < kMlpNB; ++cb) acc[i & 1][cb] = mm(w.f[i], xin[cb][i >> 1], acc[i & 1][cb]);
+        __builtin_amdgcn_sched_barrier(0);
+        const f32x4 blo = {bf16_bits_to_f32(bb.x & 0xffffu), __builtin_bit_cast(float, bb.x & 0xffff0000u),
+                           bf16_bits_to_f32(bb.y & 0xffffu), __builtin_bit_cast(float, bb.y & 0xffff0000u)};
+        const f32x4 bhi = {bf16_bits_to_f32(bb.z & 0xffffu), __builtin_bit_cast(float, bb.z & 0xffff0000u),
+                           bf16_bits_to_f32(bb.w & 0xffffu), __builtin_bit_cast(float, bb.w & 0xffff0000u)};
+#pragma unroll
+        for (int cb = 0; cb < kMlpNB; ++cb) {
+            const f32x4 lo = acc[0][cb] + blo, hi = acc[1][cb] + bhi;
+            out[(cb * 8 + wave) * 64 + lane] = u32x4{relu_bf16x2(pack_bf16x2(lo.x, lo.y)), relu_bf16x2(pack_bf16x2(lo.z, lo.w)),
+                                                     relu_bf16x2(pack_bf16x2(hi.x, hi.y)), relu_bf16x2(pack_bf16x2(hi.z, hi.w))};
         }
     };
+    auto gather = [&](const u32x4 *in, u32x4 (&y)[kMlpNB][8]) {
+#pragma unroll
+        for (int cb = 0; cb < kMlpNB; ++cb)
+#pragma unroll
+            for (int s = 0; s < 8; ++s) y[cb][s] = in[(cb * 8 + s) * 64 + lane];
+    };
 
-    u32x4 y1[2][8], y2[2][8];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                                          // W1, W3 tile, biases in LDS
-    half_layer(0, bl, x, y1);
-    __syncthreads();                                                          // every wave is done with W1's first half
-    issue_half(pw2, 0);                                                       // ... W2's first half lands behind the second half's MFMAs
-    half_layer(1, bl, x, y1);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                                          // W2 half 0 landed; W1 half 1 consumed
-    issue_half(pw2, 1);
-    half_layer(0, bl + 256, y1, y2);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    half_layer(1, bl + 256, y1, y2);
+    u32x4 y[kMlpNB][8];
+    hidden(w1, bb1, x, img);
+    __syncthreads();                                                          // every wave's columns of hidden layer 1
+    gather(img, y);
+    hidden(w2, bb2, y, img + kMlpImg);
+    __syncthreads();                                                          // ... of hidden layer 2
+    if (wave != 0) return;                                                    // no barrier below
 
-    // last layer: one tile, k = the 256 hidden units; lane (row, g = 0) holds outputs 0 .. 3
-    f32x4 d[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    // last layer: one tile, k = the 256 hidden units; lane (row, g = 0) ends holding outputs 0 .. 3
+    gather(img + kMlpImg, y);
+    f32x4 d[kMlpNB];
+#pragma unroll
+    for (int cb = 0; cb < kMlpNB; ++cb) d[cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int s = 0; s < 8; ++s) {
-        const u32x4 a = w3l[s * 64 + lane];
-        d[0] = mm(a, y2[0][s], d[0]);
-        d[1] = mm(a, y2[1][s], d[1]);
+        const u32x4 a = col < 4 ? w3f[s] : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int cb = 0; cb < kMlpNB; ++cb) d[cb] = mm(a, y[cb][s], d[cb]);
     }
     if (g == 0) {
-        const f32x4 bb = *reinterpret_cast<const f32x4 *>(bl + 512);
+        const f32x4 bb = bb3;
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
+        for (int cb = 0; cb < kMlpNB; ++cb) {
             const long long r = row0 + 16 * cb;
             if (r >= total) continue;
             const long long q = r < M ? r : r - M;
-            const f32x4 rf = *reinterpret_cast<const f32x4 *>(ref + q * 4);
             const float dl[4] = {d[cb].x + bb.x, d[cb].y + bb.y, d[cb].z + bb.z, d[cb].w + bb.w};
-            const float rv[4] = {rf.x, rf.y, rf.z, rf.w};
+            const float rv[4] = {rf[cb].x, rf[cb].y, rf[cb].z, rf[cb].w};
             float o[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -171,12 +198,9 @@ extern "C" int rdetr_box_head_k256_bf16(const uint16_t *xa, long long lda, const
     auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
     if (!al(xa) || (xb && !al(xb)) || !al(pw1) || !al(pw2) || !al(w3) || !al(reference) || !al(out_a) || (xb && !al(out_b)))
         return RDETR_ERR_UNSUPPORTED;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(box_head_k256_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kMlpLdsBytes);
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
-    const long long total = xb ? 2 * M : M, nblk = (total + kMlpWaves * kMlpRows - 1) / (kMlpWaves * kMlpRows);
+    const long long total = xb ? 2 * M : M, nblk = (total + kMlpRows - 1) / kMlpRows;
     if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(box_head_k256_kernel, dim3((unsigned)nblk), dim3(kMlpThreads), kMlpLdsBytes, static_cast<hipStream_t>(stream), xa,
+    hipLaunchKernelGGL(box_head_k256_kernel, dim3((unsigned)nblk), dim3(kMlpThreads), 0, static_cast<hipStream_t>(stream), xa,
                        lda, xb, ldb, pw1, b1, pw2, b2, w3, b3, reference, reference_is_logit, eps, M, out_a, out_b);
     return launch_status();
 }

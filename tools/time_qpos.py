@@ -1,12 +1,12 @@
 """rdetr_query_pos_k256_bf16 (csrc/qpos.hip) against the unfused sequence it replaces (4 library GEMMs + scaled_pos), each
-replayed as a HIP graph of 20 back-to-back calls: us per call at 1,800 and 3,600 rows."""
+replayed as a HIP graph of 20 back-to-back calls: us per call at 600, 1,800 and 3,600 rows.  RDETR_LIB_PATH selects the library build."""
 import os
 import sys
 
 import torch
 
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
-from relation_detr_amd import ops  # noqa: E402
+from relation_detr_amd import _lib, ops  # noqa: E402
 from relation_detr_amd.transformer import MLP  # noqa: E402
 
 dev = "cuda:0"
@@ -37,7 +37,8 @@ def timed(fn, reps=20, rounds=30):
 
 
 if __name__ == "__main__":
-  for rows in (1800, 3600):
+  print("library:", _lib.LIB_PATH)
+  for rows in (600, 1800, 3600):
       emb = torch.randn(2, rows // 2, 512, device=dev).to(torch.bfloat16)
       q = torch.randn(2, rows // 2, 256, device=dev).to(torch.bfloat16)
       fused = timed(lambda: ops.query_pos_k256(emb, q, head.layers, scale.layers))
