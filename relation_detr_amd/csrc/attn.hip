@@ -21,14 +21,13 @@
 //   softmax   = online (running max / sum in fp32, exp2 with the log2e fold), P rounded to bf16 for the PV product, fp32
 //               accumulation; a fully masked row yields NaN like torch.softmax.
 //   bias      = fp32 [B*H, N, M], read as 16-byte pieces (4 consecutive keys of one query per lane); bool mask [N, M].
+// The conventions the family shares (key-mask / key-tail rule, transposed operand read, wave-private fence) are in
+// csrc/attn_common.h.
 #include <cstdlib>
 
-#include "common.h"
+#include "attn_common.h"
 
 namespace rdetr {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kAtD = 32;                 // head dim
 constexpr int kAtTileQ = 16, kAtChunk = 64, kAtWaves = 4;
@@ -58,7 +57,6 @@ __global__ __launch_bounds__(kAtWaves *kWave) void relation_attention_kernel(
     const int qi = (blockIdx.x * (kAtWaves / S) + qgrp) * kAtTileQ + ql;
     const bool qok = qi < N;
     const int qc = qok ? qi : N - 1;
-    constexpr float kLog2e = 1.4426950408889634f;
     unsigned char *lds_k = at_lds + wave * kAtWaveLds, *lds_v = lds_k + kAtChunk * kAtKS;
 
     // Q fragment: B operand of the S^T product, B[k = d = 8 g + j][col = q]
@@ -91,11 +89,6 @@ __global__ __launch_bounds__(kAtWaves *kWave) void relation_attention_kernel(
             *reinterpret_cast<u32x4 *>(lds_v + srow * kAtVS + spiece * 16) = vr[i];
         }
     };
-    auto wave_sync = [] {                                   // the LDS image is private to the wave
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
 
     // bias / mask of this lane's 16 (query, key) pairs of a chunk: keys key0 + 16 kb + 4 g + r
     auto load_bias = [&](int key0, f32x4 (&bz)[4]) {
@@ -113,16 +106,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void relation_attention_kernel(
                     t.w = kk + 3 < M ? bias_row[kk + 3] : 0.f;
                 }
             }
-            if (mask_row) {
-                if (kk + 0 < M && mask_row[kk + 0]) t.x = -__builtin_inff();
-                if (kk + 1 < M && mask_row[kk + 1]) t.y = -__builtin_inff();
-                if (kk + 2 < M && mask_row[kk + 2]) t.z = -__builtin_inff();
-                if (kk + 3 < M && mask_row[kk + 3]) t.w = -__builtin_inff();
-            }
-            if (kk + 0 >= M) t.x = -__builtin_inff();          // keys past the end never take part
-            if (kk + 1 >= M) t.y = -__builtin_inff();
-            if (kk + 2 >= M) t.z = -__builtin_inff();
-            if (kk + 3 >= M) t.w = -__builtin_inff();
+            mask_keys(t, kk, M, mask_row);
             bz[kb] = t;
         }
     };
@@ -156,7 +140,7 @@ __global__ __launch_bounds__(kAtWaves *kWave) void relation_attention_kernel(
         for (int kb = 0; kb < 4; ++kb) {
             const u32x4 kf = *reinterpret_cast<const u32x4 *>(lds_k + (16 * kb + ql) * kAtKS + g * 16);
             f32x4 z = {0.f, 0.f, 0.f, 0.f};
-            z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qfrag), z, 0, 0, 0);
+            z = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(kf), as_bf16x8(qfrag), z, 0, 0, 0);
             // work in the log2 domain: (s * scale + bias) * log2(e)
             z.x = z.x * scale_log2e + bz[kb].x * kLog2e;
             z.y = z.y * scale_log2e + bz[kb].y * kLog2e;
@@ -199,19 +183,12 @@ __global__ __launch_bounds__(kAtWaves *kWave) void relation_attention_kernel(
             acc[cb].x *= alpha; acc[cb].y *= alpha; acc[cb].z *= alpha; acc[cb].w *= alpha;
         }
         // O^T += V^T P^T : A[d][k] = V[key(g, j)][16 cb + d] through the transposed read
-        //   lane 4 q' + p of its 16-lane group supplies row key = 32 pair (+16) + 4 g + q', columns 16 cb + 4 p .. + 3
-        const int tq = (lane >> 2) & 3, tp = lane & 3;
 #pragma unroll
         for (int pair = 0; pair < 2; ++pair) {
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
-                const unsigned char *a0 = lds_v + (32 * pair + 4 * g + tq) * kAtVS + cb * 32 + tp * 8;
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(a0));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(a0 + 16 * kAtVS));
-                const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-                const u32x4 vf = {l2.x, l2.y, h2.x, h2.y};
-                acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf[pair]),
-                                                                  acc[cb], 0, 0, 0);
+                const u32x4 vf = tr_rows8<kAtVS>(lds_v, 32 * pair, cb, lane);
+                acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(vf), as_bf16x8(pf[pair]), acc[cb], 0, 0, 0);
             }
         }
         wave_sync();                                        // the wave is done with this chunk's LDS image
@@ -277,7 +254,7 @@ static int launch_relation_attention(const uint16_t *q, const uint16_t *k, const
     const int split = total <= 512 ? 4 : (total <= 1024 ? 2 : 1);       // measured at N = M = 900: B = 2 (912
                                                                 // groups): 40.8 / 26.3 / 28.3 us for 1 / 2 / 4; B = 4: 46.4 / 49.1 / 52.4
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const float sl = scale * 1.4426950408889634f;
+    const float sl = scale * kLog2e;
     if (split == 4)
         hipLaunchKernelGGL((relation_attention_kernel<4, kLse>), dim3((unsigned)groups, (unsigned)bh), dim3(kAtWaves * kWave), 0, st, q,
                            k, v, ldq, ldk, ldv, bias, bool_mask, H, N, M, sl, out, ldo, lse2);
@@ -302,8 +279,8 @@ extern "C" int rdetr_relation_attention_bf16(const uint16_t *q, const uint16_t *
     if (B == 0 || N == 0) return RDETR_OK;
     if (M == 0) return RDETR_ERR_INVALID_ARG;
     if (!q || !k || !v || !out) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
-    if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(out, 8) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 || (bias && !al(bias, 4)))
+    if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(v, 16) || !aligned_to(out, 8) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 ||
+        (bias && !aligned_to(bias, 4)))
         return RDETR_ERR_UNSUPPORTED;
     if ((long long)B * H > 65535) return RDETR_ERR_UNSUPPORTED;
     return launch_relation_attention<false>(q, k, v, ldq, ldk, ldv, bias, bool_mask, B, H, N, M, scale, out, ldo, nullptr, stream);
@@ -319,9 +296,8 @@ extern "C" int rdetr_relation_attention_train_bf16(const uint16_t *q, const uint
     if (D != kAtD) return RDETR_ERR_UNSUPPORTED;
     const long long span = (long long)H * D;
     if (ldq < span || ldk < span || ldv < span || ldo < span) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
-    if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(out, 8) || !al(lse, 4) || ldq % 8 || ldk % 8 || ldv % 8 || ldo % 4 ||
-        (bias && !al(bias, 4)))
+    if (!aligned_to(q, 16) || !aligned_to(k, 16) || !aligned_to(v, 16) || !aligned_to(out, 8) || !aligned_to(lse, 4) || ldq % 8 || ldk % 8 ||
+        ldv % 8 || ldo % 4 || (bias && !aligned_to(bias, 4)))
         return RDETR_ERR_UNSUPPORTED;
     if ((long long)B * H > 65535) return RDETR_ERR_UNSUPPORTED;
     return launch_relation_attention<true>(q, k, v, ldq, ldk, ldv, bias, bool_mask, B, H, N, M, scale, out, ldo, lse, stream);

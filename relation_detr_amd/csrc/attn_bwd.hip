@@ -26,37 +26,17 @@
 // reads, 96 B for the transposed reads (conflict-free, as in the forward), one copy of each tile per kind of read.
 // Masking: -inf bias entries, bool-masked keys and keys past M give P = 0 and dS = 0; a fully masked row (lse2 = -inf) is
 // treated as P = 0 for all of its keys, so its gradients stay inside its own (image, head).
+// The mask rule, the transposed read and bwd_lse are csrc/attn_common.h's; the Di kernel here also serves csrc/attn_rel_bwd.hip
+// (launch_attention_bwd_di), as does the entry point's stride / alignment check (attention_bwd_layout_status).
 #include <cstdlib>
 
-#include "common.h"
+#include "attn_common.h"
 
 namespace rdetr {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kBwD = 32;                 // head dim
 constexpr int kBwTile = 64;              // keys per dkv workgroup, queries per dq workgroup, rows of a staged chunk
 constexpr int kBwRS = 80, kBwTS = 96;    // LDS row strides in bytes: row reads (ds_read_b128), transposed reads (ds_read_b64_tr_b16)
-constexpr float kBwLog2e = 1.4426950408889634f;
-
-__device__ __forceinline__ bf16x8 as_bf16x8(u32x4 x) { return __builtin_bit_cast(bf16x8, x); }
-
-// A / B operand [16 x 32] of a row-major bf16 LDS image (stride kBwTS) read TRANSPOSED: lane (c = lane & 15, g) gets column 16 cb + c
-// of rows row0 + 16 (j >> 2) + 4 g + (j & 3), j = 0..7.  Every lane of the wave must execute it (EXEC all ones).
-__device__ __forceinline__ u32x4 tr_operand(const unsigned char *img, int row0, int cb, int lane)
-{
-    const int g = lane >> 4, tq = (lane >> 2) & 3, tp = lane & 3;
-    const unsigned char *a0 = img + (row0 + 4 * g + tq) * kBwTS + cb * 32 + tp * 8;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(a0));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(a0 + 16 * kBwTS));
-    const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-    return u32x4{l2.x, l2.y, h2.x, h2.y};
-}
-
-
-// lse2 of a row as the backward uses it: a fully masked row (-inf) becomes +inf, so that exp2(z - lse2) = 0 for all its keys
-__device__ __forceinline__ float bwd_lse(float l2) { return l2 == -__builtin_inff() ? __builtin_inff() : l2; }
 
 // Di = rowsum(dO o O) per (image, head, query): one thread per (b, q, h), fixed order over the 32 columns
 __global__ __launch_bounds__(256) void relation_attention_bwd_di_kernel(const uint16_t *__restrict__ out, int ldo,
@@ -80,6 +60,14 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_di_kernel(const ui
         s += bf16_bits_to_f32(a.y >> 16) * bf16_bits_to_f32(c.y >> 16);
     }
     di[(b * H + h) * N + qi] = s;
+}
+
+void launch_attention_bwd_di(const uint16_t *out, int ldo, const uint16_t *dout, int lddo, int B, int H, int N, float *di,
+                             hipStream_t stream)
+{
+    const long long rows = (long long)B * H * N;
+    hipLaunchKernelGGL(relation_attention_bwd_di_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, out, ldo, dout,
+                       lddo, H, N, rows, di);
 }
 
 // dK, dV (and dbias = dS) of 64 keys of one (image, head); see the header comment
@@ -178,7 +166,7 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_dkv_kernel(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int ql = 16 * qb + 4 * g + r, i = 4 * qb + r;
-                const float z = s[r] * scale_log2e + bcur[i] * kBwLog2e;
+                const float z = s[r] * scale_log2e + bcur[i] * kLog2e;
                 const float p = __builtin_amdgcn_exp2f(z - lse_s[ql]);
                 const float ds = p == 0.f ? 0.f : p * (dp[r] - di_s[ql]);
                 pdv[i] = p;
@@ -203,9 +191,9 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_dkv_kernel(
         for (int pair = 0; pair < 2; ++pair) {
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
-                const u32x4 tdo = tr_operand(dt, 32 * pair, cb, lane);
+                const u32x4 tdo = tr_rows8<kBwTS>(dt, 32 * pair, cb, lane);
                 acc_dv[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(tdo), as_bf16x8(pf[pair]), acc_dv[cb], 0, 0, 0);
-                const u32x4 tq = tr_operand(qt, 32 * pair, cb, lane);
+                const u32x4 tq = tr_rows8<kBwTS>(qt, 32 * pair, cb, lane);
                 acc_dk[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(tq), as_bf16x8(sf[pair]), acc_dk[cb], 0, 0, 0);
             }
         }
@@ -290,16 +278,7 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_dq_kernel(
             if constexpr (kReadDs) {
                 if (!qok) t = f32x4{0.f, 0.f, 0.f, 0.f};        // dS read back: keys past M are 0 already
             } else {
-                if (mask_row) {
-                    if (kk + 0 < M && mask_row[kk + 0]) t.x = -__builtin_inff();
-                    if (kk + 1 < M && mask_row[kk + 1]) t.y = -__builtin_inff();
-                    if (kk + 2 < M && mask_row[kk + 2]) t.z = -__builtin_inff();
-                    if (kk + 3 < M && mask_row[kk + 3]) t.w = -__builtin_inff();
-                }
-                if (kk + 0 >= M) t.x = -__builtin_inff();
-                if (kk + 1 >= M) t.y = -__builtin_inff();
-                if (kk + 2 >= M) t.z = -__builtin_inff();
-                if (kk + 3 >= M) t.w = -__builtin_inff();
+                mask_keys(t, kk, M, mask_row);
             }
             bz[kb] = t;
         }
@@ -333,7 +312,7 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_dq_kernel(
                 f32x4 t;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float z = s[r] * scale_log2e + bcur[kb][r] * kBwLog2e;
+                    const float z = s[r] * scale_log2e + bcur[kb][r] * kLog2e;
                     const float p = __builtin_amdgcn_exp2f(z - l2);
                     t[r] = p == 0.f ? 0.f : p * (dp[r] - dd);
                 }
@@ -350,7 +329,7 @@ __global__ __launch_bounds__(256) void relation_attention_bwd_dq_kernel(
         for (int pair = 0; pair < 2; ++pair) {
 #pragma unroll
             for (int cb = 0; cb < 2; ++cb) {
-                const u32x4 tk = tr_operand(kt, 32 * pair, cb, lane);
+                const u32x4 tk = tr_rows8<kBwTS>(kt, 32 * pair, cb, lane);
                 acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(tk), as_bf16x8(sf[pair]), acc[cb], 0, 0, 0);
             }
         }
@@ -381,7 +360,7 @@ extern "C" void rdetr_dev_set_attn_bwd_dq(int v) { g_bwd_dq_mode = v; }
 extern "C" long long rdetr_relation_attention_backward_workspace_bytes(int B, int H, int N)
 {
     if (B <= 0 || H <= 0 || N <= 0) return 0;
-    return ((long long)B * H * N * 4 + 255) / 256 * 256;      // Di, fp32 [B*H, N]
+    return rdetr::attention_di_bytes(B, H, N);                // Di, fp32 [B*H, N]
 }
 
 extern "C" int rdetr_relation_attention_backward_bf16(
@@ -394,24 +373,17 @@ extern "C" int rdetr_relation_attention_backward_bf16(
     if (B <= 0 || H <= 0 || N <= 0 || M <= 0) return RDETR_ERR_INVALID_ARG;
     if (!q || !k || !v || !out || !lse || !dout || !workspace || !dq || !dk || !dv) return RDETR_ERR_INVALID_ARG;
     if (D != kBwD) return RDETR_ERR_UNSUPPORTED;
-    const long long span = (long long)H * D;
-    if (ldq < span || ldk < span || ldv < span || ldo < span || lddo < span || lddq < span || lddk < span || lddv < span)
-        return RDETR_ERR_INVALID_ARG;
-    if (workspace_bytes < rdetr_relation_attention_backward_workspace_bytes(B, H, N)) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; };
-    if (!al(q, 16) || !al(k, 16) || !al(v, 16) || !al(dout, 16) || ldq % 8 || ldk % 8 || ldv % 8 || lddo % 8)
-        return RDETR_ERR_UNSUPPORTED;
-    if (!al(out, 8) || !al(dq, 8) || !al(dk, 8) || !al(dv, 8) || ldo % 4 || lddq % 4 || lddk % 4 || lddv % 4)
-        return RDETR_ERR_UNSUPPORTED;
-    if (!al(lse, 4) || !al(workspace, 16) || (bias && !al(bias, 4)) || (dbias && !al(dbias, 4))) return RDETR_ERR_UNSUPPORTED;
+    const int lay = attention_bwd_layout_status(q, k, v, out, dout, lse, workspace, dq, dk, dv, ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv,
+                                                (long long)H * D, workspace_bytes,
+                                                rdetr_relation_attention_backward_workspace_bytes(B, H, N));
+    if (lay != RDETR_OK) return lay;
+    if ((bias && !aligned_to(bias, 4)) || (dbias && !aligned_to(dbias, 4))) return RDETR_ERR_UNSUPPORTED;
     const long long bh = (long long)B * H;
     if (bh > 65535) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float *di = static_cast<float *>(workspace);
-    const float sl = scale * kBwLog2e;
-    const long long rows = bh * N;
-    hipLaunchKernelGGL(relation_attention_bwd_di_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, out, ldo, dout, lddo,
-                       H, N, rows, di);
+    const float sl = scale * kLog2e;
+    launch_attention_bwd_di(out, ldo, dout, lddo, B, H, N, di, st);
     const dim3 gk((unsigned)((M + kBwTile - 1) / kBwTile), (unsigned)bh), gq((unsigned)((N + kBwTile - 1) / kBwTile), (unsigned)bh);
     if (dbias)
         hipLaunchKernelGGL(relation_attention_bwd_dkv_kernel<true>, gk, dim3(256), 0, st, q, k, v, ldq, ldk, ldv, dout, lddo, lse, di, bias,

@@ -660,44 +660,6 @@ def add_layer_norm(x: torch.Tensor, residual: Optional[torch.Tensor], weight: to
     return out
 
 
-def relation_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, bias: Optional[torch.Tensor] = None,
-                       mask: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
-    """softmax(Q K^T * scale + bias) V per (image, head) in one kernel (bf16, head dim 32, inference).
-    q [B,N,C], k / v [B,M,C] bf16 -- row-strided views are fine (last dim contiguous, image stride = rows * row stride);
-    bias fp32 [B*H,N,M] or None; mask bool [N,M] (True = excluded) or None -> [B,N,C] bf16."""
-    _require_device(q, k, v, bias, mask)
-    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise _lib.RdetrError("relation_attention: q, k, v must be bfloat16")
-    B, N, C = q.shape
-    M = k.shape[1]
-    if C % num_heads or k.shape != (B, M, C) or v.shape != (B, M, C):
-        raise _lib.RdetrError("relation_attention: q [B,N,C], k / v [B,M,C] expected")
-    D = C // num_heads
-
-    def rows(t, n):
-        if t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != n * t.stride(1)):
-            t = t.contiguous()
-        return t, t.stride(1)
-
-    (q, ldq), (k, ldk), (v, ldv) = rows(q, N), rows(k, M), rows(v, M)
-    if bias is not None:
-        if bias.dtype != torch.float32 or bias.numel() != B * num_heads * N * M:
-            raise _lib.RdetrError("relation_attention: bias must be float32 [B*H, N, M]")
-        bias = bias.contiguous()
-    mask_u8 = None
-    if mask is not None:
-        if tuple(mask.shape) != (N, M):
-            raise _lib.RdetrError("relation_attention: mask must be [N, M]")
-        mask_u8 = mask.to(torch.uint8).contiguous()
-    out = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
-    st = _lib.load().rdetr_relation_attention_bf16(
-        q.data_ptr(), k.data_ptr(), v.data_ptr(), ldq, ldk, ldv, None if bias is None else bias.data_ptr(),
-        None if mask_u8 is None else mask_u8.data_ptr(), B, num_heads, D, N, M,
-        float(scale if scale is not None else D ** -0.5), out.data_ptr(), C, _stream_ptr(q))
-    _lib.check(st, "rdetr_relation_attention_bf16")
-    return out
-
-
 _LN2 = 0.6931471805599453
 
 
@@ -709,11 +671,14 @@ def _attention_rows(t: torch.Tensor, n: int):
     return t, t.stride(1)
 
 
-def _attention_train_args(name: str, q, k, v, num_heads: int, bias, mask):
-    _require_device(q, k, v, bias, mask)
+def _attention_operands(name: str, q, k, v, num_heads: int, bias=None, mask=None, boxes=None, proj=None, num_pos_feats: int = 0):
+    """The operand preparation every operator of the attention family starts with (the caller has checked the device): dtype and
+    shape checks of q [B,N,C], k / v [B,M,C] bf16, of the fp32 bias [B*H,N,M], the bool mask [N,M], ``boxes`` = (src [B,N,4],
+    tgt [B,M,4]) and ``proj`` = (weight [H, 4F], bias [H] | None); q, k, v as the kernels take them
+    -> ((B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), the mask as uint8 | None)."""
     if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
         raise _lib.RdetrError(f"{name}: q, k, v must be bfloat16")
-    if q.dim() != 3 or k.dim() != 3:
+    if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
         raise _lib.RdetrError(f"{name}: q [B,N,C], k / v [B,M,C] expected")
     B, N, C = q.shape
     M = k.shape[1]
@@ -722,23 +687,69 @@ def _attention_train_args(name: str, q, k, v, num_heads: int, bias, mask):
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != B * num_heads * N * M
                              or bias.dim() not in (3, 4) or tuple(bias.shape[-2:]) != (N, M)):
         raise _lib.RdetrError(f"{name}: bias must be float32 [B*H, N, M]")
+    if boxes is not None and (tuple(boxes[0].shape) != (B, N, 4) or tuple(boxes[1].shape) != (B, M, 4)):
+        raise _lib.RdetrError(f"{name}: src_boxes [B,N,4] and tgt_boxes [B,M,4] expected")
+    if proj is not None:
+        if proj[0].numel() != num_heads * 4 * num_pos_feats:
+            raise _lib.RdetrError(f"{name}: proj_weight must be [{num_heads}, {4 * num_pos_feats}]")
+        if proj[1] is not None and proj[1].numel() != num_heads:
+            raise _lib.RdetrError(f"{name}: proj_bias must be [{num_heads}]")
     if mask is not None and (mask.dtype != torch.bool or tuple(mask.shape) != (N, M)):
         raise _lib.RdetrError(f"{name}: mask must be bool [N, M]")
-    return B, N, M, C, C // num_heads
+    mask_u8 = None if mask is None else mask.to(torch.uint8).contiguous()
+    return (B, N, M, C, C // num_heads), _attention_rows(q, N), _attention_rows(k, M), _attention_rows(v, M), mask_u8
+
+
+def _attention_grad_buffers(name: str, B: int, N: int, M: int, C: int, device, packed_qk: bool, others=()):
+    """dq [B,N,C], dk, dv [B,M,C] bf16 of a backward; ``packed_qk`` (N == M): dq and dk are the two halves of one [B, N, 2C]
+    buffer.  An empty problem launches nothing: its gradients, ``others`` included, are zeroed here
+    -> (dq, dk, dv, lddq, lddk, the packed buffer | None, empty)."""
+    if packed_qk and N != M:
+        raise _lib.RdetrError(f"{name}: packed dq / dk needs N == M")
+    if packed_qk:
+        dqk = torch.empty(B, N, 2 * C, dtype=torch.bfloat16, device=device)
+        dq, dk, ld = dqk[..., :C], dqk[..., C:], 2 * C
+    else:
+        dqk = None
+        dq, dk, ld = torch.empty(B, N, C, dtype=torch.bfloat16, device=device), torch.empty(B, M, C, dtype=torch.bfloat16, device=device), C
+    dv = torch.empty(B, M, C, dtype=torch.bfloat16, device=device)
+    empty = B * N == 0 or M == 0
+    if empty:
+        for t in (dq, dk, dv) + tuple(others):
+            if t is not None:
+                t.zero_()
+    return dq, dk, dv, ld, ld, dqk, empty
+
+
+def relation_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, bias: Optional[torch.Tensor] = None,
+                       mask: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+    """softmax(Q K^T * scale + bias) V per (image, head) in one kernel (bf16, head dim 32, inference).
+    q [B,N,C], k / v [B,M,C] bf16 -- row-strided views are fine (last dim contiguous, image stride = rows * row stride);
+    bias fp32 [B*H,N,M] or None; mask bool [N,M] (True = excluded) or None -> [B,N,C] bf16."""
+    _require_device(q, k, v, bias, mask)
+    (B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), mask_u8 = _attention_operands("relation_attention", q, k, v, num_heads, bias, mask)
+    bias = None if bias is None else bias.contiguous()
+    out = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
+    st = _lib.load().rdetr_relation_attention_bf16(
+        q.data_ptr(), k.data_ptr(), v.data_ptr(), ldq, ldk, ldv, None if bias is None else bias.data_ptr(),
+        None if mask_u8 is None else mask_u8.data_ptr(), B, num_heads, D, N, M,
+        float(scale if scale is not None else D ** -0.5), out.data_ptr(), C, _stream_ptr(q))
+    _lib.check(st, "rdetr_relation_attention_bf16")
+    return out
 
 
 def _relation_attention_train(q, k, v, num_heads: int, bias=None, mask=None, scale=None):
     """-> (out [B,N,C] bf16, lse2 fp32 [B*H, N] in the kernel's log2 domain)."""
-    B, N, M, C, D = _attention_train_args("relation_attention_train", q, k, v, num_heads, bias, mask)
+    _require_device(q, k, v, bias, mask)
+    (B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), mask_u8 = _attention_operands("relation_attention_train", q, k, v, num_heads, bias,
+                                                                                 mask)
     out = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
     lse2 = torch.empty(B * num_heads, N, dtype=torch.float32, device=q.device)
     if B * N == 0:
         return out, lse2
     if M == 0:
         raise _lib.RdetrError("relation_attention_train: no keys")
-    (q, ldq), (k, ldk), (v, ldv) = _attention_rows(q, N), _attention_rows(k, M), _attention_rows(v, M)
     bias = None if bias is None else bias.contiguous()
-    mask_u8 = None if mask is None else mask.to(torch.uint8).contiguous()
     st = _lib.load().rdetr_relation_attention_train_bf16(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), ldq, ldk, ldv, None if bias is None else bias.data_ptr(),
         None if mask_u8 is None else mask_u8.data_ptr(), B, num_heads, D, N, M,
@@ -760,34 +771,21 @@ def _relation_attention_backward(q, k, v, out, lse2, dout, num_heads: int, bias=
                                  need_dbias: bool = False, packed_qk: bool = False):
     """Backward from the log2-domain lse2 of ``_relation_attention_train`` -> (dq, dk, dv, dbias | None, the packed [B,N,2C]
     buffer that holds dq and dk | None)."""
-    B, N, M, C, D = _attention_train_args("relation_attention_backward", q, k, v, num_heads, bias, mask)
-    _require_device(out, lse2, dout)
+    _require_device(q, k, v, bias, mask, out, lse2, dout)
+    (B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), mask_u8 = _attention_operands("relation_attention_backward", q, k, v, num_heads, bias,
+                                                                                 mask)
     if out.shape != (B, N, C) or dout.shape != (B, N, C) or out.dtype != torch.bfloat16:
         raise _lib.RdetrError("relation_attention_backward: out / dout must be [B, N, C], out bf16")
     if lse2.dtype != torch.float32 or lse2.numel() != B * num_heads * N:
         raise _lib.RdetrError("relation_attention_backward: lse must be float32 [B*H, N]")
-    if packed_qk and N != M:
-        raise _lib.RdetrError("relation_attention_backward: packed dq / dk needs N == M")
     dev = q.device
-    if packed_qk:
-        dqk = torch.empty(B, N, 2 * C, dtype=torch.bfloat16, device=dev)
-        dq, dk, lddq, lddk = dqk[..., :C], dqk[..., C:], 2 * C, 2 * C
-    else:
-        dqk = None
-        dq, dk, lddq, lddk = (torch.empty(B, N, C, dtype=torch.bfloat16, device=dev), torch.empty(B, M, C, dtype=torch.bfloat16, device=dev),
-                              C, C)
-    dv = torch.empty(B, M, C, dtype=torch.bfloat16, device=dev)
     dbias = torch.empty(B * num_heads, N, M, dtype=torch.float32, device=dev) if need_dbias else None
-    if B * N == 0 or M == 0:
-        for t in (dq, dk, dv, dbias):
-            if t is not None:
-                t.zero_()
+    dq, dk, dv, lddq, lddk, dqk, empty = _attention_grad_buffers("relation_attention_backward", B, N, M, C, dev, packed_qk, (dbias,))
+    if empty:
         return dq, dk, dv, dbias, dqk
-    (q, ldq), (k, ldk), (v, ldv) = _attention_rows(q, N), _attention_rows(k, M), _attention_rows(v, M)
     (out, ldo), (dout, lddo) = _attention_rows(out, N), _attention_rows(dout.to(torch.bfloat16), N)
     lse2 = lse2.contiguous()
     bias = None if bias is None else bias.contiguous()
-    mask_u8 = None if mask is None else mask.to(torch.uint8).contiguous()
     lib = _lib.load()
     nbytes = int(lib.rdetr_relation_attention_backward_workspace_bytes(B, num_heads, N))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -857,26 +855,10 @@ def relation_attention_boxes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
     32, 16 sine features per coordinate, inference).  q [B,N,C], k / v [B,M,C] bf16 (row-strided views are fine); src_boxes
     [B,N,4] / tgt_boxes [B,M,4] cxcywh; proj_weight [8, 64(,1,1)], proj_bias [8]; mask bool [N,M] or None -> [B,N,C] bf16."""
     _require_device(q, k, v, src_boxes, tgt_boxes, proj_weight, proj_bias, mask)
-    if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
-        raise _lib.RdetrError("relation_attention_boxes: q, k, v must be bfloat16")
-    B, N, C = q.shape
-    M = k.shape[1]
-    if C % num_heads or k.shape != (B, M, C) or v.shape != (B, M, C):
-        raise _lib.RdetrError("relation_attention_boxes: q [B,N,C], k / v [B,M,C] expected")
-    if tuple(src_boxes.shape) != (B, N, 4) or tuple(tgt_boxes.shape) != (B, M, 4):
-        raise _lib.RdetrError("relation_attention_boxes: src_boxes [B,N,4] and tgt_boxes [B,M,4] expected")
-    D = C // num_heads
-
-    def rows(t, n):
-        if t.stride(2) != 1 or (t.shape[0] > 1 and t.stride(0) != n * t.stride(1)):
-            t = t.contiguous()
-        return t, t.stride(1)
-
-    (q, ldq), (k, ldk), (v, ldv) = rows(q, N), rows(k, M), rows(v, M)
+    (B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), mask_u8 = _attention_operands(
+        "relation_attention_boxes", q, k, v, num_heads, None, mask, (src_boxes, tgt_boxes), (proj_weight, proj_bias), num_pos_feats)
     src = src_boxes.detach().float().contiguous()
     tgt = tgt_boxes.detach().float().contiguous()
-    if proj_weight.numel() != num_heads * 4 * num_pos_feats:
-        raise _lib.RdetrError(f"proj_weight must be [{num_heads}, {4 * num_pos_feats}]")
     # fp32 copies of the projection (the module holds it in the network dtype), kept until a parameter changes: converted per
     # call they were two small launches in every decoder layer's dependency chain
     def f32_copy(t, shape):
@@ -890,11 +872,6 @@ def relation_attention_boxes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
         return _REL_PROJ_F32.get((t,), build)
     w = f32_copy(proj_weight, (num_heads, -1))
     pb = None if proj_bias is None else f32_copy(proj_bias, (-1,))
-    mask_u8 = None
-    if mask is not None:
-        if tuple(mask.shape) != (N, M):
-            raise _lib.RdetrError("relation_attention_boxes: mask must be [N, M]")
-        mask_u8 = mask.to(torch.uint8).contiguous()
     out = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
     st = _lib.load().rdetr_relation_attention_boxes_bf16(
         q.data_ptr(), k.data_ptr(), v.data_ptr(), ldq, ldk, ldv, src.data_ptr(), tgt.data_ptr(), w.data_ptr(),
