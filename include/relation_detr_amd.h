@@ -598,6 +598,18 @@ int rdetr_ffn_k256_bf16(const uint16_t *x, long long ldx, const uint16_t *packed
 int rdetr_ffn_ln_k256_bf16(const uint16_t *x, long long ldx, const uint16_t *packed, const uint16_t *b1, const uint16_t *b2,
                            const uint16_t *gamma, const uint16_t *beta, float eps, const uint16_t *pos, long long ldp,
                            long long M, int F, uint16_t *out, long long ldo, uint16_t *out2, long long ldo2, void *stream);
+/* Training route of the block (bf16).  rdetr_ffn_k256_train_bf16 is rdetr_ffn_k256_bf16 (the same kernel body, the same out bits)
+ * that also stores the hidden activations hid[M, F] = relu(bf16(x w1^T + b1)), rows ldh apart.  rdetr_ffn_k256_backward_bf16 is the
+ * data gradient from those: dh[M, F] = bf16(dy w2) where hid > 0, else 0 (rows ldd apart), and dx[M, 256] = dh w1, accumulated in
+ * fp32 over all of F and rounded once -- the rounding points of autograd over the two library GEMMs.  packed_t is
+ * rdetr_ffn_k256_pack_bf16(w2^T [F, 256], w1^T [256, F]) (contiguous transposed copies).  The weight and bias gradients
+ * (dy^T hid, dh^T x and the column sums) are left to the caller.  ldh, ldd >= F, multiples of 8, 16-byte aligned bases;
+ * M * ldh * 2 and M * ldd * 2 below 2^31 (hid / dh are addressed with 32-bit byte offsets), else RDETR_ERR_UNSUPPORTED.
+ * Rows at or beyond M are neither read nor written.  No atomics: two runs agree bit for bit. */
+int rdetr_ffn_k256_train_bf16(const uint16_t *x, long long ldx, const uint16_t *packed, const uint16_t *b1, const uint16_t *b2,
+                              long long M, int F, uint16_t *out, long long ldo, uint16_t *hid, long long ldh, void *stream);
+int rdetr_ffn_k256_backward_bf16(const uint16_t *dy, long long lddy, const uint16_t *packed_t, const uint16_t *hid, long long ldh,
+                                 long long M, int F, uint16_t *dh, long long ldd, uint16_t *dx, long long lddx, void *stream);
 
 #ifdef __cplusplus
 }

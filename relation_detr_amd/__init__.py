@@ -11,6 +11,7 @@ from .ops import (MultiScaleDeformableAttnFunction, MultiScaleDeformableAttnFuse
                   ms_deform_attn_backward, ms_deform_attn_backward_fused, ms_deform_attn_forward, ms_deform_attn_forward_fused,
                   relation_attention_backward, relation_attention_train, relation_bias)
 from .attn_rel_train import RelationAttentionBoxesFunction, relation_attention_boxes_backward, relation_attention_boxes_train
+from .ffn_train import FeedForwardFunction, ffn_k256_backward, ffn_k256_train
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -19,4 +20,5 @@ __all__ = [
     "ms_deform_attn_forward_fused", "ms_deform_attn_backward", "ms_deform_attn_backward_fused", "relation_bias", "bias_softmax_",
     "RelationAttentionFunction", "relation_attention_train", "relation_attention_backward",
     "RelationAttentionBoxesFunction", "relation_attention_boxes_train", "relation_attention_boxes_backward",
+    "FeedForwardFunction", "ffn_k256_train", "ffn_k256_backward",
 ]

@@ -25,6 +25,9 @@ class Options:
     linear_k256: bool = False        # encoder FFN linear1 through csrc/linear.hip (opt-in: -1 % in the two-group replay)
     ffn_fused: bool = True           # fused feed-forward block (csrc/ffn.hip) for tall bf16 inputs
     ffn_ln: bool = False             # ... with the closing add+LayerNorm in its epilogue (opt-in: 3-6 % slower in the stack)
+    ffn_train_fused: bool = False    # training, tall bf16 inputs: the block's forward (hidden activations saved) and its data gradient as
+                                     # one kernel each (FeedForwardFunction, csrc/ffn.hip) instead of two library GEMMs + ReLU passes per
+                                     # direction; weight gradients stay library GEMMs (opt-in; profiles/r10/)
     ln_pos: bool = True              # encoder: norm2 also emits the next layer's query + pos
     decoder_ln_pos: bool = True      # decoder: norm2 also emits the cross-attention's query + query_pos
     decoder_entry: bool = True       # decoder layer entry (reference scaling + sine embedding, scaled query_pos) as 2 kernels

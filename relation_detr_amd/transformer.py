@@ -23,7 +23,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
-from . import ops
+from . import ffn_train, ops
 from . import options as _options
 from .ms_deform_attn import MultiScaleDeformableAttention
 from .relation import PositionRelationEmbedding
@@ -98,11 +98,24 @@ def _fused_ffn_applies(linear1: nn.Linear, linear2: nn.Linear, x: Tensor, opts: 
             and ops.ffn_k256_supported(x, linear1.weight, linear2.weight))
 
 
+def _fused_ffn_train_applies(linear1: nn.Linear, linear2: nn.Linear, x: Tensor, opts: "_options.Options" = None) -> bool:
+    if not ((opts or _options.get()).ffn_train_fused and x.is_cuda and torch.is_grad_enabled()
+            and linear1.bias is not None and linear2.bias is not None and x.numel() // x.shape[-1] >= _K256_MIN_ROWS):
+        return False
+    params = (linear1.weight, linear1.bias, linear2.weight, linear2.bias)
+    return ((x.requires_grad or any(p.requires_grad for p in params))
+            and ffn_train.ffn_train_supported(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias))
+
+
 def feed_forward(linear1: nn.Linear, linear2: nn.Linear, x: Tensor, opts: "_options.Options" = None) -> Tensor:
     """linear2(relu(linear1(x))) (relation_transformer.py:226-233, 272-275).  Tall bf16 inputs at inference go through the fused
-    kernel (csrc/ffn.hip: the [rows, d_ffn] activations never reach HBM); options.ffn_fused = False keeps the two library GEMMs."""
+    kernel (csrc/ffn.hip: the [rows, d_ffn] activations never reach HBM); options.ffn_fused = False keeps the two library GEMMs.
+    In training, options.ffn_train_fused sends tall bf16 inputs with bf16 parameters through the same kernel body and its data
+    gradient (ffn_train.FeedForwardFunction); everything else -- and the default -- is the two library GEMMs under autograd."""
     if _fused_ffn_applies(linear1, linear2, x, opts):
         return ops.ffn_k256(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
+    if _fused_ffn_train_applies(linear1, linear2, x, opts):
+        return ffn_train.FeedForwardFunction.apply(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
     return linear2(linear_relu(linear1, x, opts))
 
 
