@@ -473,7 +473,12 @@ int rdetr_sine_pos_embed(const float *pos, long long rows, int n, int F, float t
  *                           x.flatten(2).transpose(1, 2) (+ the level embedding, relation_transformer.py:87-89) written
  *                           straight into the level's rows of the level-packed token tensor (base_transformer.py:17-23):
  *                           `out` points at the level's first row of image 0; rows are ld_out elements apart (>= C), images
- *                           out_image_stride elements.  add_vec nullable. */
+ *                           out_image_stride elements.  add_vec nullable.
+ *   rdetr_nchw_levels_to_tokens   all L <= 8 levels of a pyramid in ONE launch: out [B, S, C] = cat over the levels of the above,
+ *                           `out` pointing at row 0 of image 0.  level_src / level_vec: L HOST pointers to the levels' DEVICE
+ *                           tensors [B, C, P_l] and vectors [C] (level_vec or any of its entries may be NULL); level_pixels: L
+ *                           host ints P_l.  The tables travel in the kernel's argument block, so the call is one kernel node
+ *                           of a captured graph.  Same values as the per-level calls. */
 int rdetr_zero_masked_rows(void *x, const unsigned char *mask, long long rows, int row_bytes, long long ld_bytes,
                            void *stream);
 int rdetr_row_max(const void *x, int is_bf16, long long rows, int C, long long ldx, void *out, void *stream);
@@ -560,6 +565,8 @@ int rdetr_pyramid_points(const unsigned char *const *level_masks, const int *lev
                          int keep_is_bf16, float *valid_ratios, float *reference, float *logit, void *keep, void *stream);
 int rdetr_nchw_to_tokens(const void *src, const void *add_vec, int is_bf16, int B, int C, int P,
                          long long out_image_stride, long long ld_out, void *out, void *stream);
+int rdetr_nchw_levels_to_tokens(const void *const *level_src, const void *const *level_vec, const int *level_pixels, int L,
+                                int is_bf16, int B, int C, long long out_image_stride, long long ld_out, void *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Dense projection with K = 256 (embed_dim) for tall bf16 inputs, hand-written MFMA kernel (csrc/linear.hip):

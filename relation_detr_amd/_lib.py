@@ -77,6 +77,7 @@ SIGNATURES = {
     "rdetr_ffn_k256_train_bf16": [_vp, _c_ll, _vp, _vp, _vp, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp],
     "rdetr_ffn_k256_backward_bf16": [_vp, _c_ll, _vp, _vp, _c_ll, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp],
     "rdetr_nchw_to_tokens": [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp],
+    "rdetr_nchw_levels_to_tokens": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp],
     "rdetr_add_layernorm_f32": [_vp] * 4 + [_c_ll, _c_int, _c_float, _vp, _vp],
     "rdetr_add_layernorm_bf16": [_vp] * 4 + [_c_ll, _c_int, _c_float, _vp, _vp],
     "rdetr_add_layernorm_strided_f32": [_vp] * 4 + [_c_ll, _c_int, _c_ll, _c_ll, _c_ll, _c_float, _vp, _vp],

@@ -16,6 +16,7 @@
 //   nchw_to_tokens     x.flatten(2).transpose(1, 2) of one pyramid level (+ a per-channel vector: the level embedding of
 //                      models/bricks/relation_transformer.py:87-89) written into its row range of the level-packed
 //                      [B, S, C] token tensor (models/bricks/base_transformer.py:17-23): LDS-tiled transpose, 64 x 64
+//   nchw_levels_to_tokens   the same for up to 8 levels of a pyramid in one launch
 #include "common.h"
 
 namespace rdetr {
@@ -228,6 +229,91 @@ __global__ __launch_bounds__(256) void nchw_to_tokens_bf16_vec_kernel(const uint
             v = u32x4{o[0], o[1], o[2], o[3]};
         }
         *reinterpret_cast<u32x4 *>(out + (size_t)b * out_image_stride + (size_t)(p0 + px) * ld_out + c0 + 8 * cg) = v;
+    }
+}
+
+// ---- every level of a pyramid in ONE launch: a flattened list of 64-pixel tiles over the levels ---------------------------
+// The per-level launches above are a dependent chain of L short kernels at the entry of every step; here a workgroup finds its
+// level from the prefix counts in the by-value argument struct (no device-side table, so the call captures into a graph as one
+// kernel node).  A destination row starts on a 16-byte boundary whatever the level's pixel count, so bf16 stores are 16 bytes per
+// lane for every level; only the source side depends on the level: 16-byte loads where its pixel count is a multiple of 8,
+// 2-byte loads coalesced along pixels where it is not (25 x 42 and 13 x 21 of the R50 pyramid).  Same arithmetic per element.
+// One difference in bits from the per-level path: a bf16 level without a vector whose pixel count is not a multiple of 8 is
+// COPIED here, as torch's cat does, where nchw_to_tokens_kernel adds 0.f (-0.0 became +0.0, a signalling NaN quiet).
+struct TokLevels {
+    const void *src[8];               // [B, C, P_l]
+    const void *vec[8];               // [C] or null
+    int pixels[8], row0[8];           // P_l and the level's first row of the destination
+    int tile0[9];                     // prefix counts of the 64-pixel tiles
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void nchw_levels_to_tokens_kernel(TokLevels lv, int L, int C, long long out_image_stride,
+                                                                    long long ld_out, int wide, T *__restrict__ out)
+{
+    int l = 0;
+    while (l + 1 < L && (int)blockIdx.x >= lv.tile0[l + 1]) ++l;             // uniform over the workgroup
+    const int P = lv.pixels[l], p0 = ((int)blockIdx.x - lv.tile0[l]) * 64;
+    const int b = blockIdx.z, c0 = blockIdx.y * 64, tid = threadIdx.x;
+    const int tx = tid & 63, ty = tid >> 6;
+    const T *src = static_cast<const T *>(lv.src[l]) + ((size_t)b * C + c0) * (size_t)P + p0;
+    const T *add_vec = static_cast<const T *>(lv.vec[l]);
+    T *o = out + (size_t)b * out_image_stride + ((size_t)lv.row0[l] + p0) * ld_out + c0;
+    if constexpr (sizeof(T) == 4) {                                           // fp32: 4-byte accesses, as nchw_to_tokens_kernel
+        __shared__ float tile[64][65];
+#pragma unroll 4
+        for (int i = ty; i < 64; i += 4) tile[i][tx] = (c0 + i < C && p0 + tx < P) ? src[(size_t)i * P + tx] : 0.f;
+        __syncthreads();
+        const float av = (add_vec && c0 + tx < C) ? add_vec[c0 + tx] : 0.f;
+#pragma unroll 4
+        for (int i = ty; i < 64; i += 4)
+            if (p0 + i < P && c0 + tx < C) o[(size_t)i * ld_out + tx] = tile[tx][i] + av;
+    } else {
+        __shared__ __attribute__((aligned(16))) uint16_t tile[64][72];       // [pixel][channel], rows 144 B apart
+        if (P % 8 == 0 && reinterpret_cast<uintptr_t>(lv.src[l]) % 16 == 0) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int it = tid + 256 * k, ch = it >> 3, pg = it & 7;
+                u32x4 v = {0u, 0u, 0u, 0u};
+                if (c0 + ch < C && p0 + 8 * pg < P) v = *reinterpret_cast<const u32x4 *>(src + (size_t)ch * P + 8 * pg);
+                const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    tile[8 * pg + 2 * j][ch] = (uint16_t)(w[j] & 0xffffu);
+                    tile[8 * pg + 2 * j + 1][ch] = (uint16_t)(w[j] >> 16);
+                }
+            }
+        } else {
+#pragma unroll 4
+            for (int i = ty; i < 64; i += 4)                                   // channel c0 + i, pixel p0 + tx
+                tile[tx][i] = (c0 + i < C && p0 + tx < P) ? src[(size_t)i * P + tx] : (uint16_t)0;
+        }
+        __syncthreads();
+        if (wide) {                                                           // C, ld_out, image stride % 8 == 0, aligned out and vectors
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const int it = tid + 256 * k, px = it >> 3, cg = it & 7;
+                if (p0 + px >= P || c0 + 8 * cg >= C) continue;
+                u32x4 v = *reinterpret_cast<const u32x4 *>(&tile[px][8 * cg]);
+                if (add_vec) {
+                    const u32x4 a = *reinterpret_cast<const u32x4 *>(add_vec + c0 + 8 * cg);
+                    const unsigned vw[4] = {v.x, v.y, v.z, v.w}, aw[4] = {a.x, a.y, a.z, a.w};
+                    unsigned s[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        s[j] = pack_bf16x2(bf16_bits_to_f32(vw[j] & 0xffffu) + bf16_bits_to_f32(aw[j] & 0xffffu),
+                                           bf16_bits_to_f32(vw[j] >> 16) + bf16_bits_to_f32(aw[j] >> 16));
+                    v = u32x4{s[0], s[1], s[2], s[3]};
+                }
+                *reinterpret_cast<u32x4 *>(o + (size_t)px * ld_out + 8 * cg) = v;
+            }
+        } else {
+            const float av = (add_vec && c0 + tx < C) ? bf16_bits_to_f32(add_vec[c0 + tx]) : 0.f;
+#pragma unroll 4
+            for (int i = ty; i < 64; i += 4)
+                if (p0 + i < P && c0 + tx < C)
+                    o[(size_t)i * ld_out + tx] = (uint16_t)f32_to_bf16_bits(bf16_bits_to_f32(tile[i][tx]) + av);
+        }
     }
 }
 
@@ -473,5 +559,41 @@ extern "C" int rdetr_nchw_to_tokens(const void *src, const void *add_vec, int is
     else
         hipLaunchKernelGGL((nchw_to_tokens_kernel<float>), grid, dim3(256), 0, st, static_cast<const float *>(src),
                            static_cast<const float *>(add_vec), C, P, out_image_stride, ld_out, static_cast<float *>(out));
+    return launch_status();
+}
+
+extern "C" int rdetr_nchw_levels_to_tokens(const void *const *level_src, const void *const *level_vec, const int *level_pixels, int L,
+                                           int is_bf16, int B, int C, long long out_image_stride, long long ld_out, void *out,
+                                           void *stream)
+{
+    if (L <= 0 || B < 0 || C <= 0 || !level_src || !level_pixels || ld_out < C || out_image_stride < 0) return RDETR_ERR_INVALID_ARG;
+    if (L > 8 || B > 65535 || (C + 63) / 64 > 65535 || (is_bf16 != 0 && is_bf16 != 1)) return RDETR_ERR_UNSUPPORTED;
+    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    TokLevels lv = {};
+    long long rows = 0, tiles = 0;
+    bool wide = C % 8 == 0 && ld_out % 8 == 0 && out_image_stride % 8 == 0 && al16(out);
+    for (int l = 0; l < L; ++l) {
+        if (level_pixels[l] < 0 || (level_pixels[l] > 0 && !level_src[l])) return RDETR_ERR_INVALID_ARG;
+        lv.src[l] = level_src[l];
+        lv.vec[l] = level_vec ? level_vec[l] : nullptr;
+        lv.pixels[l] = level_pixels[l];
+        lv.row0[l] = (int)rows;
+        lv.tile0[l] = (int)tiles;
+        rows += level_pixels[l];
+        tiles += (level_pixels[l] + 63) / 64;
+        if (rows >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
+        wide = wide && al16(lv.vec[l]);
+    }
+    lv.tile0[L] = (int)tiles;
+    if (B == 0 || tiles == 0) return RDETR_OK;
+    if (!out) return RDETR_ERR_INVALID_ARG;
+    const dim3 grid((unsigned)tiles, (unsigned)((C + 63) / 64), (unsigned)B);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (is_bf16)
+        hipLaunchKernelGGL((nchw_levels_to_tokens_kernel<uint16_t>), grid, dim3(256), 0, st, lv, L, C, out_image_stride, ld_out,
+                           (int)wide, static_cast<uint16_t *>(out));
+    else
+        hipLaunchKernelGGL((nchw_levels_to_tokens_kernel<float>), grid, dim3(256), 0, st, lv, L, C, out_image_stride, ld_out, 0,
+                           static_cast<float *>(out));
     return launch_status();
 }

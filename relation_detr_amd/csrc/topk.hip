@@ -4,6 +4,8 @@
 // torch's multi-block radix select + sort takes 84 us for [4, 22,323] and 118 us for [4, 81,900]; the stack pays that on every
 // image group's chain.  Here: a multi-workgroup radix select on the top 12 key bits (histogram, scan, partition: three short
 // launches that use the whole chip; per-workgroup partial histograms, so the workspace needs no zeroing) and one workgroup per row that refines the boundary bin and sorts the k winners.
+// Rows of up to kTkOneLaunchMaxN elements take the same steps in ONE launch, one workgroup per row (topk_row_kernel): with two
+// rows per image group the four launches are a latency chain.
 //
 // Order: TOTAL and deterministic -- by value descending, equal values by index ascending, NaN above everything (torch.topk's
 // order among equal values is unspecified; its NaN rule is the same).  Every comparison is made on a 64-bit composite
@@ -17,6 +19,14 @@ constexpr int kTkBins = 4096;                  // level 1: top 12 bits of the 32
 constexpr int kTkItems = 16;                   // elements per thread in the streaming kernels
 constexpr int kTkBlock = 256;
 constexpr int kTkChunk = kTkBlock * kTkItems;  // 4096 elements per workgroup
+// Rows of up to this many elements are selected in one launch (topk_row_kernel), longer ones by the four launches A - D; so is an
+// x that is not aligned to its element size (no contiguous tensor yields one; the 16-byte loads need it).  The value follows from
+// tools/time_topk.py's table of both paths on one MI355X (profiles/r11/time_topk.txt, us per call, four launches -> one launch):
+//   [2, 22323] bf16 k=900  33.3 -> 27.9 (scores concentrated in two bins 44.7 -> 42.5)     [2, 27300] fp32 k=300  32.9 -> 26.7
+//   [2, 81900] fp32 k=300  37.2 -> 40.4     [1, 81900] fp32 k=300  36.2 -> 40.2     ([1, 204098] bf16: not tried in one launch)
+// so the crossover lies between 27,300 and 81,900 elements: the 22,323- and 27,300-element selections take the one launch, the
+// 81,900- and 204,098-element ones keep the four.  Below 2^19 so that the tests reach both paths.
+constexpr int kTkOneLaunchMaxN = 32768;
 
 struct TkCtrl {                                // per row, in the workspace
     unsigned bin, above, out_count, cand_count;
@@ -168,18 +178,14 @@ __device__ __forceinline__ unsigned tk_suffix_exclusive(unsigned v, unsigned *wa
     return incl - v + above_waves;
 }
 
-__global__ __launch_bounds__(1024) void topk_finish_kernel(const TkCtrl *__restrict__ ctrl, const unsigned long long *__restrict__ cand, int n,
-                                                          unsigned long long *__restrict__ winners, int k, float *__restrict__ values,
-                                                          long long *__restrict__ indices)
+// The body of D, shared with the one-launch kernel below: `hist` 1024 counters, `wave_tot` 16, `keys` 1024 composites, `sel` 3 words
+// of LDS; c: the row's `cnt` candidates, w: its winners (the first `above` are in place), both in global memory.
+__device__ __forceinline__ void tk_refine_sort(unsigned above, unsigned cnt, const unsigned long long *c, unsigned long long *w, int k, int r,
+                                               unsigned *hist, unsigned *wave_tot, unsigned long long *keys, unsigned *sel,
+                                               float *__restrict__ values, long long *__restrict__ indices)
 {
-    __shared__ unsigned hist[1024];
-    __shared__ unsigned wave_tot[16];
-    __shared__ unsigned long long keys[1024];
-    __shared__ unsigned sel_bin, sel_above, append;
-    const int r = blockIdx.x, t = threadIdx.x;
-    const unsigned above = ctrl[r].above, cnt = ctrl[r].cand_count;
-    const unsigned long long *c = cand + (size_t)r * n;
-    unsigned long long *w = winners + (size_t)r * k;
+    unsigned &sel_bin = sel[0], &sel_above = sel[1], &append = sel[2];
+    const int t = threadIdx.x;
     unsigned need = (unsigned)k - above;                               // 1 <= need <= cnt
     unsigned long long prefix = 0, pmask = 0;                          // bits of the threshold fixed so far (below bit 40)
     for (int shift = 30; shift >= 0; shift -= 10) {
@@ -235,6 +241,160 @@ __global__ __launch_bounds__(1024) void topk_finish_kernel(const TkCtrl *__restr
     }
 }
 
+__global__ __launch_bounds__(1024) void topk_finish_kernel(const TkCtrl *__restrict__ ctrl, const unsigned long long *__restrict__ cand, int n,
+                                                          unsigned long long *__restrict__ winners, int k, float *__restrict__ values,
+                                                          long long *__restrict__ indices)
+{
+    __shared__ unsigned hist[1024];
+    __shared__ unsigned wave_tot[16];
+    __shared__ unsigned long long keys[1024];
+    __shared__ unsigned sel[3];
+    const int r = blockIdx.x;
+    tk_refine_sort(ctrl[r].above, ctrl[r].cand_count, cand + (size_t)r * n, winners + (size_t)r * k, k, r, hist, wave_tot, keys, sel, values,
+                   indices);
+}
+
+// ---- A to D in ONE launch: one 1024-thread workgroup per row ------------------------------------------------------------------
+// With the two rows of an image group the four launches above are a latency chain (hist 8.6 + scan 7.7 + partition 8.5 + finish
+// 17.0 us), not a bandwidth problem: a row of the sizes the stack selects from is 45 - 410 KB.  One workgroup builds the level-1
+// histogram in LDS (16-byte loads, 4 in flight per lane), scans it, and passes over the row a second time (from L2) to append
+// winners and boundary-bin candidates to the workspace; positions come from a prefix over the wave and one LDS counter per class,
+// no global atomic and no zero-initialised workspace.  The workgroup then reads back its own global writes (fence + barrier) in
+// the refinement and the sort of D.  Same composites, hence the same values and indices as the four launches.
+constexpr int kTkUnroll = 4;                   // 16-byte loads in flight per lane
+
+template <bool BF16> __device__ __forceinline__ void tk_vec_keys(const u32x4 v, unsigned *key)
+{
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (BF16) {
+            key[2 * j] = tk_key(bf16_bits_to_f32(w[j] & 0xffffu));
+            key[2 * j + 1] = tk_key(bf16_bits_to_f32(w[j] >> 16));
+        } else {
+            key[j] = tk_key(__builtin_bit_cast(float, w[j]));
+        }
+    }
+}
+
+template <bool BF16>
+__global__ __launch_bounds__(1024) void topk_row_kernel(const void *__restrict__ x, int n, int k, unsigned long long *__restrict__ cand,
+                                                        unsigned long long *__restrict__ winners, float *__restrict__ values,
+                                                        long long *__restrict__ indices)
+{
+    constexpr int kPer = BF16 ? 8 : 4, kEs = BF16 ? 2 : 4;
+    __shared__ unsigned hist[kTkBins];
+    __shared__ unsigned wave_tot[16];
+    __shared__ unsigned long long keys[1024];
+    __shared__ unsigned sel[3], bnd[2], cls[2];                                // bnd: boundary bin, count above; cls: winners, candidates
+    const int r = blockIdx.x, t = threadIdx.x, lane = t & 63;
+    const unsigned char *row = static_cast<const unsigned char *>(x) + (size_t)r * n * kEs;
+    unsigned long long *c = cand + (size_t)r * n, *w = winners + (size_t)r * k;
+    // [0, head) scalar up to the first 16-byte boundary, nv vectors, [head + nv * kPer, n) scalar
+    const int head = min(n, (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(row) & 15u)) & 15u) / kEs));
+    const int nv = (n - head) / kPer, tail0 = head + nv * kPer;
+    const u32x4 *vrow = reinterpret_cast<const u32x4 *>(row + (size_t)head * kEs);
+    auto edge_index = [&](int e) { return e < head ? e : tail0 + (e - head); };      // the e-th scalar element, e < head + n - tail0
+    const int edges = head + n - tail0;                                              // < 2 * kPer
+    for (int i = t; i < kTkBins; i += 1024) hist[i] = 0;
+    if (t == 0) cls[0] = cls[1] = 0;
+    __syncthreads();
+    for (int v0 = t; v0 < nv; v0 += 1024 * kTkUnroll) {
+        u32x4 d[kTkUnroll] = {};
+#pragma unroll
+        for (int u = 0; u < kTkUnroll; ++u)
+            if (v0 + 1024 * u < nv) d[u] = vrow[v0 + 1024 * u];
+#pragma unroll
+        for (int u = 0; u < kTkUnroll; ++u)
+            if (v0 + 1024 * u < nv) {
+                unsigned key[kPer];
+                tk_vec_keys<BF16>(d[u], key);
+                unsigned bin = key[0] >> 20, run = 1;                         // one atomic per run of equal bins: scores near the
+#pragma unroll
+                for (int j = 1; j < kPer; ++j) {                              // class prior put most of a row into a few bins
+                    const unsigned bj = key[j] >> 20;
+                    if (bj != bin) {
+                        atomicAdd(&hist[bin], run);
+                        bin = bj;
+                        run = 0;
+                    }
+                    ++run;
+                }
+                atomicAdd(&hist[bin], run);
+            }
+    }
+    if (t < edges) atomicAdd(&hist[tk_key(tk_load(row, BF16, (size_t)edge_index(t))) >> 20], 1u);
+    __syncthreads();
+    {   // the bin that holds the k-th largest element and the number of elements above it: 4 bins per thread, as topk_scan_kernel
+        const unsigned cb[4] = {hist[4 * t], hist[4 * t + 1], hist[4 * t + 2], hist[4 * t + 3]};
+        unsigned run = tk_suffix_exclusive(cb[0] + cb[1] + cb[2] + cb[3], wave_tot, t);
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+            if (run < (unsigned)k && run + cb[j] >= (unsigned)k) {
+                bnd[0] = (unsigned)(4 * t + j);
+                bnd[1] = run;
+            }
+            run += cb[j];
+        }
+    }
+    __syncthreads();
+    const unsigned bstar = bnd[0], above = bnd[1];
+    for (int v0 = t; v0 - t < nv; v0 += 1024 * kTkUnroll) {                    // trip count uniform over the workgroup (shuffles below)
+        u32x4 d[kTkUnroll] = {};
+#pragma unroll
+        for (int u = 0; u < kTkUnroll; ++u)
+            if (v0 + 1024 * u < nv) d[u] = vrow[v0 + 1024 * u];
+        unsigned key[kTkUnroll * kPer];
+        unsigned nw = 0, nc = 0, fw = 0, fc = 0;                              // counts and per-item flags of this thread
+#pragma unroll
+        for (int u = 0; u < kTkUnroll; ++u)
+            if (v0 + 1024 * u < nv) {
+                tk_vec_keys<BF16>(d[u], key + u * kPer);
+#pragma unroll
+                for (int j = 0; j < kPer; ++j) {
+                    const unsigned bin = key[u * kPer + j] >> 20;
+                    if (bin > bstar) { fw |= 1u << (u * kPer + j); ++nw; }
+                    else if (bin == bstar) { fc |= 1u << (u * kPer + j); ++nc; }
+                }
+            }
+        if (__ballot((nw | nc) != 0) == 0ull) continue;                        // uniform over the wave
+        unsigned pw = nw, pc = nc;                                            // inclusive prefix over the wave's lanes
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned a = __shfl_up(pw, o, 64), bq = __shfl_up(pc, o, 64);
+            if (lane >= o) { pw += a; pc += bq; }
+        }
+        unsigned bw = 0, bc = 0;
+        if (lane == 63) {                                                      // one LDS atomic per wave and class
+            bw = pw ? atomicAdd(&cls[0], pw) : 0u;
+            bc = pc ? atomicAdd(&cls[1], pc) : 0u;
+        }
+        unsigned ow = __shfl(bw, 63, 64) + pw - nw, oc = __shfl(bc, 63, 64) + pc - nc;
+#pragma unroll
+        for (int u = 0; u < kTkUnroll; ++u)
+#pragma unroll
+            for (int j = 0; j < kPer; ++j) {
+                const int q = u * kPer + j;
+                if ((fw | fc) >> q & 1u) {
+                    const unsigned i = (unsigned)(head + (v0 + 1024 * u) * kPer + j);
+                    const unsigned long long comp = ((unsigned long long)key[q] << 20) | (unsigned long long)(0xfffffu - i);
+                    if (fw >> q & 1u) w[ow++] = comp;
+                    else c[oc++] = comp;
+                }
+            }
+    }
+    if (t < edges) {
+        const unsigned i = (unsigned)edge_index(t);
+        const unsigned key1 = tk_key(tk_load(row, BF16, (size_t)i));
+        const unsigned long long comp = ((unsigned long long)key1 << 20) | (unsigned long long)(0xfffffu - i);
+        if ((key1 >> 20) > bstar) w[atomicAdd(&cls[0], 1u)] = comp;
+        else if ((key1 >> 20) == bstar) c[atomicAdd(&cls[1], 1u)] = comp;
+    }
+    __threadfence_block();                                                     // the workgroup reads its own global writes back below
+    __syncthreads();
+    tk_refine_sort(above, cls[1], c, w, k, r, hist, wave_tot, keys, sel, values, indices);
+}
+
 }  // namespace rdetr
 
 using namespace rdetr;
@@ -263,6 +423,13 @@ extern "C" int rdetr_topk(const void *x, int is_bf16, int rows, int n, int k, vo
     TkCtrl *ctrl = reinterpret_cast<TkCtrl *>(ws + (size_t)rows * chunks * kTkBins * 4);
     unsigned long long *cand = reinterpret_cast<unsigned long long *>(ws + (size_t)rows * ((size_t)chunks * kTkBins * 4 + 16));
     unsigned long long *winners = cand + (size_t)rows * n;
+    if (n <= kTkOneLaunchMaxN && reinterpret_cast<uintptr_t>(x) % (is_bf16 ? 2 : 4) == 0) {
+        if (is_bf16)
+            hipLaunchKernelGGL((topk_row_kernel<true>), dim3((unsigned)rows), dim3(1024), 0, st, x, n, k, cand, winners, values, indices);
+        else
+            hipLaunchKernelGGL((topk_row_kernel<false>), dim3((unsigned)rows), dim3(1024), 0, st, x, n, k, cand, winners, values, indices);
+        return launch_status();
+    }
     const dim3 grid((unsigned)chunks, (unsigned)rows);
     hipLaunchKernelGGL(topk_hist_kernel, grid, dim3(kTkBlock), 0, st, x, is_bf16, n, hist);
     hipLaunchKernelGGL(topk_scan_kernel, dim3((unsigned)rows), dim3(1024), 0, st, hist, chunks, k, ctrl);

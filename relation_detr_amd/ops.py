@@ -1238,15 +1238,28 @@ def tokens_from_levels(levels, add_vecs=None, out: Optional[torch.Tensor] = None
     if tuple(out.shape) != (B, S, C) or out.dtype != x0.dtype or out.stride(-1) != 1 or (B > 1 and out.stride(0) < S * out.stride(1)):
         raise _lib.RdetrError("tokens_from_levels: out must be [B, S, C] in the levels' dtype with contiguous channels")
     lib, es, row = _lib.load(), out.element_size(), 0
+    xs, vecs = [], []
     for l, x in enumerate(levels):
         if x.shape[:2] != (B, C) or x.dtype != x0.dtype:
             raise _lib.RdetrError("tokens_from_levels: levels must agree in batch, channels and dtype")
-        x = x.contiguous()
+        xs.append(x.contiguous())
         vec = None
         if add_vecs is not None:
             vec = add_vecs[l].to(x0.dtype).contiguous()
             if vec.numel() != C:
                 raise _lib.RdetrError("tokens_from_levels: add_vecs[l] needs C entries")
+        vecs.append(vec)
+    L = len(xs)
+    if L <= 8:                                      # the whole pyramid in one launch (level tables by value, as pyramid_points)
+        import ctypes
+        src = (ctypes.c_void_p * L)(*[x.data_ptr() for x in xs])
+        vp = (ctypes.c_void_p * L)(*[None if v is None else v.data_ptr() for v in vecs])
+        pix = (ctypes.c_int * L)(*[x.shape[2] * x.shape[3] for x in xs])
+        st = lib.rdetr_nchw_levels_to_tokens(src, vp, pix, L, int(x0.dtype == torch.bfloat16), B, C, out.stride(0), out.stride(1),
+                                             out.data_ptr(), _stream_ptr(x0))
+        _lib.check(st, "rdetr_nchw_levels_to_tokens")
+        return out
+    for x, vec in zip(xs, vecs):
         P = x.shape[2] * x.shape[3]
         st = lib.rdetr_nchw_to_tokens(x.data_ptr(), vec.data_ptr() if vec is not None else None, int(x0.dtype == torch.bfloat16),
                                       B, C, P, out.stride(0), out.stride(1), out.data_ptr() + row * out.stride(1) * es,
