@@ -264,6 +264,35 @@ int rdetr_msda_backward_fused_bf16(const uint16_t *value, const int64_t *spatial
                                    void *workspace, long long workspace_bytes, float *grad_value, uint16_t *grad_offsets,
                                    uint16_t *grad_logits, float *grad_ref_partial, void *stream);
 
+/* The fused-producer bf16 backward on a HEAD-MAJOR value (training counterpart of the RDETR_VALUE_BHSD forward): arguments as
+ * rdetr_msda_backward_fused_bf16 except that
+ *   value_bhsd [B,H,S,D] bf16 and grad_value_bhsd [B,H,S,D] fp32 are head-major (what rdetr_value_to_head_major_bf16 writes);
+ *   sampling_offsets / attn_logits take row strides ld_offsets / ld_logits (elements; 0 = dense; ld_offsets even: the
+ *   convention of rdetr_msda_forward_fused_ex_bf16), and grad_offsets / grad_logits take row strides of their own, so each
+ *   pair can be the column slices [0, 2*H*L*P) and [2*H*L*P, 3*H*L*P) of ONE [B*Nq, 3*H*L*P] buffer: the output of the merged
+ *   query projection and its gradient.
+ * The layout is an addressing matter only: the same kernel body, the same products summed in the same order, so
+ * grad_offsets / grad_logits / grad_ref_partial have the bits of rdetr_msda_backward_fused_bf16 on the [B,S,H,D] copy of the
+ * value, and so has the deterministic grad_value after the permutation.  Both modes (workspace NULL: float atomics into a
+ * zero-filled grad_value; otherwise rdetr_msda_backward_det_workspace_bytes() bytes, every grad_value row overwritten).
+ * RDETR_ERR_INVALID_ARG: null / negative / short workspace / a stride below its row length / odd ld_offsets or
+ * ld_grad_offsets; RDETR_ERR_UNSUPPORTED: other than H = 8, D = 32, P = 4, L <= 8, or a missed alignment (value, grad_value,
+ * reference_points, workspace 16 bytes; offsets 4, logits 2).  B = 0 or Nq = 0: nothing is written. */
+int rdetr_msda_backward_fused_hm_bf16(const uint16_t *value_bhsd, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                      const uint16_t *sampling_offsets, int ld_offsets, const uint16_t *attn_logits, int ld_logits,
+                                      const float *reference_points, int ref_dim, const uint16_t *grad_out, int B, int S, int H,
+                                      int D, int L, int Nq, int P, void *workspace, long long workspace_bytes,
+                                      float *grad_value_bhsd, uint16_t *grad_offsets, int ld_grad_offsets, uint16_t *grad_logits,
+                                      int ld_grad_logits, float *grad_ref_partial, void *stream);
+
+/* Adjoint of rdetr_value_to_head_major_bf16: grad_hm [B, H, S, D] fp32 -> dst [B*S, H*D] bf16 (rows `ld` elements apart,
+ * ld % 8 == 0, 16-byte aligned: dst may be a column slice of a wider buffer), channel = head * D + c, rounded to bf16 once
+ * (round-to-nearest-even).  Rows of padded positions (`key_padding_mask` u8 [B, S], may be NULL) are written as zeros without
+ * reading their source: the backward of the zero-fill of models/bricks/ms_deform_attn.py:316-319 and the cast of the fp32
+ * gradient, in one pass.  H = 8, D = 32. */
+int rdetr_grad_value_from_head_major_bf16(const float *grad_hm, const uint8_t *key_padding_mask, int B, int S, int H, int D,
+                                          uint16_t *dst, long long ld, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Position-relation bias.
  * Replaces  PositionRelationEmbedding.forward  models/bricks/relation_transformer.py:520-532

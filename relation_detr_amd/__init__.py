@@ -12,6 +12,7 @@ from .ops import (MultiScaleDeformableAttnFunction, MultiScaleDeformableAttnFuse
                   relation_attention_backward, relation_attention_train, relation_bias)
 from .attn_rel_train import RelationAttentionBoxesFunction, relation_attention_boxes_backward, relation_attention_boxes_train
 from .ffn_train import FeedForwardFunction, ffn_k256_backward, ffn_k256_train
+from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -21,4 +22,5 @@ __all__ = [
     "RelationAttentionFunction", "relation_attention_train", "relation_attention_backward",
     "RelationAttentionBoxesFunction", "relation_attention_boxes_train", "relation_attention_boxes_backward",
     "FeedForwardFunction", "ffn_k256_train", "ffn_k256_backward",
+    "MultiScaleDeformableAttnHeadMajorFunction", "ms_deform_attn_backward_fused_hm", "grad_value_from_head_major",
 ]

@@ -146,6 +146,30 @@ __global__ __launch_bounds__(256) void zero_masked_rows_kernel(unsigned char *__
     }
 }
 
+// ---- head-major fp32 gradient -> [B*S, 256] bf16 rows (adjoint of the value's head-major re-layout) --------------------
+// grad_hm [B,8,S,32] fp32 -> dst row (b*S + s), channel head*32 + c, rounded to bf16 once; rows of padded positions are written as
+// zeros and their source is not read.  Pure data movement, no LDS: lane = one 16-byte chunk (8 channels) of a pixel row, so a wave
+// stores two whole 512-byte pixel rows per instruction, and the four lanes of a head read its whole 128-byte row (two 16-byte
+// loads each).  32 pixel rows per workgroup, four per lane.
+__global__ __launch_bounds__(256) void grad_value_from_head_major_kernel(const float *__restrict__ grad_hm, const unsigned char *__restrict__ mask,
+                                                                         long long rows, int S, long long ld, uint16_t *__restrict__ dst)
+{
+    const int j = threadIdx.x & 31, head = j >> 2, k = j & 3;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const long long r = (long long)blockIdx.x * 32 + i * 8 + (threadIdx.x >> 5);
+        if (r >= rows) break;
+        u32x4 o = u32x4{0u, 0u, 0u, 0u};
+        if (!(mask && mask[r])) {
+            const long long b = r / S, s = r - b * S;
+            const f32x4 *src = reinterpret_cast<const f32x4 *>(grad_hm + (((size_t)b * 8 + head) * (size_t)S + (size_t)s) * 32 + k * 8);
+            const f32x4 lo = src[0], hi = src[1];
+            o = u32x4{pack_bf16x2(lo.x, lo.y), pack_bf16x2(lo.z, lo.w), pack_bf16x2(hi.x, hi.y), pack_bf16x2(hi.z, hi.w)};
+        }
+        *reinterpret_cast<u32x4 *>(dst + (size_t)r * (size_t)ld + j * 8) = o;
+    }
+}
+
 // ---- row maximum (NaN propagates, as torch.max) ---------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void row_max_kernel(const T *__restrict__ x, long long rows, int C, long long ldx, T *__restrict__ out)
@@ -519,6 +543,19 @@ extern "C" int rdetr_zero_masked_rows(void *x, const unsigned char *mask, long l
     if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(zero_masked_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<unsigned char *>(x), mask, rows, row_bytes, ld_bytes);
+    return launch_status();
+}
+
+extern "C" int rdetr_grad_value_from_head_major_bf16(const float *grad_hm, const uint8_t *key_padding_mask, int B, int S, int H, int D,
+                                                     uint16_t *dst, long long ld, void *stream)
+{
+    if (B < 0 || S < 0 || H != 8 || D != 32 || ld < H * D || ld % 8) return RDETR_ERR_INVALID_ARG;
+    if (B == 0 || S == 0) return RDETR_OK;
+    if (!grad_hm || !dst || (reinterpret_cast<uintptr_t>(grad_hm) & 15) || (reinterpret_cast<uintptr_t>(dst) & 15)) return RDETR_ERR_INVALID_ARG;
+    const long long rows = (long long)B * S, nblk = (rows + 31) / 32;
+    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(grad_value_from_head_major_kernel, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), grad_hm,
+                       key_padding_mask, rows, S, ld, dst);
     return launch_status();
 }
 

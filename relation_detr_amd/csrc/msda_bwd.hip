@@ -198,15 +198,23 @@ __device__ __forceinline__ void st_val2(uint16_t *p, float x, float y) { *reinte
 //   * closing step, in the set-up layout (coalesced rows): softmax backward grad_logit_k = w_k (s_k - sum_j w_j s_j) with
 //     s_k = <grad_out, sample_k>, the location chain rule onto the offsets, and per-level sums onto the reference point.
 // Every sum except grad_value's is a fixed shuffle tree: grad_offsets / grad_logits / grad_ref are the same bits in both modes.
-template <typename T, bool DET>
+//
+// HM (rdetr_msda_backward_fused_hm_bf16): value and grad_value are HEAD-MAJOR [B,H,S,D] -- an addressing matter only.  The plane of
+// (image b, head m) starts at ((b*H + m) * S) * D, a pixel is one 128-byte grad row (64 bytes of bf16 value) instead of 1 KiB
+// (512), the descriptors cover exactly that plane (an out-of-level corner and anything past pixel S-1 is dropped, it cannot land
+// in the next head's plane), and a deterministic key is the row (b*H + m)*S + pixel of the head-major grad_value.  The raw
+// producer inputs and their gradients take row strides (elements), so that each pair can be two column slices of one
+// [B*Nq, 3*H*L*P] buffer.  Set-up, corner products, shuffle trees and closing step are this one body for every instantiation.
+template <typename T, bool DET, bool HM>
 __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
     const T *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ level_start,
     const T *__restrict__ offsets, const T *__restrict__ logits, const float *__restrict__ ref, int ref_dim,
     const T *__restrict__ grad_out, int S, int L, int Nq, int tiles_per_image, int nblk, float *__restrict__ grad_value,
     T *__restrict__ grad_offsets, T *__restrict__ grad_logits, float *__restrict__ grad_ref, unsigned *__restrict__ rec_key,
-    unsigned *__restrict__ rec_id, float *__restrict__ rec_w)
+    unsigned *__restrict__ rec_id, float *__restrict__ rec_w, int ld_off, int ld_lg, int ld_goff, int ld_glg)
 {
     constexpr bool kBf16 = sizeof(T) == 2;
+    constexpr unsigned kPix = HM ? kBHeadBytes : kBPixelBytes;         // bytes from one pixel's grad_value row to the next
     const int LP = L * kBP;
     __shared__ BwdLevels lvl;
     __shared__ u32x4 st_off[kBWaves][kBMaxL * kBP * 2];
@@ -232,8 +240,9 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
 
     // grad_value: fp32 [B,S,H,D], 1 KiB per pixel; value: T, sizeof(T) * 256 bytes per pixel -- the staged corner offsets are
     // grad_value byte offsets, shifted right by one for a bf16 value (the invalid offset 0x80000000 stays out of range)
-    const size_t plane = (size_t)b * S * (kBH * kBD) + (size_t)m * kBD;
-    const unsigned nrec = (unsigned)S * kBPixelBytes - (unsigned)m * kBHeadBytes;
+    // (head-major: 128 / 64 bytes per pixel, one plane per descriptor)
+    const size_t plane = HM ? ((size_t)b * kBH + m) * (size_t)S * kBD : (size_t)b * S * (kBH * kBD) + (size_t)m * kBD;
+    const unsigned nrec = HM ? (unsigned)S * kBHeadBytes : (unsigned)S * kBPixelBytes - (unsigned)m * kBHeadBytes;
     const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(value) + plane, 0,
                                                                           kBf16 ? nrec / 2 : nrec, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(grad_value + plane, 0, nrec, 0x00020000);
@@ -247,6 +256,11 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
 
     const size_t row = (size_t)b * Nq + (qok ? q : 0);
     const size_t hrow = (row * kBH + m) * (size_t)LP;
+    // this (query, head)'s LP logits / 2*LP offsets and their gradients: dense rows, or (HM) rows ld_* elements apart
+    const size_t i_lg = HM ? row * (size_t)ld_lg + (size_t)(m * LP) : hrow;
+    const size_t i_off = HM ? row * (size_t)ld_off + (size_t)(m * LP) * 2 : hrow * 2;
+    const size_t i_glg = HM ? row * (size_t)ld_glg + (size_t)(m * LP) : hrow;
+    const size_t i_goff = HM ? row * (size_t)ld_goff + (size_t)(m * LP) * 2 : hrow * 2;
     u32x4 *soff = st_off[wave];
     f32x4 *sfrac = st_frac[wave];
     f32x4 *smisc = st_misc[wave];
@@ -255,8 +269,8 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
     const bool pok = c < LP;
     const int l = pok ? c / kBP : 0;
     const int h = lvl.h[l], w = lvl.w[l];
-    const float lg = pok ? ld_f32(logits + hrow + c) : -__builtin_inff();
-    const f32x2 off = pok ? ld_f32x2(offsets + (hrow + c) * 2) : f32x2{0.f, 0.f};
+    const float lg = pok ? ld_f32(logits + i_lg + c) : -__builtin_inff();
+    const f32x2 off = pok ? ld_f32x2(offsets + i_off + c * 2) : f32x2{0.f, 0.f};
     float mx = lg;
 #pragma unroll
     for (int o = 1; o < 32; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
@@ -286,22 +300,23 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
         const float lx = inside ? x - xf : 0.f, ly = inside ? y - yf : 0.f;
         const bool okx0 = inside && x0 >= 0, okx1 = inside && x0 + 1 <= w - 1;
         const bool oky0 = y0 >= 0, oky1 = y0 + 1 <= h - 1;
-        const unsigned base = (unsigned)(lvl.start[l] + y0 * w + x0) * kBPixelBytes;
-        const unsigned rowb = (unsigned)w * kBPixelBytes;
+        const unsigned base = (unsigned)(lvl.start[l] + y0 * w + x0) * kPix;
+        const unsigned rowb = (unsigned)w * kPix;
         u32x4 o;
         o.x = (okx0 && oky0) ? base : kBInvalid;
-        o.y = (okx1 && oky0) ? base + kBPixelBytes : kBInvalid;
+        o.y = (okx1 && oky0) ? base + kPix : kBInvalid;
         o.z = (okx0 && oky1) ? base + rowb : kBInvalid;
-        o.w = (okx1 && oky1) ? base + rowb + kBPixelBytes : kBInvalid;
+        o.w = (okx1 && oky1) ? base + rowb + kPix : kBInvalid;
         const float a = inside ? wk : 0.f;
         soff[c * 2 + pair] = o;
         sfrac[c * 2 + pair] = f32x4{1.f - ly, 1.f - lx, ly, lx};
         smisc[c * 2 + pair] = f32x4{a, (float)w, (float)h, inside ? 1.f : 0.f};
         if constexpr (DET) {
             if (qok) {                                   // the records of msda_bwd_wave_kernel<true>
-                const unsigned rbase = (unsigned)((size_t)b * S) * kBH + (unsigned)m;
+                // key = row of grad_value: (image, pixel, head), or head-major (image, head, pixel)
+                const unsigned rbase = HM ? (unsigned)(((size_t)b * kBH + m) * (size_t)S) : (unsigned)((size_t)b * S) * kBH + (unsigned)m;
                 const float hy = 1.f - ly, hx = 1.f - lx;
-                auto key = [&](unsigned ob) { return ob == kBInvalid ? 0xffffffffu : rbase + (ob / kBPixelBytes) * kBH; };
+                auto key = [&](unsigned ob) { return ob == kBInvalid ? 0xffffffffu : rbase + (ob / kPix) * (HM ? 1u : (unsigned)kBH); };
                 const size_t rec = (hrow + c) * 4;
                 *reinterpret_cast<u32x4 *>(rec_key + rec) = u32x4{key(o.x), key(o.y), key(o.z), key(o.w)};
                 *reinterpret_cast<u32x4 *>(rec_id + rec) = u32x4{(unsigned)rec, (unsigned)rec + 1u, (unsigned)rec + 2u, (unsigned)rec + 3u};
@@ -366,8 +381,8 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
         rw += __shfl_xor(rw, o, 64);
     }
     if (qok && pok) {
-        st_val(grad_logits + hrow + c, g_logit);
-        st_val2(grad_offsets + (hrow + c) * 2, gox, goy);
+        st_val(grad_logits + i_glg + c, g_logit);
+        st_val2(grad_offsets + i_goff + c * 2, gox, goy);
         if (grad_ref && (c & (kBP - 1)) == 0) {
             float *gr = grad_ref + ((row * kBH + m) * L + l) * (size_t)ref_dim;
             if (ref_dim == 2)
@@ -574,14 +589,25 @@ extern "C" int rdetr_msda_backward_det_f32(const float *value, const int64_t *sp
 }
 
 // ---- fused-producer backward ---------------------------------------------------------------------------------------------------
-template <typename T>
+// HM: head-major value / grad_value and row strides (elements, 0 = dense) for the producer inputs and their gradients
+template <typename T, bool HM = false>
 static int msda_backward_fused(const T *value, const int64_t *shapes, const int64_t *level_start, const T *offsets, const T *logits,
                                const float *ref, int ref_dim, const T *grad_out, int B, int S, int H, int D, int L, int Nq, int P,
                                void *workspace, long long workspace_bytes, float *grad_value, T *grad_offsets, T *grad_logits,
-                               float *grad_ref_partial, hipStream_t st)
+                               float *grad_ref_partial, hipStream_t st, int ld_off = 0, int ld_lg = 0, int ld_goff = 0, int ld_glg = 0)
 {
     if (B < 0 || S < 0 || Nq < 0 || H <= 0 || D <= 0 || L <= 0 || P <= 0 || workspace_bytes < 0) return RDETR_ERR_INVALID_ARG;
     if (ref_dim != 2 && ref_dim != 4) return RDETR_ERR_INVALID_ARG;
+    if constexpr (HM) {
+        const long long n_lg = (long long)H * L * P;
+        auto bad = [](int ld, long long n) { return ld < 0 || (ld && ld < n); };
+        if (bad(ld_off, 2 * n_lg) || bad(ld_lg, n_lg) || bad(ld_goff, 2 * n_lg) || bad(ld_glg, n_lg) || ld_off % 2 || ld_goff % 2)
+            return RDETR_ERR_INVALID_ARG;
+        if (!ld_off) ld_off = (int)(2 * n_lg);
+        if (!ld_lg) ld_lg = (int)n_lg;
+        if (!ld_goff) ld_goff = (int)(2 * n_lg);
+        if (!ld_glg) ld_glg = (int)n_lg;
+    }
     if (B == 0 || Nq == 0) return RDETR_OK;
     if (!value || !shapes || !level_start || !offsets || !logits || !ref || !grad_out || !grad_value || !grad_offsets || !grad_logits ||
         S == 0)
@@ -591,15 +617,15 @@ static int msda_backward_fused(const T *value, const int64_t *shapes, const int6
     if (!(al(value, 16) && al(grad_value, 16) && al(grad_out, sizeof(T)) && al(offsets, 2 * sizeof(T)) && al(logits, sizeof(T)) &&
           al(grad_offsets, 2 * sizeof(T)) && al(grad_logits, sizeof(T)) && al(ref, 16) && al(grad_ref_partial, 16) &&
           (!workspace || al(workspace, 16))))
-        return RDETR_ERR_INVALID_ARG;
-    if ((long long)S * kBPixelBytes >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
+        return HM ? RDETR_ERR_UNSUPPORTED : RDETR_ERR_INVALID_ARG;
+    if ((long long)S * (HM ? kBHeadBytes : kBPixelBytes) >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
     const int tiles = (Nq + 2 * kBWaves - 1) / (2 * kBWaves);
     const long long nblk = (long long)B * kBH * tiles;
     if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
     if (!workspace) {
-        hipLaunchKernelGGL((msda_bwd_fused_kernel<T, false>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes,
+        hipLaunchKernelGGL((msda_bwd_fused_kernel<T, false, HM>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes,
                            level_start, offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, (int)nblk, grad_value, grad_offsets,
-                           grad_logits, grad_ref_partial, nullptr, nullptr, nullptr);
+                           grad_logits, grad_ref_partial, nullptr, nullptr, nullptr, ld_off, ld_lg, ld_goff, ld_glg);
         return launch_status();
     }
     // deterministic mode: the workspace of rdetr_msda_backward_det_f32 (same record count).  Records + sorted copies are 20 bytes
@@ -614,9 +640,9 @@ static int msda_backward_fused(const T *value, const int64_t *shapes, const int6
     unsigned *rec_key = reinterpret_cast<unsigned *>(ws + d.off_key), *rec_id = reinterpret_cast<unsigned *>(ws + d.off_id);
     float *rec_w = reinterpret_cast<float *>(ws + d.off_w);
     unsigned *skey = reinterpret_cast<unsigned *>(ws + d.off_skey), *sid = reinterpret_cast<unsigned *>(ws + d.off_sid);
-    hipLaunchKernelGGL((msda_bwd_fused_kernel<T, true>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes, level_start,
+    hipLaunchKernelGGL((msda_bwd_fused_kernel<T, true, HM>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes, level_start,
                        offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, (int)nblk, grad_value, grad_offsets, grad_logits,
-                       grad_ref_partial, rec_key, rec_id, rec_w);
+                       grad_ref_partial, rec_key, rec_id, rec_w, ld_off, ld_lg, ld_goff, ld_glg);
     if (launch_status() != RDETR_OK) return RDETR_ERR_LAUNCH;
     size_t tmp = d.tmp_bytes;
     if (hipcub::DeviceRadixSort::SortPairs(ws + d.off_tmp, tmp, rec_key, skey, rec_id, sid, (int)d.nrec, 0, d.key_bits, st) != hipSuccess)
@@ -646,4 +672,18 @@ extern "C" int rdetr_msda_backward_fused_bf16(const uint16_t *value, const int64
     return msda_backward_fused<uint16_t>(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
                                          ref_dim, grad_out, B, S, H, D, L, Nq, P, workspace, workspace_bytes, grad_value, grad_offsets,
                                          grad_logits, grad_ref_partial, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rdetr_msda_backward_fused_hm_bf16(const uint16_t *value_bhsd, const int64_t *spatial_shapes, const int64_t *level_start_index,
+                                                 const uint16_t *sampling_offsets, int ld_offsets, const uint16_t *attn_logits,
+                                                 int ld_logits, const float *reference_points, int ref_dim, const uint16_t *grad_out,
+                                                 int B, int S, int H, int D, int L, int Nq, int P, void *workspace,
+                                                 long long workspace_bytes, float *grad_value_bhsd, uint16_t *grad_offsets,
+                                                 int ld_grad_offsets, uint16_t *grad_logits, int ld_grad_logits, float *grad_ref_partial,
+                                                 void *stream)
+{
+    return msda_backward_fused<uint16_t, true>(value_bhsd, spatial_shapes, level_start_index, sampling_offsets, attn_logits,
+                                               reference_points, ref_dim, grad_out, B, S, H, D, L, Nq, P, workspace, workspace_bytes,
+                                               grad_value_bhsd, grad_offsets, grad_logits, grad_ref_partial,
+                                               static_cast<hipStream_t>(stream), ld_offsets, ld_logits, ld_grad_offsets, ld_grad_logits);
 }

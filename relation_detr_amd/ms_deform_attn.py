@@ -16,7 +16,7 @@ import warnings
 import torch
 from torch import Tensor, nn
 
-from . import ops
+from . import msda_train_hm, ops
 from . import options as _options
 
 
@@ -151,6 +151,19 @@ class MultiScaleDeformableAttention(nn.Module):
         if reference_points.shape[-1] not in (2, 4):
             raise ValueError(
                 "Last dim of reference_points must be 2 or 4, but get {} instead.".format(reference_points.shape[-1]))
+        if self._trains_head_major(query, reference_points, value):
+            # training on the eval path's data (msda_train_hm.py): value_proj WITHOUT the fill pass (its weight gradient stays with
+            # autograd), the two query projections as ONE differentiable GEMM whose column slices the kernels read -- and whose
+            # gradient they write -- in place, then the head-major core; padded rows are zeroed by the re-layout both ways
+            H_, L_, P_ = self.num_heads, self.num_levels, self.num_points
+            so, aw = self.sampling_offsets, self.attention_weights
+            v = self.value_proj(value)
+            both = torch.nn.functional.linear(query, torch.cat([so.weight, aw.weight], 0), torch.cat([so.bias, aw.bias], 0))
+            offsets, logits = msda_train_hm.split_merged_projection(both, H_ * L_ * P_ * 2)
+            core = msda_train_hm.MultiScaleDeformableAttnHeadMajorFunction.apply(
+                v, key_padding_mask, spatial_shapes, level_start_index, offsets.view(*query.shape[:2], H_, L_, P_, 2),
+                logits.view(*query.shape[:2], H_, L_ * P_), reference_points.float().contiguous())
+            return self._output(core, v.dtype, post_norm)
         fused = (value.is_cuda and not torch.is_grad_enabled()
                  and ops.msda_fast_path(self.num_heads, self.embed_dim // self.num_heads, self.num_levels, self.num_points))
         # the padding mask inside the kernel costs 4 byte loads per sample: cheaper than a fill pass over the projected
@@ -225,6 +238,23 @@ class MultiScaleDeformableAttention(nn.Module):
             core = ops.MultiScaleDeformableAttnFunction.apply(
                 v.to(core_dtype).contiguous(), spatial_shapes, level_start_index, loc.float().contiguous(),
                 weights.float().contiguous(), self.im2col_step)
+        return self._output(core, vdt, post_norm)
+
+    def _trains_head_major(self, query: Tensor, reference_points: Tensor, value: Tensor) -> bool:
+        """The `msda_train_head_major` route: a call that needs gradients, on the shape the eval path serves head-major (bf16,
+        fast-path sizes, queries = the pyramid's own pixels, S >= 4096, `value_head_major`), 2-d reference points."""
+        if not (self.options.msda_train_head_major and self.options.value_head_major and torch.is_grad_enabled() and value.is_cuda):
+            return False
+        so, aw, vp = self.sampling_offsets, self.attention_weights, self.value_proj
+        if not (value.dtype == torch.bfloat16 and query.dtype == torch.bfloat16 and reference_points.shape[-1] == 2
+                and query.shape[1] == value.shape[1] and value.shape[1] >= 4096 and value.dim() == 3 and query.shape[0] == value.shape[0]
+                and all(m.weight.dtype == torch.bfloat16 for m in (so, aw, vp)) and so.bias is not None and aw.bias is not None
+                and ops.msda_fast_path(self.num_heads, self.embed_dim // self.num_heads, self.num_levels, self.num_points)):
+            return False
+        return any(t.requires_grad for t in (query, value, reference_points, *so.parameters(), *aw.parameters(), *vp.parameters()))
+
+    def _output(self, core: Tensor, vdt, post_norm) -> Tensor:
+        """Everything after the core: the output projection and, with ``post_norm``, the caller's residual + LayerNorm."""
         if core.dtype != vdt:
             core = core.to(vdt)
         if post_norm is None:

@@ -49,6 +49,13 @@ class Options:
     msda_train_fused: bool = False   # training: softmax + locations inside the gather and its backward (MultiScaleDeformableAttnFusedFunction)
                                      # instead of the torch producer + MultiScaleDeformableAttnFunction (opt-in; core fwd + bwd 0.57-0.97x
                                      # the old route's time at every measured shape, profiles/r05/msda_train_fused_ab.txt)
+    msda_train_head_major: bool = False  # training, bf16 encoder shape (Nq == S >= 4096, 2-d reference points): the eval path's head-major
+                                         # forward (value_to_head_major with the padding fill folded in, resident kernel where it pays), the
+                                         # backward on the head-major value (MultiScaleDeformableAttnHeadMajorFunction, msda_train_hm.py) with
+                                         # grad_value handed to value_proj as bf16 in one pass, and the merged query projection (opt-in; no
+                                         # effect without grad; R50 encoder shape: module forward + backward 0.93-0.95x the time of
+                                         # msda_train_fused at B = 1, 2 and 4, atomic and deterministic; the core alone 0.98-1.00x -- the
+                                         # float atomics bound it in either layout; profiles/r11/msda_train_hm_ab.txt)
     # --- self_attn.py ---------------------------------------------------------------------------------------------------
     attn_train_fused: bool = False   # training, bf16, head dim 32: the decoder self-attention core as the flash-style forward + its
                                      # backward (RelationAttentionFunction, csrc/attn.hip + csrc/attn_bwd.hip) instead of the GEMM +

@@ -11,6 +11,20 @@ Shapes: the R50 encoder shape (bench.R50_SHAPES, S = Nq = 22,323, 2-d reference 
 warm-up, median over the reps.  Every gradient the step produces (value, offsets, logits, reference points) is requested.
 
     python tools/time_msda_train.py [--reps 15] [--warmup 3] [--label TEXT] [--quick] [--route old|new]
+
+``--hm``: the head-major training route instead (msda_train_head_major, relation_detr_amd/msda_train_hm.py) against the parent's best
+(msda_train_fused), bf16, the R50 encoder shape at B = 1, 2 and 4 with a padding mask on the tail of the last image, atomic and
+deterministic grad_value:
+
+  core    masked_fill + MultiScaleDeformableAttnFusedFunction on the [B,S,8,32] value (what the module runs; "nofill": the Function
+          alone) against MultiScaleDeformableAttnHeadMajorFunction on the projected value + mask; gradients for value, offsets,
+          logits and reference points
+  module  MultiScaleDeformableAttention.forward + backward (query = value shape; every input and parameter gradient), the same
+          weights in both modules
+
+The routes of a rep run in alternating order (forward order on even reps, reversed on odd ones).
+
+    python tools/time_msda_train.py --hm [--reps 15] [--warmup 3] [--batches 1 2 4] [--label TEXT]
 """
 import argparse
 import os
@@ -99,6 +113,83 @@ def time_config(name, B, Nq, ref_dim, dtype, det, reps, warmup, dev, only=None):
     torch.cuda.empty_cache()
 
 
+def _timed_routes(routes, reset, reps, warmup):
+    """{name: callable} -> {name: [ms per rep]}; every rep runs all routes, in forward order on even reps and reversed on odd ones."""
+    times = {k: [] for k in routes}
+    names = list(routes)
+    for i in range(warmup + reps):
+        for key in (names if i % 2 == 0 else names[::-1]):
+            reset()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            routes[key]()
+            e1.record()
+            torch.cuda.synchronize()
+            if i >= warmup:
+                times[key].append(e0.elapsed_time(e1))
+    return times
+
+
+def _fmt(times, key):
+    v = times[key]
+    return f"{key} {statistics.median(v):8.3f} ms [{min(v):.3f}-{max(v):.3f}]"
+
+
+def time_head_major(B, det, reps, warmup, dev):
+    from relation_detr_amd import MultiScaleDeformableAttention, msda_train_hm, options
+    leaves, shp, start, go = inputs(B, None, 2, torch.bfloat16, dev)
+    ops.host_levels(shp, start)
+    S = leaves[0].shape[1]
+    v = leaves[0].detach().view(B, S, 256).clone().requires_grad_(True)        # the projected value, before the padding fill
+    off, lg, ref = leaves[1:]
+    mask = torch.zeros(B, S, dtype=torch.bool, device=dev)
+    mask[B - 1, -S // 10:] = True
+    tensors = [v, off, lg, ref]
+
+    def reset():
+        for t in tensors:
+            t.grad = None
+
+    def fused(fill=True):
+        vv = v.masked_fill(mask[..., None], 0.0) if fill else v
+        ops.MultiScaleDeformableAttnFusedFunction.apply(vv.view(B, S, 8, 32), shp, start, off, lg, ref).backward(go)
+
+    def head_major():
+        msda_train_hm.MultiScaleDeformableAttnHeadMajorFunction.apply(v, mask, shp, start, off, lg, ref).backward(go)
+
+    tag = f"B={B} {'det   ' if det else 'atomic'}"
+    torch.use_deterministic_algorithms(det, warn_only=True)
+    try:
+        t = _timed_routes({"fused": fused, "nofill": lambda: fused(False), "hm": head_major}, reset, reps, warmup)
+        ratio = statistics.median(t["hm"]) / statistics.median(t["fused"])
+        print(f"core   {tag}  {_fmt(t, 'fused')}  {_fmt(t, 'nofill')}  {_fmt(t, 'hm')}  hm/fused {ratio:.3f}", flush=True)
+        # the module: same weights, the two switches
+        mods = {}
+        torch.manual_seed(0)
+        for key, on in (("fused", False), ("hm", True)):
+            with options.override(msda_train_fused=True, msda_train_head_major=on):
+                m = MultiScaleDeformableAttention(256, 4, 8, 4)
+            if mods:
+                m.load_state_dict(mods["fused"].state_dict())
+            else:
+                with torch.no_grad():
+                    for p in m.parameters():
+                        p.add_(torch.randn_like(p) * 0.02)
+            mods[key] = m.to(dev).to(torch.bfloat16).train()
+        g = torch.Generator().manual_seed(1)
+        q, x = (torch.randn(B, S, 256, generator=g).to(torch.bfloat16).to(dev).requires_grad_(True) for _ in range(2))
+        r = ref.detach().clone().requires_grad_(True)
+        tensors = [q, x, r] + [p for m in mods.values() for p in m.parameters()]
+        run = lambda m: m(q, r, x, shp, start, mask).backward(go)
+        t = _timed_routes({k: (lambda m=m: run(m)) for k, m in mods.items()}, reset, reps, warmup)
+        ratio = statistics.median(t["hm"]) / statistics.median(t["fused"])
+        print(f"module {tag}  {_fmt(t, 'fused')}  {_fmt(t, 'hm')}  hm/fused {ratio:.3f}", flush=True)
+    finally:
+        torch.use_deterministic_algorithms(False)
+    del leaves, tensors, mods
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=15)
@@ -106,10 +197,21 @@ def main():
     ap.add_argument("--label", default="")
     ap.add_argument("--quick", action="store_true", help="encoder B=1 and decoder only, for a profiler run")
     ap.add_argument("--route", choices=("old", "new"), help="run one route only (a profiler run)")
+    ap.add_argument("--hm", action="store_true", help="time the head-major training route against msda_train_fused")
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4], help="batch sizes of --hm")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("time_msda_train.py needs a GPU")
     dev = torch.device("cuda", 0)
+    if a.hm:
+        print(f"MSDA training, bf16, R50 encoder shape (S = Nq = 22,323, 2-d reference points): msda_train_fused (fused) vs "
+              f"msda_train_head_major (hm).  {a.label}")
+        print(f"device {torch.cuda.get_device_name(0)}, torch {torch.__version__}, median of {a.reps} reps after {a.warmup} warm-up "
+              f"[min-max], hipEvents around forward + backward of each route, route order alternating per rep")
+        for det in (False, True):
+            for B in a.batches:
+                time_head_major(B, det, a.reps, a.warmup, dev)
+        return
     print(f"MSDA core forward + backward, training mode: old route (torch producer + MultiScaleDeformableAttnFunction) vs new "
           f"(MultiScaleDeformableAttnFusedFunction).  {a.label}")
     print(f"device {torch.cuda.get_device_name(0)}, torch {torch.__version__}, median of {a.reps} reps after {a.warmup} warm-up "
