@@ -65,8 +65,6 @@ __device__ __forceinline__ void mask_keys(f32x4 &t, int kk, int M, const unsigne
     if (kk + 3 >= M) t.w = -__builtin_inff();
 }
 
-inline bool aligned_to(const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
 // The refusals both backward entry points share, in their order: row strides shorter than the H * D columns and a short
 // workspace are invalid arguments; operands the kernels' 16- / 8-byte accesses cannot take are unsupported.  RDETR_OK otherwise.
 inline int attention_bwd_layout_status(const void *q, const void *k, const void *v, const void *out, const void *dout, const void *lse,

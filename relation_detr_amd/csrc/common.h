@@ -50,6 +50,8 @@ __device__ __forceinline__ unsigned int relu_bf16x2(unsigned int packed)
     return __builtin_bit_cast(unsigned int, __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, packed), s16x2_t{0, 0}));
 }
 
+inline bool aligned_to(const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
+
 inline int launch_status()
 {
     return hipGetLastError() == hipSuccess ? RDETR_OK : RDETR_ERR_LAUNCH;

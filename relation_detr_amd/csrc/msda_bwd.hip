@@ -6,19 +6,27 @@
 // (b,q,head), 4 atomicAdd per thread per point, thread 0 serially sums 32 partials for the
 // location / weight gradients).
 //
-// One wavefront owns one head and two consecutive queries, one channel per lane: the 4 corner rows are re-gathered
-// (needed for d/dloc and d/dweight), `w_corner * g * attn` is scattered into grad_value with hardware fp32 atomics
-// whose wave instruction covers two full 128-byte head rows (out-of-level corners carry offset 0x80000000 and are
-// dropped by the buffer range check), and the per-head sums over D = 32 channels for grad_loc / grad_attn are
-// 32-lane xor-shuffle reductions instead of a shared-memory pass.
+// ONE BODY, TWO PRODUCERS.  One wavefront owns one head and two consecutive queries, one channel per lane.  The body is defined
+// once and used by every instantiation:
+//   * bwd_prologue    -- level table into LDS, logical block -> (image, head, wave, query of the pair, channel);
+//   * bwd_stage_point -- lane (pair, c) turns point c of its query (pixel coordinates, weight) into what the loop reads from LDS:
+//                        four corner byte offsets (0x80000000 = no row, dropped by the buffer range check), {hy, hx, ly, lx} and
+//                        {weight, W_l, H_l, inside}; "inside a level" and the NaN rule live here, and so do the records of the
+//                        deterministic mode;
+//   * bwd_point_loop  -- per point the 4 corner rows are re-gathered (needed for d/dloc and d/dweight), `w_corner * g * weight` is
+//                        scattered into grad_value with hardware fp32 atomics whose wave instruction covers two full 128-byte
+//                        head rows, and the sums over D = 32 channels are 32-lane xor-shuffle reductions instead of a
+//                        shared-memory pass; lane c leaves with point c's (d/dweight, d/dx, d/dy).
+// A producer is what surrounds them: how a lane obtains (x, y, weight) and what it does with the three sums.
+// msda_bwd_wave_kernel (materialised) loads location and weight and stores the sums; msda_bwd_fused_kernel recomputes both from
+// raw offsets / logits / reference points as the forward did, then runs the softmax backward and the chain rule onto them.
+// BwdPlane<T, HM> is the addressing of one (image, head) plane: fp32 or bf16 value, [B,S,H,D] or head-major.
 //
-// Float atomics make grad_value's summation order run-dependent (as in the reference).
-//
-// DETERMINISTIC mode (rdetr_msda_backward_det_f32; SURVEY section 8 f4 "deterministic alternative to atomics"): the same kernel
-// writes one (pixel-row key, weight) record per sample corner instead of adding; the records are sorted by key with a stable
-// radix sort (hipCUB / rocPRIM, caller-provided temporary storage) and `msda_bwd_segment_sum_kernel` adds each value row's
-// records in sorted = original sample order -- a fixed order, the same bits from run to run.  grad_loc / grad_attn are
-// shuffle-tree sums inside a wave in both modes.
+// Float atomics make grad_value's summation order run-dependent (as in the reference).  DETERMINISTIC mode (DET; SURVEY section 8
+// f4 "deterministic alternative to atomics"): bwd_stage_point writes one (grad_value-row key, weight) record per sample corner and
+// the loop does not add; the records are sorted by key with a stable radix sort (hipCUB / rocPRIM, caller-provided temporary
+// storage) and `msda_bwd_segment_sum_kernel` adds each row's records in sorted = original sample order -- the same bits from run
+// to run.  Every other gradient is a shuffle-tree sum inside a wave: the same bits in both modes.
 #include <hipcub/hipcub.hpp>
 
 #include "common.h"
@@ -44,10 +52,176 @@ __device__ __forceinline__ float sum32(float v)
     return v;
 }
 
-// One wavefront = ONE head x TWO consecutive queries; lane = pair*32 + channel, one channel per lane.
-// Every atomic wave instruction therefore adds two full 128-byte head rows (the access shape that runs at the
-// chip-wide float-atomic rate, MI355X_MICROARCH.md "Global float atomics"; the first version, 4 channels per lane
+// The block's LDS: the level table and, per wave, [point][pair]: corner offsets | {hy, hx, ly, lx} | {weight (0 if outside), W_l,
+// H_l, inside}
+struct BwdShared {
+    BwdLevels lvl;
+    u32x4 st_off[kBWaves][kBMaxL * kBP * 2];
+    f32x4 st_frac[kBWaves][kBMaxL * kBP * 2];
+    f32x4 st_misc[kBWaves][kBMaxL * kBP * 2];
+};
+
+// Where a lane works.  One wavefront = ONE head x TWO consecutive queries; lane = pair*32 + c, one channel per lane (and, in the
+// set-up, one point per lane).  Every atomic wave instruction therefore adds two full 128-byte head rows (the access shape that
+// runs at the chip-wide float-atomic rate, MI355X_MICROARCH.md "Global float atomics"; the first version, 4 channels per lane
 // x 8 heads, added 8 x 32 sparse bytes per instruction and reached 0.36 TB/s).
+struct BwdLane {
+    int b, m, wave, pair, c, q;     // image, head, wave of the block, query of the wave's two, channel, query index
+    bool qok;                       // q < Nq
+};
+
+// level table -> LDS; logical block -> (image b, head m, tile of 2*kBWaves consecutive queries)
+__device__ __forceinline__ BwdLane bwd_prologue(BwdShared &sh, const int64_t *__restrict__ shapes, const int64_t *__restrict__ level_start,
+                                                int L, int Nq, int tiles_per_image, int nblk)
+{
+    const int tid = threadIdx.x;
+    if (tid < L) {
+        sh.lvl.h[tid] = (int)shapes[2 * tid];
+        sh.lvl.w[tid] = (int)shapes[2 * tid + 1];
+        sh.lvl.start[tid] = (int)level_start[tid];
+    }
+    __syncthreads();
+
+    const int logical = xcd_contiguous_block(blockIdx.x, nblk);
+    const int bm = logical / tiles_per_image;
+    const int tile = logical - bm * tiles_per_image;
+    const int b = bm / kBH, m = bm - b * kBH;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63, pair = lane >> 5, c = lane & 31;
+    const int q = (tile * kBWaves + wave) * 2 + pair;
+    return BwdLane{b, m, wave, pair, c, q, q < Nq};
+}
+
+// The plane of (image b, head m) in value (T: fp32, or bf16 loaded two bytes per lane and converted) and in the fp32 grad_value.
+// [B,S,H,D]: a pixel is 1 KiB of grad_value (sizeof(T) * 256 bytes of value) and the descriptors run from the head's first row to
+// the end of the image.  HM, head-major [B,H,S,D] -- an addressing matter only: the plane starts at ((b*H + m) * S) * D, a pixel is
+// one 128-byte grad row (64 bytes of bf16 value) and the descriptors cover exactly that plane (an out-of-level corner and anything
+// past pixel S-1 is dropped, it cannot land in the next head's plane).  Offsets are grad_value byte offsets at pixel pitch kPix,
+// shifted right by one for a bf16 value (the invalid offset 0x80000000 stays out of range).
+template <typename T, bool HM>
+struct BwdPlane {
+    static constexpr bool kBf16 = sizeof(T) == 2;
+    static constexpr unsigned kPix = HM ? kBHeadBytes : kBPixelBytes;     // bytes from one pixel's grad_value row to the next
+    __amdgpu_buffer_rsrc_t rs_v, rs_g;
+    unsigned lane_off, lane_off_v;
+
+    __device__ __forceinline__ BwdPlane(const T *value, float *grad_value, const BwdLane &ln, int S)
+    {
+        const size_t plane = HM ? ((size_t)ln.b * kBH + ln.m) * (size_t)S * kBD : (size_t)ln.b * S * (kBH * kBD) + (size_t)ln.m * kBD;
+        const unsigned nrec = HM ? (unsigned)S * kBHeadBytes : (unsigned)S * kBPixelBytes - (unsigned)ln.m * kBHeadBytes;
+        rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(value) + plane, 0, kBf16 ? nrec / 2 : nrec, 0x00020000);
+        rs_g = __builtin_amdgcn_make_buffer_rsrc(grad_value + plane, 0, nrec, 0x00020000);
+        lane_off = (unsigned)ln.c * 4u;
+        lane_off_v = (unsigned)ln.c * (unsigned)sizeof(T);
+    }
+    __device__ __forceinline__ float load(unsigned off) const
+    {
+        if constexpr (kBf16)
+            return bf16_bits_to_f32(__builtin_amdgcn_raw_buffer_load_b16(rs_v, (off >> 1) + lane_off_v, 0, 0));
+        else
+            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_v, off + lane_off_v, 0, 0));
+    }
+    __device__ __forceinline__ void add(float v, unsigned off) const
+    {
+        __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32(v, rs_g, off + lane_off, 0, 0);
+    }
+};
+
+// Lane (pair, c) stages point c of its query: (x, y) in pixel coordinates of level l = c / P, `weight` its attention weight.
+// Returns whether the point is inside its level (false for a NaN location, whose every derived value is then selected to 0).
+// DET: also one record per corner: key = the row of grad_value it adds to -- (image, pixel, head), or head-major (image, head,
+// pixel); all ones: no row --, weight = bilinear weight * attention weight; the record's position (hrow + c) * 4 + corner IS its
+// identity (query, head, point, corner).
+template <bool DET, bool HM>
+__device__ __forceinline__ bool bwd_stage_point(BwdShared &sh, const BwdLane &ln, float x, float y, float weight, int S, size_t hrow,
+                                                unsigned *__restrict__ rec_key, unsigned *__restrict__ rec_id, float *__restrict__ rec_w)
+{
+    constexpr unsigned kPix = HM ? kBHeadBytes : kBPixelBytes;
+    const int l = ln.c / kBP;
+    const int h = sh.lvl.h[l], w = sh.lvl.w[l];
+    const bool inside = ln.qok && (y > -1.f) && (x > -1.f) && (y < (float)h) && (x < (float)w);
+    const float xf = floorf(x), yf = floorf(y);
+    const int x0 = inside ? (int)xf : 0, y0 = inside ? (int)yf : 0;
+    const float lx = inside ? x - xf : 0.f, ly = inside ? y - yf : 0.f;   // NaN-safe
+    const bool okx0 = inside && x0 >= 0, okx1 = inside && x0 + 1 <= w - 1;
+    const bool oky0 = y0 >= 0, oky1 = y0 + 1 <= h - 1;
+    const unsigned base = (unsigned)(sh.lvl.start[l] + y0 * w + x0) * kPix;
+    const unsigned rowb = (unsigned)w * kPix;
+    u32x4 o;
+    o.x = (okx0 && oky0) ? base : kBInvalid;
+    o.y = (okx1 && oky0) ? base + kPix : kBInvalid;
+    o.z = (okx0 && oky1) ? base + rowb : kBInvalid;
+    o.w = (okx1 && oky1) ? base + rowb + kPix : kBInvalid;
+    const float a = inside ? weight : 0.f;
+    sh.st_off[ln.wave][ln.c * 2 + ln.pair] = o;
+    sh.st_frac[ln.wave][ln.c * 2 + ln.pair] = f32x4{1.f - ly, 1.f - lx, ly, lx};
+    sh.st_misc[ln.wave][ln.c * 2 + ln.pair] = f32x4{a, (float)w, (float)h, inside ? 1.f : 0.f};
+    if constexpr (DET) {
+        if (ln.qok) {
+            const unsigned rbase = HM ? (unsigned)(((size_t)ln.b * kBH + ln.m) * (size_t)S) : (unsigned)((size_t)ln.b * S) * kBH + (unsigned)ln.m;
+            const float hy = 1.f - ly, hx = 1.f - lx;
+            auto key = [&](unsigned ob) { return ob == kBInvalid ? 0xffffffffu : rbase + (ob / kPix) * (HM ? 1u : (unsigned)kBH); };
+            const size_t rec = (hrow + ln.c) * 4;
+            *reinterpret_cast<u32x4 *>(rec_key + rec) = u32x4{key(o.x), key(o.y), key(o.z), key(o.w)};
+            *reinterpret_cast<u32x4 *>(rec_id + rec) = u32x4{(unsigned)rec, (unsigned)rec + 1u, (unsigned)rec + 2u, (unsigned)rec + 3u};
+            *reinterpret_cast<f32x4 *>(rec_w + rec) = f32x4{(hy * hx) * a, (hy * lx) * a, (ly * hx) * a, (ly * lx) * a};
+        }
+    }
+    return inside;
+}
+
+// what a wave's lanes staged becomes visible to the wave
+__device__ __forceinline__ void bwd_wave_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct BwdSums {
+    float s, gx, gy;                // d loss / d weight, d loss / d (normalised x), d loss / d (normalised y)
+};
+
+// Every lane (channel c, top gradient g) walks the LP staged points of its query; -> the sums of point `c`, kept by lane c of the pair
+template <bool DET, typename Plane>
+__device__ __forceinline__ BwdSums bwd_point_loop(const BwdShared &sh, const BwdLane &ln, const Plane &pl, int LP, float g)
+{
+    const u32x4 *soff = sh.st_off[ln.wave];
+    const f32x4 *sfrac = sh.st_frac[ln.wave];
+    const f32x4 *smisc = sh.st_misc[ln.wave];
+    BwdSums my{0.f, 0.f, 0.f};
+
+#pragma nounroll
+    for (int pt = 0; pt < LP; ++pt) {
+        const u32x4 o = soff[pt * 2 + ln.pair];
+        const f32x4 fr = sfrac[pt * 2 + ln.pair];      // hy, hx, ly, lx
+        const f32x4 mi = smisc[pt * 2 + ln.pair];      // weight (0 if outside), W, H, inside
+        const float v00 = pl.load(o.x), v01 = pl.load(o.y), v10 = pl.load(o.z), v11 = pl.load(o.w);
+        const float hy = fr.x, hx = fr.y, ly = fr.z, lx = fr.w;
+        const float ga = g * mi.x;                                   // top_grad * weight
+        if constexpr (!DET) {
+            pl.add((hy * hx) * ga, o.x);
+            pl.add((hy * lx) * ga, o.y);
+            pl.add((ly * hx) * ga, o.z);
+            pl.add((ly * lx) * ga, o.w);
+        }
+        // d/dx and d/dy of the bilinear sample (ms_deform_im2col_cuda.cuh:102-141)
+        const float dxs = hy * (v01 - v00) + ly * (v11 - v10);
+        const float dys = hx * (v10 - v00) + lx * (v11 - v01);
+        const float smp = (hy * hx) * v00 + (hy * lx) * v01 + (ly * hx) * v10 + (ly * lx) * v11;
+        const float s = sum32(g * smp) * mi.w;                       // grad wrt the weight
+        const float gx = sum32(ga * dxs) * mi.y;                     // * W_l
+        const float gy = sum32(ga * dys) * mi.z;                     // * H_l
+        if (ln.c == pt) {
+            my.s = s;
+            my.gx = gx;
+            my.gy = gy;
+        }
+    }
+    return my;
+}
+
+// Materialised producer: sampling locations and attention weights as the reference operator takes them; the sums are the result.
 template <bool DET>
 __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_wave_kernel(
     const float *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ level_start,
@@ -56,120 +230,28 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_wave_kernel(
     float *__restrict__ grad_attn, unsigned *__restrict__ rec_key, unsigned *__restrict__ rec_id, float *__restrict__ rec_w)
 {
     const int LP = L * kBP;
-    __shared__ BwdLevels lvl;
-    // per wave, [point][pair]: corner offsets | {hy, hx, ly, lx} | {attn (0 if outside), W_l, H_l, inside}
-    __shared__ u32x4 st_off[kBWaves][kBMaxL * kBP * 2];
-    __shared__ f32x4 st_frac[kBWaves][kBMaxL * kBP * 2];
-    __shared__ f32x4 st_misc[kBWaves][kBMaxL * kBP * 2];
+    __shared__ BwdShared sh;
+    const BwdLane ln = bwd_prologue(sh, shapes, level_start, L, Nq, tiles_per_image, nblk);
+    const BwdPlane<float, false> pl(value, grad_value, ln, S);
+    const int c = ln.c;
+    const size_t row = (size_t)ln.b * Nq + (ln.qok ? ln.q : 0);
+    const size_t hrow = (row * kBH + ln.m) * (size_t)LP;
 
-    const int tid = threadIdx.x;
-    if (tid < L) {
-        lvl.h[tid] = (int)shapes[2 * tid];
-        lvl.w[tid] = (int)shapes[2 * tid + 1];
-        lvl.start[tid] = (int)level_start[tid];
-    }
-    __syncthreads();
-
-    // logical block -> (image b, head m, tile of 2*kBWaves consecutive queries)
-    const int logical = xcd_contiguous_block(blockIdx.x, nblk);
-    const int bm = logical / tiles_per_image;
-    const int tile = logical - bm * tiles_per_image;
-    const int b = bm / kBH, m = bm - b * kBH;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63, pair = lane >> 5, c = lane & 31;
-    const int q = (tile * kBWaves + wave) * 2 + pair;
-    const bool qok = q < Nq;
-
-    const size_t plane = (size_t)b * S * (kBH * kBD) + (size_t)m * kBD;
-    const unsigned nrec = (unsigned)S * kBPixelBytes - (unsigned)m * kBHeadBytes;
-    const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(value) + plane, 0, nrec, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(grad_value + plane, 0, nrec, 0x00020000);
-    const unsigned lane_off = (unsigned)c * 4u;
-
-    const size_t row = (size_t)b * Nq + (qok ? q : 0);
-    const size_t hrow = (row * kBH + m) * (size_t)LP;
-    u32x4 *soff = st_off[wave];
-    f32x4 *sfrac = st_frac[wave];
-    f32x4 *smisc = st_misc[wave];
-
-    // ---- set-up: lane (pair, c) prepares point c (and c + 32 for L > 8 ... LP <= 32) of its query ---------------
     if (c < LP) {
-        const int pt = c;
-        const f32x2 xy = *reinterpret_cast<const f32x2 *>(loc + (hrow + pt) * 2);
-        const float a = attn[hrow + pt];
-        const int l = pt / kBP;
-        const int h = lvl.h[l], w = lvl.w[l];
+        const f32x2 xy = *reinterpret_cast<const f32x2 *>(loc + (hrow + c) * 2);
+        const float a = attn[hrow + c];
+        const int l = c / kBP;
+        const int h = sh.lvl.h[l], w = sh.lvl.w[l];
         const float x = xy.x * (float)w - 0.5f, y = xy.y * (float)h - 0.5f;
-        const bool inside = qok && (y > -1.f) && (x > -1.f) && (y < (float)h) && (x < (float)w);
-        const float xf = floorf(x), yf = floorf(y);
-        const int x0 = inside ? (int)xf : 0, y0 = inside ? (int)yf : 0;
-        const float lx = inside ? x - xf : 0.f, ly = inside ? y - yf : 0.f;   // NaN-safe
-        const bool okx0 = inside && x0 >= 0, okx1 = inside && x0 + 1 <= w - 1;
-        const bool oky0 = y0 >= 0, oky1 = y0 + 1 <= h - 1;
-        const unsigned base = (unsigned)(lvl.start[l] + y0 * w + x0) * kBPixelBytes;
-        const unsigned rowb = (unsigned)w * kBPixelBytes;
-        u32x4 o;
-        o.x = (okx0 && oky0) ? base : kBInvalid;
-        o.y = (okx1 && oky0) ? base + kBPixelBytes : kBInvalid;
-        o.z = (okx0 && oky1) ? base + rowb : kBInvalid;
-        o.w = (okx1 && oky1) ? base + rowb + kBPixelBytes : kBInvalid;
-        soff[pt * 2 + pair] = o;
-        sfrac[pt * 2 + pair] = f32x4{1.f - ly, 1.f - lx, ly, lx};
-        smisc[pt * 2 + pair] = f32x4{inside ? a : 0.f, (float)w, (float)h, inside ? 1.f : 0.f};
-        if constexpr (DET) {
-            // one record per corner: key = the (image, pixel, head) row of grad_value it adds to (all ones: no row), weight =
-            // bilinear weight * attention weight; the record's position IS its identity (query, head, point, corner)
-            if (qok) {
-                const unsigned rbase = (unsigned)((size_t)b * S) * kBH + (unsigned)m;
-                const float hy = 1.f - ly, hx = 1.f - lx, aa = inside ? a : 0.f;
-                auto key = [&](unsigned off) { return off == kBInvalid ? 0xffffffffu : rbase + (off / kBPixelBytes) * kBH; };
-                const size_t rec = (hrow + pt) * 4;
-                *reinterpret_cast<u32x4 *>(rec_key + rec) = u32x4{key(o.x), key(o.y), key(o.z), key(o.w)};
-                *reinterpret_cast<u32x4 *>(rec_id + rec) = u32x4{(unsigned)rec, (unsigned)rec + 1u, (unsigned)rec + 2u, (unsigned)rec + 3u};
-                *reinterpret_cast<f32x4 *>(rec_w + rec) = f32x4{(hy * hx) * aa, (hy * lx) * aa, (ly * hx) * aa, (ly * lx) * aa};
-            }
-        }
+        bwd_stage_point<DET, false>(sh, ln, x, y, a, S, hrow, rec_key, rec_id, rec_w);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    bwd_wave_fence();
 
-    const float g = grad_out[row * (kBH * kBD) + m * kBD + c];
-    float my_ga = 0.f, my_gx = 0.f, my_gy = 0.f;                  // results of point `c`, kept by lane c of the pair
-
-#pragma unroll 2
-    for (int pt = 0; pt < LP; ++pt) {
-        const u32x4 o = soff[pt * 2 + pair];
-        const f32x4 fr = sfrac[pt * 2 + pair];      // hy, hx, ly, lx
-        const f32x4 mi = smisc[pt * 2 + pair];      // attn (0 if outside), W, H, inside
-        const float v00 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_v, o.x + lane_off, 0, 0));
-        const float v01 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_v, o.y + lane_off, 0, 0));
-        const float v10 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_v, o.z + lane_off, 0, 0));
-        const float v11 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_v, o.w + lane_off, 0, 0));
-        const float hy = fr.x, hx = fr.y, ly = fr.z, lx = fr.w;
-        const float ga = g * mi.x;                                   // top_grad * attn_weight
-        if constexpr (!DET) {
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((hy * hx) * ga, rs_g, o.x + lane_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((hy * lx) * ga, rs_g, o.y + lane_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((ly * hx) * ga, rs_g, o.z + lane_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((ly * lx) * ga, rs_g, o.w + lane_off, 0, 0);
-        }
-        // d/dx and d/dy of the bilinear sample (ms_deform_im2col_cuda.cuh:102-141)
-        const float dxs = hy * (v01 - v00) + ly * (v11 - v10);
-        const float dys = hx * (v10 - v00) + lx * (v11 - v01);
-        const float smp = (hy * hx) * v00 + (hy * lx) * v01 + (ly * hx) * v10 + (ly * lx) * v11;
-        const float ga_w = sum32(g * smp) * mi.w;                    // grad wrt attention weight
-        const float gx = sum32(ga * dxs) * mi.y;                     // * W_l
-        const float gy = sum32(ga * dys) * mi.z;                     // * H_l
-        if (c == pt) {
-            my_ga = ga_w;
-            my_gx = gx;
-            my_gy = gy;
-        }
-    }
-    if (qok && c < LP) {                                              // 16-20 contiguous floats per query-head
-        grad_attn[hrow + c] = my_ga;
-        *reinterpret_cast<f32x2 *>(grad_loc + (hrow + c) * 2) = f32x2{my_gx, my_gy};
+    const float g = grad_out[row * (kBH * kBD) + ln.m * kBD + c];
+    const BwdSums my = bwd_point_loop<DET>(sh, ln, pl, LP, g);
+    if (ln.qok && c < LP) {                                           // 16-20 contiguous floats per query-head
+        grad_attn[hrow + c] = my.s;
+        *reinterpret_cast<f32x2 *>(grad_loc + (hrow + c) * 2) = f32x2{my.gx, my.gy};
     }
 }
 
@@ -186,25 +268,17 @@ __device__ __forceinline__ void st_val(uint16_t *p, float v) { *p = (uint16_t)f3
 __device__ __forceinline__ void st_val2(float *p, float x, float y) { *reinterpret_cast<f32x2 *>(p) = f32x2{x, y}; }
 __device__ __forceinline__ void st_val2(uint16_t *p, float x, float y) { *reinterpret_cast<unsigned *>(p) = pack_bf16x2(x, y); }
 
-// Fused-producer backward (rdetr_msda_backward_fused_*): the inputs of the fused forward (raw offsets and logits in value's dtype,
-// reference points) instead of materialised locations / weights.  The work shape of msda_bwd_wave_kernel -- one wave = one head x
-// two queries, one channel per lane, the four corner rows re-gathered, fp32 atomics covering two full 128-byte grad_value head
-// rows per wave instruction -- with three changes:
+// Fused producer (rdetr_msda_backward_fused_*): the inputs of the fused forward (raw offsets and logits in value's dtype, reference
+// points) instead of materialised locations / weights.
 //   * set-up: lane (pair, c) recomputes the soft-maxed weight and the sampling location of point c (L*P <= 32: both queries in 64
 //     lanes, lanes c >= L*P are -inf padding slots) with the arithmetic of the forward kernel for that dtype (msda_fwd.hip: fp32
 //     expf and divisions; bf16 the hardware exp2 and products with reciprocals), max and sum by xor-shuffles, so the backward
 //     differentiates the weights and locations the forward used;
-//   * bf16 value rows (64 bytes per head) are loaded two bytes per lane and converted to fp32; grad_value stays fp32;
 //   * closing step, in the set-up layout (coalesced rows): softmax backward grad_logit_k = w_k (s_k - sum_j w_j s_j) with
 //     s_k = <grad_out, sample_k>, the location chain rule onto the offsets, and per-level sums onto the reference point.
 // Every sum except grad_value's is a fixed shuffle tree: grad_offsets / grad_logits / grad_ref are the same bits in both modes.
-//
-// HM (rdetr_msda_backward_fused_hm_bf16): value and grad_value are HEAD-MAJOR [B,H,S,D] -- an addressing matter only.  The plane of
-// (image b, head m) starts at ((b*H + m) * S) * D, a pixel is one 128-byte grad row (64 bytes of bf16 value) instead of 1 KiB
-// (512), the descriptors cover exactly that plane (an out-of-level corner and anything past pixel S-1 is dropped, it cannot land
-// in the next head's plane), and a deterministic key is the row (b*H + m)*S + pixel of the head-major grad_value.  The raw
-// producer inputs and their gradients take row strides (elements), so that each pair can be two column slices of one
-// [B*Nq, 3*H*L*P] buffer.  Set-up, corner products, shuffle trees and closing step are this one body for every instantiation.
+// HM (rdetr_msda_backward_fused_hm_bf16): value and grad_value are head-major (BwdPlane), and the raw producer inputs and their
+// gradients take row strides (elements), so that each pair can be two column slices of one [B*Nq, 3*H*L*P] buffer.
 template <typename T, bool DET, bool HM>
 __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
     const T *__restrict__ value, const int64_t *__restrict__ shapes, const int64_t *__restrict__ level_start,
@@ -214,61 +288,25 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
     unsigned *__restrict__ rec_id, float *__restrict__ rec_w, int ld_off, int ld_lg, int ld_goff, int ld_glg)
 {
     constexpr bool kBf16 = sizeof(T) == 2;
-    constexpr unsigned kPix = HM ? kBHeadBytes : kBPixelBytes;         // bytes from one pixel's grad_value row to the next
     const int LP = L * kBP;
-    __shared__ BwdLevels lvl;
-    __shared__ u32x4 st_off[kBWaves][kBMaxL * kBP * 2];
-    __shared__ f32x4 st_frac[kBWaves][kBMaxL * kBP * 2];
-    __shared__ f32x4 st_misc[kBWaves][kBMaxL * kBP * 2];
+    __shared__ BwdShared sh;
+    const BwdLane ln = bwd_prologue(sh, shapes, level_start, L, Nq, tiles_per_image, nblk);
+    const BwdPlane<T, HM> pl(value, grad_value, ln, S);
+    const int m = ln.m, c = ln.c;
+    const bool qok = ln.qok;
 
-    const int tid = threadIdx.x;
-    if (tid < L) {
-        lvl.h[tid] = (int)shapes[2 * tid];
-        lvl.w[tid] = (int)shapes[2 * tid + 1];
-        lvl.start[tid] = (int)level_start[tid];
-    }
-    __syncthreads();
-
-    const int logical = xcd_contiguous_block(blockIdx.x, nblk);
-    const int bm = logical / tiles_per_image;
-    const int tile = logical - bm * tiles_per_image;
-    const int b = bm / kBH, m = bm - b * kBH;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63, pair = lane >> 5, c = lane & 31;
-    const int q = (tile * kBWaves + wave) * 2 + pair;
-    const bool qok = q < Nq;
-
-    // grad_value: fp32 [B,S,H,D], 1 KiB per pixel; value: T, sizeof(T) * 256 bytes per pixel -- the staged corner offsets are
-    // grad_value byte offsets, shifted right by one for a bf16 value (the invalid offset 0x80000000 stays out of range)
-    // (head-major: 128 / 64 bytes per pixel, one plane per descriptor)
-    const size_t plane = HM ? ((size_t)b * kBH + m) * (size_t)S * kBD : (size_t)b * S * (kBH * kBD) + (size_t)m * kBD;
-    const unsigned nrec = HM ? (unsigned)S * kBHeadBytes : (unsigned)S * kBPixelBytes - (unsigned)m * kBHeadBytes;
-    const __amdgpu_buffer_rsrc_t rs_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(value) + plane, 0,
-                                                                          kBf16 ? nrec / 2 : nrec, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(grad_value + plane, 0, nrec, 0x00020000);
-    const unsigned lane_off = (unsigned)c * 4u, lane_off_v = (unsigned)c * (unsigned)sizeof(T);
-    auto load_v = [&](unsigned off) {
-        if constexpr (kBf16)
-            return bf16_bits_to_f32(__builtin_amdgcn_raw_buffer_load_b16(rs_v, (off >> 1) + lane_off_v, 0, 0));
-        else
-            return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_v, off + lane_off_v, 0, 0));
-    };
-
-    const size_t row = (size_t)b * Nq + (qok ? q : 0);
+    const size_t row = (size_t)ln.b * Nq + (qok ? ln.q : 0);
     const size_t hrow = (row * kBH + m) * (size_t)LP;
     // this (query, head)'s LP logits / 2*LP offsets and their gradients: dense rows, or (HM) rows ld_* elements apart
     const size_t i_lg = HM ? row * (size_t)ld_lg + (size_t)(m * LP) : hrow;
     const size_t i_off = HM ? row * (size_t)ld_off + (size_t)(m * LP) * 2 : hrow * 2;
     const size_t i_glg = HM ? row * (size_t)ld_glg + (size_t)(m * LP) : hrow;
     const size_t i_goff = HM ? row * (size_t)ld_goff + (size_t)(m * LP) * 2 : hrow * 2;
-    u32x4 *soff = st_off[wave];
-    f32x4 *sfrac = st_frac[wave];
-    f32x4 *smisc = st_misc[wave];
 
     // ---- set-up: lane (pair, c) = point c of its query; softmax over the 32 lanes of the pair -------------------------------
     const bool pok = c < LP;
     const int l = pok ? c / kBP : 0;
-    const int h = lvl.h[l], w = lvl.w[l];
+    const int h = sh.lvl.h[l], w = sh.lvl.w[l];
     const float lg = pok ? ld_f32(logits + i_lg + c) : -__builtin_inff();
     const f32x2 off = pok ? ld_f32x2(offsets + i_off + c * 2) : f32x2{0.f, 0.f};
     float mx = lg;
@@ -293,70 +331,12 @@ __global__ __launch_bounds__(kBWaves *kWave) void msda_bwd_fused_kernel(
         xy.y = rc.y + off.y * (1.0f / kBP) * rc.w * 0.5f;
     }
     const float x = xy.x * (float)w - 0.5f, y = xy.y * (float)h - 0.5f;
-    const bool inside = pok && qok && (y > -1.f) && (x > -1.f) && (y < (float)h) && (x < (float)w);    // false for NaN
-    if (pok) {
-        const float xf = floorf(x), yf = floorf(y);
-        const int x0 = inside ? (int)xf : 0, y0 = inside ? (int)yf : 0;
-        const float lx = inside ? x - xf : 0.f, ly = inside ? y - yf : 0.f;
-        const bool okx0 = inside && x0 >= 0, okx1 = inside && x0 + 1 <= w - 1;
-        const bool oky0 = y0 >= 0, oky1 = y0 + 1 <= h - 1;
-        const unsigned base = (unsigned)(lvl.start[l] + y0 * w + x0) * kPix;
-        const unsigned rowb = (unsigned)w * kPix;
-        u32x4 o;
-        o.x = (okx0 && oky0) ? base : kBInvalid;
-        o.y = (okx1 && oky0) ? base + kPix : kBInvalid;
-        o.z = (okx0 && oky1) ? base + rowb : kBInvalid;
-        o.w = (okx1 && oky1) ? base + rowb + kPix : kBInvalid;
-        const float a = inside ? wk : 0.f;
-        soff[c * 2 + pair] = o;
-        sfrac[c * 2 + pair] = f32x4{1.f - ly, 1.f - lx, ly, lx};
-        smisc[c * 2 + pair] = f32x4{a, (float)w, (float)h, inside ? 1.f : 0.f};
-        if constexpr (DET) {
-            if (qok) {                                   // the records of msda_bwd_wave_kernel<true>
-                // key = row of grad_value: (image, pixel, head), or head-major (image, head, pixel)
-                const unsigned rbase = HM ? (unsigned)(((size_t)b * kBH + m) * (size_t)S) : (unsigned)((size_t)b * S) * kBH + (unsigned)m;
-                const float hy = 1.f - ly, hx = 1.f - lx;
-                auto key = [&](unsigned ob) { return ob == kBInvalid ? 0xffffffffu : rbase + (ob / kPix) * (HM ? 1u : (unsigned)kBH); };
-                const size_t rec = (hrow + c) * 4;
-                *reinterpret_cast<u32x4 *>(rec_key + rec) = u32x4{key(o.x), key(o.y), key(o.z), key(o.w)};
-                *reinterpret_cast<u32x4 *>(rec_id + rec) = u32x4{(unsigned)rec, (unsigned)rec + 1u, (unsigned)rec + 2u, (unsigned)rec + 3u};
-                *reinterpret_cast<f32x4 *>(rec_w + rec) = f32x4{(hy * hx) * a, (hy * lx) * a, (ly * hx) * a, (ly * lx) * a};
-            }
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    const bool inside = pok && bwd_stage_point<DET, HM>(sh, ln, x, y, wk, S, hrow, rec_key, rec_id, rec_w);
+    bwd_wave_fence();
 
     const float g = ld_f32(grad_out + row * (kBH * kBD) + m * kBD + c);
-    float my_s = 0.f, my_gx = 0.f, my_gy = 0.f;                   // results of point `c`, kept by lane c of the pair
-
-#pragma unroll 2
-    for (int pt = 0; pt < LP; ++pt) {
-        const u32x4 o = soff[pt * 2 + pair];
-        const f32x4 fr = sfrac[pt * 2 + pair];      // hy, hx, ly, lx
-        const f32x4 mi = smisc[pt * 2 + pair];      // weight (0 if outside), W, H, inside
-        const float v00 = load_v(o.x), v01 = load_v(o.y), v10 = load_v(o.z), v11 = load_v(o.w);
-        const float hy = fr.x, hx = fr.y, ly = fr.z, lx = fr.w;
-        const float ga = g * mi.x;
-        if constexpr (!DET) {
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((hy * hx) * ga, rs_g, o.x + lane_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((hy * lx) * ga, rs_g, o.y + lane_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((ly * hx) * ga, rs_g, o.z + lane_off, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_atomic_fadd_f32((ly * lx) * ga, rs_g, o.w + lane_off, 0, 0);
-        }
-        const float dxs = hy * (v01 - v00) + ly * (v11 - v10);
-        const float dys = hx * (v10 - v00) + lx * (v11 - v01);
-        const float smp = (hy * hx) * v00 + (hy * lx) * v01 + (ly * hx) * v10 + (ly * lx) * v11;
-        const float s = sum32(g * smp) * mi.w;                       // d loss / d weight_k
-        const float gx = sum32(ga * dxs) * mi.y;                     // d loss / d loc_k (normalised x), * W_l
-        const float gy = sum32(ga * dys) * mi.z;                     // ... y, * H_l
-        if (c == pt) {
-            my_s = s;
-            my_gx = gx;
-            my_gy = gy;
-        }
-    }
+    const BwdSums my = bwd_point_loop<DET>(sh, ln, pl, LP, g);
+    const float my_s = my.s, my_gx = my.gx, my_gy = my.gy;
 
     // ---- closing step, lane = point: softmax backward, offsets, reference-point partials ------------------------------------
     const float tot = sum32(wk * my_s);                               // padding lanes: 0 * 0
@@ -476,42 +456,17 @@ __global__ __launch_bounds__(256) void msda_bwd_generic_kernel(
 
 using namespace rdetr;
 
-extern "C" int rdetr_msda_backward_f32(const float *value, const int64_t *spatial_shapes,
-                                       const int64_t *level_start_index, const float *sampling_loc,
-                                       const float *attn_weight, const float *grad_out, int B, int S, int H, int D,
-                                       int L, int Nq, int P, float *grad_value, float *grad_sampling_loc,
-                                       float *grad_attn_weight, void *stream)
+// ---- host pipeline: one grid rule, one deterministic-workspace layout, one sort + segment-sum tail -----------------------------
+namespace {
+// one block = one head x 2*kBWaves queries; false: more blocks than a grid dimension holds
+bool bwd_grid(int B, int Nq, int &tiles, int &nblk)
 {
-    if (B < 0 || S < 0 || Nq < 0 || H <= 0 || D <= 0 || L <= 0 || P <= 0) return RDETR_ERR_INVALID_ARG;
-    if (B == 0 || Nq == 0) return RDETR_OK;
-    if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight || !grad_out || !grad_value ||
-        !grad_sampling_loc || !grad_attn_weight || S == 0)
-        return RDETR_ERR_INVALID_ARG;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const bool fast = H == kBH && D == kBD && P == kBP && L <= kBMaxL && al16(value) && al16(grad_out) &&
-                      al16(grad_value) && reinterpret_cast<uintptr_t>(sampling_loc) % 8 == 0 &&
-                      reinterpret_cast<uintptr_t>(grad_sampling_loc) % 8 == 0 &&
-                      (long long)S * kBPixelBytes < (1ll << 31);
-    if (fast) {
-        const int tiles = (Nq + 2 * kBWaves - 1) / (2 * kBWaves);
-        const long long nblk = (long long)B * kBH * tiles;
-        if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(msda_bwd_wave_kernel<false>, dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value,
-                           spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, S, L, Nq, tiles,
-                           (int)nblk, grad_value, grad_sampling_loc, grad_attn_weight, nullptr, nullptr, nullptr);
-        return launch_status();
-    }
-    const long long total = (long long)B * Nq * H * L * P;
-    const long long want = (total + 255) / 256;
-    hipLaunchKernelGGL(msda_bwd_generic_kernel, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, st, value,
-                       spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, S, H, D, L, Nq, P, total,
-                       grad_value, grad_sampling_loc, grad_attn_weight);
-    return launch_status();
+    tiles = (Nq + 2 * kBWaves - 1) / (2 * kBWaves);
+    const long long n = (long long)B * kBH * tiles;
+    nblk = (int)n;
+    return n <= 0x7fffffffll;
 }
 
-// ---- deterministic mode --------------------------------------------------------------------------------------------------------
-namespace {
 struct DetLayout {
     long long nrec, nrows;
     size_t off_key, off_id, off_w, off_skey, off_sid, off_tmp, tmp_bytes, total;
@@ -535,8 +490,77 @@ bool det_layout(int B, int S, int L, int Nq, DetLayout &d)
     d.total = d.off_tmp + up(d.tmp_bytes);
     return true;
 }
+
+struct DetPtrs {
+    unsigned *rec_key, *rec_id;
+    float *rec_w;
+    unsigned *skey, *sid;
+    void *tmp;
+};
+DetPtrs det_pointers(void *workspace, const DetLayout &d)
+{
+    unsigned char *ws = static_cast<unsigned char *>(workspace);
+    return DetPtrs{reinterpret_cast<unsigned *>(ws + d.off_key), reinterpret_cast<unsigned *>(ws + d.off_id),
+                   reinterpret_cast<float *>(ws + d.off_w), reinterpret_cast<unsigned *>(ws + d.off_skey),
+                   reinterpret_cast<unsigned *>(ws + d.off_sid), ws + d.off_tmp};
+}
+
+// Deterministic mode after the records are written: sort them by key, then every row of grad_value = the sum of its records.
+// No records (nrec == 0): nothing to sort, every row is zero.
+template <typename G>
+int det_sort_and_sum(const DetLayout &d, const DetPtrs &p, const G *grad_out, int L, float *grad_value, hipStream_t st)
+{
+    size_t tmp = d.tmp_bytes;
+    if (d.nrec > 0 && hipcub::DeviceRadixSort::SortPairs(p.tmp, tmp, p.rec_key, p.skey, p.rec_id, p.sid, (int)d.nrec, 0, d.key_bits, st) != hipSuccess)
+        return RDETR_ERR_LAUNCH;
+    hipLaunchKernelGGL(msda_bwd_segment_sum_kernel<G>, dim3((unsigned)((d.nrows + 7) / 8)), dim3(256), 0, st, p.skey, p.sid, p.rec_w, grad_out,
+                       d.nrec, d.nrows, L * kBP, grad_value);
+    return launch_status();
+}
+
+// what both materialised entries need of their operands besides grad_value: every pointer present ...
+bool wave_operands_present(const void *value, const void *shapes, const void *level_start, const void *loc, const void *attn,
+                           const void *grad_out, const void *grad_loc, const void *grad_attn)
+{
+    return value && shapes && level_start && loc && attn && grad_out && grad_loc && grad_attn;
+}
+// ... and, for msda_bwd_wave_kernel, the alignment of its vector accesses and a plane within a buffer descriptor's 2 GiB
+bool wave_operands_fit(const void *value, const void *grad_out, const void *grad_value, const void *loc, const void *grad_loc, int S)
+{
+    return aligned_to(value, 16) && aligned_to(grad_out, 16) && aligned_to(grad_value, 16) && aligned_to(loc, 8) &&
+           aligned_to(grad_loc, 8) && (long long)S * kBPixelBytes < (1ll << 31);
+}
 }  // namespace
 
+extern "C" int rdetr_msda_backward_f32(const float *value, const int64_t *spatial_shapes,
+                                       const int64_t *level_start_index, const float *sampling_loc,
+                                       const float *attn_weight, const float *grad_out, int B, int S, int H, int D,
+                                       int L, int Nq, int P, float *grad_value, float *grad_sampling_loc,
+                                       float *grad_attn_weight, void *stream)
+{
+    if (B < 0 || S < 0 || Nq < 0 || H <= 0 || D <= 0 || L <= 0 || P <= 0) return RDETR_ERR_INVALID_ARG;
+    if (B == 0 || Nq == 0) return RDETR_OK;
+    if (!wave_operands_present(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_sampling_loc,
+                               grad_attn_weight) || !grad_value || S == 0)
+        return RDETR_ERR_INVALID_ARG;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (H == kBH && D == kBD && P == kBP && L <= kBMaxL && wave_operands_fit(value, grad_out, grad_value, sampling_loc, grad_sampling_loc, S)) {
+        int tiles, nblk;
+        if (!bwd_grid(B, Nq, tiles, nblk)) return RDETR_ERR_UNSUPPORTED;
+        hipLaunchKernelGGL(msda_bwd_wave_kernel<false>, dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value,
+                           spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, S, L, Nq, tiles,
+                           nblk, grad_value, grad_sampling_loc, grad_attn_weight, nullptr, nullptr, nullptr);
+        return launch_status();
+    }
+    const long long total = (long long)B * Nq * H * L * P;
+    const long long want = (total + 255) / 256;
+    hipLaunchKernelGGL(msda_bwd_generic_kernel, dim3((unsigned)(want < 65536 ? want : 65536)), dim3(256), 0, st, value,
+                       spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, S, H, D, L, Nq, P, total,
+                       grad_value, grad_sampling_loc, grad_attn_weight);
+    return launch_status();
+}
+
+// ---- deterministic mode --------------------------------------------------------------------------------------------------------
 extern "C" long long rdetr_msda_backward_det_workspace_bytes(int B, int S, int H, int D, int L, int Nq, int P)
 {
     if (B <= 0 || S <= 0 || Nq <= 0 || H != kBH || D != kBD || P != kBP || L <= 0 || L > kBMaxL) return 0;
@@ -555,37 +579,26 @@ extern "C" int rdetr_msda_backward_det_f32(const float *value, const int64_t *sp
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (B == 0 || S == 0) return RDETR_OK;
     if (Nq == 0) {                                                              // no records: every row of grad_value is zero
-        hipLaunchKernelGGL(msda_bwd_segment_sum_kernel<float>, dim3((unsigned)(((long long)B * S * kBH + 7) / 8)), dim3(256), 0, st, nullptr, nullptr,
-                           nullptr, nullptr, 0ll, (long long)B * S * kBH, L * kBP, grad_value);
-        return launch_status();
+        DetLayout none{};
+        none.nrows = (long long)B * S * kBH;
+        return det_sort_and_sum<float>(none, DetPtrs{}, nullptr, L, grad_value, st);
     }
-    if (!value || !spatial_shapes || !level_start_index || !sampling_loc || !attn_weight || !grad_out || !grad_sampling_loc ||
-        !grad_attn_weight || !workspace)
+    if (!wave_operands_present(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_out, grad_sampling_loc,
+                               grad_attn_weight) || !workspace)
         return RDETR_ERR_INVALID_ARG;
-    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (!(al16(value) && al16(grad_out) && al16(grad_value) && al16(workspace) && reinterpret_cast<uintptr_t>(sampling_loc) % 8 == 0 &&
-          reinterpret_cast<uintptr_t>(grad_sampling_loc) % 8 == 0 && (long long)S * kBPixelBytes < (1ll << 31)))
+    if (!wave_operands_fit(value, grad_out, grad_value, sampling_loc, grad_sampling_loc, S) || !aligned_to(workspace, 16))
         return RDETR_ERR_UNSUPPORTED;
     DetLayout d;
     if (!det_layout(B, S, L, Nq, d)) return RDETR_ERR_UNSUPPORTED;
     if (workspace_bytes < (long long)d.total) return RDETR_ERR_INVALID_ARG;
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    unsigned *rec_key = reinterpret_cast<unsigned *>(ws + d.off_key), *rec_id = reinterpret_cast<unsigned *>(ws + d.off_id);
-    float *rec_w = reinterpret_cast<float *>(ws + d.off_w);
-    unsigned *skey = reinterpret_cast<unsigned *>(ws + d.off_skey), *sid = reinterpret_cast<unsigned *>(ws + d.off_sid);
-    const int tiles = (Nq + 2 * kBWaves - 1) / (2 * kBWaves);
-    const long long nblk = (long long)B * kBH * tiles;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    const DetPtrs p = det_pointers(workspace, d);
+    int tiles, nblk;
+    if (!bwd_grid(B, Nq, tiles, nblk)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(msda_bwd_wave_kernel<true>, dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, spatial_shapes,
-                       level_start_index, sampling_loc, attn_weight, grad_out, S, L, Nq, tiles, (int)nblk, grad_value, grad_sampling_loc,
-                       grad_attn_weight, rec_key, rec_id, rec_w);
+                       level_start_index, sampling_loc, attn_weight, grad_out, S, L, Nq, tiles, nblk, grad_value, grad_sampling_loc,
+                       grad_attn_weight, p.rec_key, p.rec_id, p.rec_w);
     if (launch_status() != RDETR_OK) return RDETR_ERR_LAUNCH;
-    size_t tmp = d.tmp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(ws + d.off_tmp, tmp, rec_key, skey, rec_id, sid, (int)d.nrec, 0, d.key_bits, st) != hipSuccess)
-        return RDETR_ERR_LAUNCH;
-    hipLaunchKernelGGL(msda_bwd_segment_sum_kernel<float>, dim3((unsigned)((d.nrows + 7) / 8)), dim3(256), 0, st, skey, sid, rec_w, grad_out, d.nrec,
-                       d.nrows, L * kBP, grad_value);
-    return launch_status();
+    return det_sort_and_sum(d, p, grad_out, L, grad_value, st);
 }
 
 // ---- fused-producer backward ---------------------------------------------------------------------------------------------------
@@ -613,18 +626,16 @@ static int msda_backward_fused(const T *value, const int64_t *shapes, const int6
         S == 0)
         return RDETR_ERR_INVALID_ARG;
     if (H != kBH || D != kBD || P != kBP || L > kBMaxL) return RDETR_ERR_UNSUPPORTED;
-    auto al = [](const void *p, size_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
-    if (!(al(value, 16) && al(grad_value, 16) && al(grad_out, sizeof(T)) && al(offsets, 2 * sizeof(T)) && al(logits, sizeof(T)) &&
-          al(grad_offsets, 2 * sizeof(T)) && al(grad_logits, sizeof(T)) && al(ref, 16) && al(grad_ref_partial, 16) &&
-          (!workspace || al(workspace, 16))))
+    if (!(aligned_to(value, 16) && aligned_to(grad_value, 16) && aligned_to(grad_out, sizeof(T)) && aligned_to(offsets, 2 * sizeof(T)) &&
+          aligned_to(logits, sizeof(T)) && aligned_to(grad_offsets, 2 * sizeof(T)) && aligned_to(grad_logits, sizeof(T)) &&
+          aligned_to(ref, 16) && aligned_to(grad_ref_partial, 16) && aligned_to(workspace, 16)))
         return HM ? RDETR_ERR_UNSUPPORTED : RDETR_ERR_INVALID_ARG;
     if ((long long)S * (HM ? kBHeadBytes : kBPixelBytes) >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
-    const int tiles = (Nq + 2 * kBWaves - 1) / (2 * kBWaves);
-    const long long nblk = (long long)B * kBH * tiles;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    int tiles, nblk;
+    if (!bwd_grid(B, Nq, tiles, nblk)) return RDETR_ERR_UNSUPPORTED;
     if (!workspace) {
         hipLaunchKernelGGL((msda_bwd_fused_kernel<T, false, HM>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes,
-                           level_start, offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, (int)nblk, grad_value, grad_offsets,
+                           level_start, offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, nblk, grad_value, grad_offsets,
                            grad_logits, grad_ref_partial, nullptr, nullptr, nullptr, ld_off, ld_lg, ld_goff, ld_glg);
         return launch_status();
     }
@@ -636,20 +647,12 @@ static int msda_backward_fused(const T *value, const int64_t *shapes, const int6
     DetLayout d;
     if (!det_layout(B, S, L, Nq, d)) return RDETR_ERR_UNSUPPORTED;
     if (workspace_bytes < (long long)d.total) return RDETR_ERR_INVALID_ARG;
-    unsigned char *ws = static_cast<unsigned char *>(workspace);
-    unsigned *rec_key = reinterpret_cast<unsigned *>(ws + d.off_key), *rec_id = reinterpret_cast<unsigned *>(ws + d.off_id);
-    float *rec_w = reinterpret_cast<float *>(ws + d.off_w);
-    unsigned *skey = reinterpret_cast<unsigned *>(ws + d.off_skey), *sid = reinterpret_cast<unsigned *>(ws + d.off_sid);
+    const DetPtrs p = det_pointers(workspace, d);
     hipLaunchKernelGGL((msda_bwd_fused_kernel<T, true, HM>), dim3((unsigned)nblk), dim3(kBWaves * kWave), 0, st, value, shapes, level_start,
-                       offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, (int)nblk, grad_value, grad_offsets, grad_logits,
-                       grad_ref_partial, rec_key, rec_id, rec_w, ld_off, ld_lg, ld_goff, ld_glg);
+                       offsets, logits, ref, ref_dim, grad_out, S, L, Nq, tiles, nblk, grad_value, grad_offsets, grad_logits,
+                       grad_ref_partial, p.rec_key, p.rec_id, p.rec_w, ld_off, ld_lg, ld_goff, ld_glg);
     if (launch_status() != RDETR_OK) return RDETR_ERR_LAUNCH;
-    size_t tmp = d.tmp_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(ws + d.off_tmp, tmp, rec_key, skey, rec_id, sid, (int)d.nrec, 0, d.key_bits, st) != hipSuccess)
-        return RDETR_ERR_LAUNCH;
-    hipLaunchKernelGGL(msda_bwd_segment_sum_kernel<T>, dim3((unsigned)((d.nrows + 7) / 8)), dim3(256), 0, st, skey, sid, rec_w, grad_out,
-                       d.nrec, d.nrows, L * kBP, grad_value);
-    return launch_status();
+    return det_sort_and_sum(d, p, grad_out, L, grad_value, st);
 }
 
 extern "C" int rdetr_msda_backward_fused_f32(const float *value, const int64_t *spatial_shapes, const int64_t *level_start_index,

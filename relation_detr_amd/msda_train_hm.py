@@ -24,17 +24,8 @@ from typing import Optional
 import torch
 
 from . import _lib, ops
-from .ops import _producer_row_stride, _require_contiguous, _require_device, _stream_ptr
-
-
-def _mask_u8(key_padding_mask: Optional[torch.Tensor], B: int, S: int) -> Optional[torch.Tensor]:
-    if key_padding_mask is None:
-        return None
-    if tuple(key_padding_mask.shape) != (B, S):
-        raise _lib.RdetrError("key_padding_mask must be [B, S]")
-    if key_padding_mask.dtype == torch.bool:
-        return key_padding_mask.contiguous().view(torch.uint8)
-    return key_padding_mask.to(torch.uint8).contiguous()
+from .ops import (_check_fused_operands, _mask_u8, _msda_backward_buffers, _producer_operand, _require_contiguous, _require_device,
+                  _stream_ptr, _value_dims)
 
 
 def grad_value_from_head_major(grad_hm: torch.Tensor, key_padding_mask: Optional[torch.Tensor] = None,
@@ -81,36 +72,20 @@ def ms_deform_attn_backward_fused_hm(value_hm: torch.Tensor, spatial_shapes: tor
     ``ops.ms_deform_attn_backward_fused`` on the [B,S,8,32] copy of the value."""
     _require_device(value_hm, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, grad_output,
                     grad_producer_out)
-    if value_hm.dim() != 4 or sampling_offsets.dim() != 6 or reference_points.dim() != 4 or value_hm.dtype != torch.bfloat16:
-        raise _lib.RdetrError("expected a bfloat16 value [B,H,S,D], sampling_offsets [B,Nq,H,L,P,2], reference_points [B,Nq,L,2|4]")
-    B, H, S, D = value_hm.shape
-    _, Nq, H2, L, P, two = sampling_offsets.shape
-    ref_dim = reference_points.shape[-1]
-    if (H2, two) != (H, 2) or sampling_offsets.shape[0] != B or tuple(attn_logits.shape) != (B, Nq, H, L * P):
-        raise _lib.RdetrError("sampling_offsets / attn_logits shapes do not match value")
-    if tuple(reference_points.shape[:3]) != (B, Nq, L) or ref_dim not in (2, 4):
-        raise _lib.RdetrError("reference_points must be [B, Nq, L, 2|4]")
-    if tuple(grad_output.shape) != (B, Nq, H * D):
-        raise _lib.RdetrError("grad_output must be [B, Nq, H*D]")
-    if (sampling_offsets.dtype != torch.bfloat16 or attn_logits.dtype != torch.bfloat16 or grad_output.dtype != torch.bfloat16
-            or reference_points.dtype != torch.float32):
-        raise _lib.RdetrError("sampling_offsets / attn_logits / grad_output must be bfloat16, reference_points float32")
-    if spatial_shapes.shape[0] != L:
-        raise _lib.RdetrError("spatial_shapes has a different number of levels than sampling_offsets")
+    if value_hm.dtype != torch.bfloat16:
+        raise _lib.RdetrError("ms_deform_attn_backward_fused_hm: expected a bfloat16 value [B,H,S,D]")
+    B, S, H, D = dims = _value_dims(value_hm, "bhsd")
+    Nq, L, P, ref_dim = _check_fused_operands(dims, value_hm.dtype, spatial_shapes, level_start_index, sampling_offsets, attn_logits,
+                                              reference_points)
+    if tuple(grad_output.shape) != (B, Nq, H * D) or grad_output.dtype != value_hm.dtype:
+        raise _lib.RdetrError("grad_output must be [B, Nq, H*D] in value's dtype")
     if not ops.msda_fast_path(H, D, L, P):
         raise _lib.RdetrError("ms_deform_attn_backward_fused_hm: H = 8, D = 32, P = 4, L <= 8 only")
-    ld_off = _producer_row_stride(sampling_offsets)
-    ld_lg = _producer_row_stride(attn_logits)
-    if ld_off is None:
-        sampling_offsets, ld_off = sampling_offsets.contiguous(), 0
-    if ld_lg is None:
-        attn_logits, ld_lg = attn_logits.contiguous(), 0
+    sampling_offsets, ld_off = _producer_operand(sampling_offsets)
+    attn_logits, ld_lg = _producer_operand(attn_logits)
     grad_output = grad_output.contiguous()
     _require_contiguous(value=value_hm, spatial_shapes=spatial_shapes, level_start_index=level_start_index,
                         reference_points=reference_points)
-    ops.check_levels(spatial_shapes, level_start_index, S)
-    if deterministic is None:
-        deterministic = torch.are_deterministic_algorithms_enabled()
     n_lg = H * L * P
     dev = value_hm.device
     if grad_producer_out is not None or _merged_slices(sampling_offsets, attn_logits, ld_off, ld_lg, n_lg):
@@ -127,18 +102,9 @@ def ms_deform_attn_backward_fused_hm(value_hm: torch.Tensor, spatial_shapes: tor
         grad_off = torch.empty(B, Nq, H, L, P, 2, dtype=torch.bfloat16, device=dev)
         grad_lg = torch.empty(B, Nq, H, L * P, dtype=torch.bfloat16, device=dev)
         ld_goff = ld_glg = 0
-    lib = _lib.load()
-    ws, nbytes = None, 0
-    if deterministic and B * Nq > 0:
-        nbytes = int(lib.rdetr_msda_backward_det_workspace_bytes(B, S, H, D, L, Nq, P))
-        if nbytes <= 0:
-            raise _lib.RdetrError("deterministic ms_deform_attn_backward_fused_hm: fewer than 2^31 sample corners only")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    # atomic mode adds into grad_value; the deterministic mode writes every row (nothing runs when B * Nq == 0)
-    grad_value = torch.empty(value_hm.shape, dtype=torch.float32, device=dev) if ws is not None else \
-        torch.zeros(value_hm.shape, dtype=torch.float32, device=dev)
-    grad_ref = torch.empty(B, Nq, H, L, ref_dim, dtype=torch.float32, device=dev) if need_ref_grad else None
-    st = lib.rdetr_msda_backward_fused_hm_bf16(
+    ws, nbytes, grad_value, grad_ref = _msda_backward_buffers("ms_deform_attn_backward_fused_hm", value_hm, dims, L, Nq, P,
+                                                              deterministic, ref_dim if need_ref_grad else None)
+    st = _lib.load().rdetr_msda_backward_fused_hm_bf16(
         value_hm.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_offsets.data_ptr(), ld_off,
         attn_logits.data_ptr(), ld_lg, reference_points.data_ptr(), ref_dim, grad_output.data_ptr(), B, S, H, D, L, Nq, P,
         None if ws is None else ws.data_ptr(), nbytes, grad_value.data_ptr(), grad_off.data_ptr(), ld_goff, grad_lg.data_ptr(), ld_glg,

@@ -231,6 +231,17 @@ def ms_deform_attn_forward(value: torch.Tensor, spatial_shapes: torch.Tensor, le
     return out
 
 
+def _mask_u8(key_padding_mask: Optional[torch.Tensor], B: int, S: int) -> Optional[torch.Tensor]:
+    """key_padding_mask [B, S] (bool or integer) as a contiguous uint8 tensor for the kernels; None stays None."""
+    if key_padding_mask is None:
+        return None
+    if tuple(key_padding_mask.shape) != (B, S):
+        raise _lib.RdetrError("key_padding_mask must be [B, S]")
+    if key_padding_mask.dtype == torch.bool:
+        return key_padding_mask.contiguous().view(torch.uint8)
+    return key_padding_mask.to(torch.uint8).contiguous()
+
+
 def value_to_head_major(value: torch.Tensor, key_padding_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Projected value [B,S,256] bf16 (rows may be a column slice of a wider buffer) -> head-major [B,8,S,32], the rows of
     padded positions zeroed on the way (ms_deform_attn.py:316-319): the layout the window kernel fills its LDS windows
@@ -241,15 +252,9 @@ def value_to_head_major(value: torch.Tensor, key_padding_mask: Optional[torch.Te
     B, S, _ = value.shape
     if value.stride(2) != 1 or (B > 1 and value.stride(0) != S * value.stride(1)) or value.stride(1) % 8 or value.data_ptr() % 16:
         value = value.contiguous()
-    mask_ptr = None
-    if key_padding_mask is not None:
-        if tuple(key_padding_mask.shape) != (B, S):
-            raise _lib.RdetrError("key_padding_mask must be [B, S]")
-        mask_u8 = key_padding_mask.contiguous().view(torch.uint8) if key_padding_mask.dtype == torch.bool \
-            else key_padding_mask.to(torch.uint8).contiguous()
-        mask_ptr = mask_u8.data_ptr()
+    mask = _mask_u8(key_padding_mask, B, S)
     out = torch.empty(B, 8, S, 32, dtype=torch.bfloat16, device=value.device)
-    st = _lib.load().rdetr_value_to_head_major_bf16(value.data_ptr(), value.stride(1), mask_ptr, B, S, 8, 32, out.data_ptr(),
+    st = _lib.load().rdetr_value_to_head_major_bf16(value.data_ptr(), value.stride(1), None if mask is None else mask.data_ptr(), B, S, 8, 32, out.data_ptr(),
                                                     _stream_ptr(value))
     _lib.check(st, "rdetr_value_to_head_major_bf16")
     return out
@@ -271,6 +276,57 @@ def _producer_row_stride(t: torch.Tensor):
     return ld
 
 
+def _producer_operand(t: torch.Tensor):
+    """(tensor, ld) to hand to a kernel: `t` with its row stride where `_producer_row_stride` has one, else a contiguous copy."""
+    ld = _producer_row_stride(t)
+    return (t.contiguous(), 0) if ld is None else (t, ld)
+
+
+def _check_fused_operands(dims, dtype, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points,
+                          forward: bool = False):
+    """The raw producer operands of the fused MSDA entries against value's (B, S, H, D) and dtype: sampling_offsets
+    [B,Nq,H,L,P,2] and attn_logits [B,Nq,H,L*P] in `dtype`, reference_points [B,Nq,L,2|4] fp32, an L-level table that fits S.
+    -> (Nq, L, P, ref_dim).  ``forward``: the forward takes logits of any shape with the right element count, and answers a bad
+    reference shape with the reference module's ValueError (ms_deform_attn.py:340)."""
+    B, S, H, D = dims
+    if sampling_offsets.dim() != 6 or reference_points.dim() != 4:
+        raise _lib.RdetrError("expected value [B,S,H,D], sampling_offsets [B,Nq,H,L,P,2], reference_points [B,Nq,L,2|4]")
+    _, Nq, H2, L, P, two = sampling_offsets.shape
+    ref_dim = reference_points.shape[-1]
+    logits_ok = attn_logits.numel() == B * Nq * H * L * P if forward else tuple(attn_logits.shape) == (B, Nq, H, L * P)
+    if (H2, two) != (H, 2) or sampling_offsets.shape[0] != B or not logits_ok:
+        raise _lib.RdetrError("sampling_offsets / attn_logits shapes do not match value")
+    if tuple(reference_points.shape[:3]) != (B, Nq, L) or ref_dim not in (2, 4):
+        if forward:
+            raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead.".format(ref_dim))
+        raise _lib.RdetrError("reference_points must be [B, Nq, L, 2|4]")
+    if sampling_offsets.dtype != dtype or attn_logits.dtype != dtype or reference_points.dtype != torch.float32:
+        raise _lib.RdetrError("sampling_offsets / attn_logits must have value's dtype, reference_points float32")
+    if spatial_shapes.shape[0] != L:
+        raise _lib.RdetrError("spatial_shapes has a different number of levels than sampling_offsets")
+    check_levels(spatial_shapes, level_start_index, S)
+    return Nq, L, P, ref_dim
+
+
+def _msda_backward_buffers(name: str, value: torch.Tensor, dims, L: int, Nq: int, P: int, deterministic: Optional[bool],
+                           ref_dim: Optional[int] = None):
+    """-> (workspace | None, its size, grad_value fp32 in value's shape, per-head reference-point partial [B,Nq,H,L,ref_dim] | None).
+    ``deterministic`` (None: ``torch.are_deterministic_algorithms_enabled()``) gets the sort workspace and an uninitialised
+    grad_value, of which that mode writes every row; the atomic mode adds into zeros.  Nothing runs when B * Nq == 0: zeros."""
+    B, S, H, D = dims
+    if deterministic is None:
+        deterministic = torch.are_deterministic_algorithms_enabled()
+    ws, nbytes = None, 0
+    if deterministic and B * Nq > 0:
+        nbytes = int(_lib.load().rdetr_msda_backward_det_workspace_bytes(B, S, H, D, L, Nq, P))
+        if nbytes <= 0:
+            raise _lib.RdetrError(f"deterministic {name}: H = 8, D = 32, P = 4, L <= 8 and fewer than 2^31 sample corners only")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
+    grad_value = (torch.zeros if ws is None else torch.empty)(value.shape, dtype=torch.float32, device=value.device)
+    grad_ref = None if ref_dim is None else torch.empty(B, Nq, H, L, ref_dim, dtype=torch.float32, device=value.device)
+    return ws, nbytes, grad_value, grad_ref
+
+
 def ms_deform_attn_forward_fused(value: torch.Tensor, spatial_shapes: torch.Tensor, level_start_index: torch.Tensor,
                                  sampling_offsets: torch.Tensor, attn_logits: torch.Tensor,
                                  reference_points: torch.Tensor, key_padding_mask: Optional[torch.Tensor] = None,
@@ -283,12 +339,8 @@ def ms_deform_attn_forward_fused(value: torch.Tensor, spatial_shapes: torch.Tens
     Same result as softmax + sampling-location arithmetic + ms_deform_attn_forward (ms_deform_attn.py:322-370)."""
     _require_device(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, key_padding_mask)
     # the two projection outputs may be column slices of one wider GEMM output (rows evenly strided, each row contiguous)
-    ld_off = _producer_row_stride(sampling_offsets)
-    ld_lg = _producer_row_stride(attn_logits)
-    if ld_off is None:
-        sampling_offsets, ld_off = sampling_offsets.contiguous(), 0
-    if ld_lg is None:
-        attn_logits, ld_lg = attn_logits.contiguous(), 0
+    sampling_offsets, ld_off = _producer_operand(sampling_offsets)
+    attn_logits, ld_lg = _producer_operand(attn_logits)
     # a [B,S,H,D] bf16 value may be row-strided: the 256-column slice of a wider projection output (pixel stride in elements)
     value_ld = 0
     if (value.dim() == 4 and not value.is_contiguous() and value_layout == "bshd" and value.dtype == torch.bfloat16
@@ -299,34 +351,18 @@ def ms_deform_attn_forward_fused(value: torch.Tensor, spatial_shapes: torch.Tens
     else:
         _require_contiguous(value=value)
     _require_contiguous(spatial_shapes=spatial_shapes, level_start_index=level_start_index, reference_points=reference_points)
-    if value.dim() != 4 or sampling_offsets.dim() != 6 or reference_points.dim() != 4:
-        raise _lib.RdetrError("expected value [B,S,H,D], sampling_offsets [B,Nq,H,L,P,2], reference_points [B,Nq,L,2|4]")
     B, S, H, D = _value_dims(value, value_layout)
-    _, Nq, H2, L, P, two = sampling_offsets.shape
-    ref_dim = reference_points.shape[-1]
-    if (H2, two) != (H, 2) or sampling_offsets.shape[0] != B or attn_logits.numel() != B * Nq * H * L * P:
-        raise _lib.RdetrError("sampling_offsets / attn_logits shapes do not match value")
-    if tuple(reference_points.shape[:3]) != (B, Nq, L) or ref_dim not in (2, 4):
-        raise ValueError("Last dim of reference_points must be 2 or 4, but get {} instead.".format(ref_dim))
-    if sampling_offsets.dtype != value.dtype or attn_logits.dtype != value.dtype or reference_points.dtype != torch.float32:
-        raise _lib.RdetrError("sampling_offsets / attn_logits must have value's dtype, reference_points float32")
-    if spatial_shapes.shape[0] != L:
-        raise _lib.RdetrError("spatial_shapes has a different number of levels than sampling_offsets")
+    Nq, L, P, ref_dim = _check_fused_operands((B, S, H, D), value.dtype, spatial_shapes, level_start_index, sampling_offsets,
+                                              attn_logits, reference_points, forward=True)
     if algo not in ("auto", "direct", "window", "resident"):
         raise ValueError("algo must be 'auto', 'direct', 'window' or 'resident'")
     if value.dtype not in (torch.float32, torch.bfloat16):
         raise _lib.RdetrError(f"value dtype {value.dtype} not supported (float32 or bfloat16)")
     if value.dtype == torch.float32 and (value_layout != "bshd" or algo not in ("auto", "direct")):    # fp32: the direct kernel only
         raise _lib.RdetrError("value_layout / algo options exist for bfloat16 value only")
-    check_levels(spatial_shapes, level_start_index, S)
     lib = _lib.load()
-    mask_ptr = None
-    if key_padding_mask is not None:
-        if tuple(key_padding_mask.shape) != (B, S):
-            raise _lib.RdetrError("key_padding_mask must be [B, S]")
-        mask_u8 = key_padding_mask.contiguous().view(torch.uint8) if key_padding_mask.dtype == torch.bool \
-            else key_padding_mask.to(torch.uint8).contiguous()
-        mask_ptr = mask_u8.data_ptr()
+    mask = _mask_u8(key_padding_mask, B, S)
+    mask_ptr = None if mask is None else mask.data_ptr()
     out = torch.empty(B, Nq, H * D, dtype=value.dtype, device=value.device)
     if (value.dtype == torch.bfloat16 and value_layout == "bhsd" and mask_ptr is None and not value_ld
             and (algo == "resident" or (algo == "auto" and _resident_pays(B, Nq, L, host_levels(spatial_shapes, level_start_index)[0])))):
@@ -389,26 +425,16 @@ def ms_deform_attn_backward(value: torch.Tensor, spatial_shapes: torch.Tensor, l
     if tuple(grad_output.shape) != (B, Nq, H * D):
         raise _lib.RdetrError("grad_output must be [B, Nq, H*D]")
     check_levels(spatial_shapes, level_start_index, S)
-    if deterministic is None:
-        deterministic = torch.are_deterministic_algorithms_enabled()
-    if deterministic:
-        lib = _lib.load()
-        nbytes = int(lib.rdetr_msda_backward_det_workspace_bytes(B, S, H, D, L, Nq, P))
-        if nbytes < 0 or (nbytes == 0 and B * S * Nq > 0):
-            raise _lib.RdetrError("deterministic ms_deform_attn_backward: H = 8, D = 32, P = 4, L <= 8 and fewer than 2^31 sample corners only")
-        ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=value.device)
-        grad_value = torch.empty_like(value)                    # every row is written
-        grad_loc = torch.empty_like(sampling_loc)
-        grad_attn = torch.empty_like(attn_weight)
-        st = lib.rdetr_msda_backward_det_f32(
+    ws, nbytes, grad_value, _ = _msda_backward_buffers("ms_deform_attn_backward", value, (B, S, H, D), L, Nq, P, deterministic)
+    grad_loc = torch.empty_like(sampling_loc)
+    grad_attn = torch.empty_like(attn_weight)
+    if ws is not None:
+        st = _lib.load().rdetr_msda_backward_det_f32(
             value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(), attn_weight.data_ptr(),
             grad_output.data_ptr(), B, S, H, D, L, Nq, P, ws.data_ptr(), nbytes, grad_value.data_ptr(), grad_loc.data_ptr(),
             grad_attn.data_ptr(), _stream_ptr(value))
         _lib.check(st, "rdetr_msda_backward_det_f32")
         return [grad_value, grad_loc, grad_attn]
-    grad_value = torch.zeros_like(value)                       # accumulated with atomics
-    grad_loc = torch.empty_like(sampling_loc)
-    grad_attn = torch.empty_like(attn_weight)
     st = _lib.load().rdetr_msda_backward_f32(
         value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_loc.data_ptr(),
         attn_weight.data_ptr(), grad_output.data_ptr(), B, S, H, D, L, Nq, P, grad_value.data_ptr(),
@@ -450,43 +476,21 @@ def ms_deform_attn_backward_fused(value: torch.Tensor, spatial_shapes: torch.Ten
     _require_device(value, spatial_shapes, level_start_index, sampling_offsets, attn_logits, reference_points, grad_output)
     if value.dtype not in (torch.float32, torch.bfloat16):
         raise _lib.RdetrError(f"value dtype {value.dtype} not supported (float32 or bfloat16)")
-    if value.dim() != 4 or sampling_offsets.dim() != 6 or reference_points.dim() != 4:
-        raise _lib.RdetrError("expected value [B,S,H,D], sampling_offsets [B,Nq,H,L,P,2], reference_points [B,Nq,L,2|4]")
-    B, S, H, D = value.shape
-    _, Nq, H2, L, P, two = sampling_offsets.shape
-    ref_dim = reference_points.shape[-1]
-    if (H2, two) != (H, 2) or sampling_offsets.shape[0] != B or tuple(attn_logits.shape) != (B, Nq, H, L * P):
-        raise _lib.RdetrError("sampling_offsets / attn_logits shapes do not match value")
-    if tuple(reference_points.shape[:3]) != (B, Nq, L) or ref_dim not in (2, 4):
-        raise _lib.RdetrError("reference_points must be [B, Nq, L, 2|4]")
-    if tuple(grad_output.shape) != (B, Nq, H * D):
-        raise _lib.RdetrError("grad_output must be [B, Nq, H*D]")
-    if (sampling_offsets.dtype != value.dtype or attn_logits.dtype != value.dtype or grad_output.dtype != value.dtype
-            or reference_points.dtype != torch.float32):
-        raise _lib.RdetrError("sampling_offsets / attn_logits / grad_output must have value's dtype, reference_points float32")
-    if spatial_shapes.shape[0] != L:
-        raise _lib.RdetrError("spatial_shapes has a different number of levels than sampling_offsets")
+    B, S, H, D = dims = _value_dims(value, "bshd")
+    Nq, L, P, ref_dim = _check_fused_operands(dims, value.dtype, spatial_shapes, level_start_index, sampling_offsets, attn_logits,
+                                              reference_points)
+    if tuple(grad_output.shape) != (B, Nq, H * D) or grad_output.dtype != value.dtype:
+        raise _lib.RdetrError("grad_output must be [B, Nq, H*D] in value's dtype")
     if not msda_fast_path(H, D, L, P):
         raise _lib.RdetrError("ms_deform_attn_backward_fused: H = 8, D = 32, P = 4, L <= 8 only")
     grad_output = grad_output.contiguous()
     _require_contiguous(value=value, spatial_shapes=spatial_shapes, level_start_index=level_start_index,
                         sampling_offsets=sampling_offsets, attn_logits=attn_logits, reference_points=reference_points)
-    check_levels(spatial_shapes, level_start_index, S)
-    if deterministic is None:
-        deterministic = torch.are_deterministic_algorithms_enabled()
-    lib = _lib.load()
-    ws, nbytes = None, 0
-    if deterministic and B * Nq > 0:
-        nbytes = int(lib.rdetr_msda_backward_det_workspace_bytes(B, S, H, D, L, Nq, P))
-        if nbytes <= 0:
-            raise _lib.RdetrError("deterministic ms_deform_attn_backward_fused: fewer than 2^31 sample corners only")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=value.device)
-    # atomic mode adds into grad_value; the deterministic mode writes every row (nothing runs when B * Nq == 0)
-    grad_value = torch.empty(value.shape, dtype=torch.float32, device=value.device) if ws is not None else \
-        torch.zeros(value.shape, dtype=torch.float32, device=value.device)
+    ws, nbytes, grad_value, grad_ref = _msda_backward_buffers("ms_deform_attn_backward_fused", value, dims, L, Nq, P, deterministic,
+                                                              ref_dim if need_ref_grad else None)
     grad_off = torch.empty_like(sampling_offsets)
     grad_lg = torch.empty_like(attn_logits)
-    grad_ref = torch.empty(B, Nq, H, L, ref_dim, dtype=torch.float32, device=value.device) if need_ref_grad else None
+    lib = _lib.load()
     fn = lib.rdetr_msda_backward_fused_bf16 if value.dtype == torch.bfloat16 else lib.rdetr_msda_backward_fused_f32
     st = fn(value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(), sampling_offsets.data_ptr(),
             attn_logits.data_ptr(), reference_points.data_ptr(), ref_dim, grad_output.data_ptr(), B, S, H, D, L, Nq, P,

@@ -626,6 +626,7 @@ KERNEL_ENTRIES: Dict[str, Callable] = {
 HOST_ONLY = frozenset({
     "_cptr", "_stream_ptr", "_require_device", "_require_contiguous", "host_levels", "check_levels", "levels_window_ok",
     "_host_level_arrays", "_msda_algo", "_resident_pays", "_value_dims", "_producer_row_stride", "msda_fast_path",
+    "_mask_u8", "_producer_operand", "_check_fused_operands", "_msda_backward_buffers",
     "relation_bias_backward_supported", "_row_matrix", "_attention_rows", "_attention_operands", "_attention_grad_buffers", "_rows_view",
     "box_head_k256_supported", "query_pos_k256_supported", "encoder_proj_supported", "topk_supported", "linear_k256_supported",
     "ffn_k256_supported", "linear_ln_k256_supported",

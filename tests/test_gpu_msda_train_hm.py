@@ -14,14 +14,17 @@ import pytest
 import torch
 
 from helpers import kink_mask, pyramid
-from test_gpu_msda_train_fused import DEV, NAN_AT, SHAPES4, SHAPES5, _n, close_bf16, oracle, producer_inputs, ref_mask
+from test_gpu_msda_train_fused import (DEV, NAN_AT, SHAPES1, SHAPES4, SHAPES5, SHAPES8, _n, close_bf16, kept_enough, oracle, producer_inputs,
+                                       ref_mask)
 
 pytestmark = pytest.mark.gpu
 
 BF = torch.bfloat16
 SHAPES3 = [(9, 13), (5, 7), (3, 4)]
-# one block of the backward serves 8 queries: Nq = 5 is below that, Nq = 37 no multiple of it
-CASES = [(SHAPES4, 37, 2), (SHAPES4, 5, 2), (SHAPES5, 37, 2), (SHAPES5, 5, 4), (SHAPES3, 37, 2)]
+# one block of the backward serves 8 queries: Nq = 5 is below that, Nq = 37 no multiple of it, Nq = 11 one full block and a tail
+# whose last wave holds a single valid query
+CASES = [(SHAPES4, 37, 2), (SHAPES4, 5, 2), (SHAPES5, 37, 2), (SHAPES5, 5, 4), (SHAPES3, 37, 2),
+         (SHAPES8, 11, 2), (SHAPES8, 11, 4), (SHAPES1, 11, 2), (SHAPES1, 11, 4)]
 Q_LAST, Q_FIRST = 1, 2                 # queries (image 1) whose corners are pixel S-1 / pixel 0
 RESIDENT_SHAPES = [(100, 134), (50, 67), (25, 34), (13, 17)]      # S = 17,821 >= 16,384: "auto" takes the resident kernel
 MODULE_SHAPES = [(56, 76), (28, 38), (14, 19), (7, 10)]           # S = 5,656: the smallest such pyramid past the 4,096 gate
@@ -131,6 +134,7 @@ def test_head_major_backward_matches_oracle(hm, idx, deterministic):
     assert gv.shape == c["vh"].shape
     _, rv, ro, rl, rr, loc = c["oracle"]
     gv_bshd = gv.permute(0, 2, 1, 3)
+    kept_enough(CASES[idx][0], loc, shp)
     close_bf16(gv_bshd, rv, "grad_value")
     close_bf16(glg, rl, "grad_logits")
     close_bf16(goff, ro, "grad_offsets", kink_mask(_n(loc), shp.numpy()))

@@ -164,7 +164,9 @@ def test_msda_autograd_vs_oracle(rd):
 
 
 @pytest.mark.parametrize("shapes,B,Nq", [([(12, 20), (6, 10), (3, 5), (2, 3)], 2, 37), ([(40, 56), (20, 28), (10, 14), (5, 7)], 2, 3010),
-                                         ([(10, 16), (5, 8), (3, 4), (2, 2), (1, 1)], 1, 29)])
+                                         ([(10, 16), (5, 8), (3, 4), (2, 2), (1, 1)], 1, 29),
+                                         # 8 levels: L*P = 32, every lane stages a point; 1 level; Nq = 11: a full block + a one-query wave
+                                         ([(6, 7), (5, 5), (4, 5), (3, 4), (3, 3), (2, 3), (2, 2), (1, 2)], 2, 11), ([(5, 6)], 2, 11)])
 def test_msda_backward_deterministic_mode(rd, shapes, B, Nq):
     """rdetr_msda_backward_det_f32: grad_value through sorted per-row sums instead of float atomics.  Same
     gradients as the C oracle (double accumulation) within the bounds of the atomic kernel, the SAME BITS on a second run, every
