@@ -537,6 +537,16 @@ int rdetr_box_head_k256_bf16(const uint16_t *xa, long long lda, const uint16_t *
                              const float *reference, int reference_is_logit, float eps, long long M, float *out_a, float *out_b,
                              void *stream);
 
+/* rdetr_box_head_k256_bf16 plus the layer's class head on input A (class_head[i] = nn.Linear(256, C), relation_transformer.py:358)
+ * in the same launch:  out_cls [M, C] = xa Wc^T + bc, bf16, row stride ldc elements (>= C; rows need no alignment beyond 2 bytes).
+ *   pwc  class_head[i].weight [C, 256] zero-padded to [256, 256] and packed by rdetr_linear_pack_k256_bf16;  bc [C] bf16
+ *   1 <= C <= 256 (anything larger is RDETR_ERR_UNSUPPORTED).  Same products and fp32 accumulation as the GEMM it replaces,
+ *   rounded to bf16 once; out_a / out_b are bit for bit what rdetr_box_head_k256_bf16 writes. */
+int rdetr_box_head_cls_k256_bf16(const uint16_t *xa, long long lda, const uint16_t *xb, long long ldb, const uint16_t *pw1,
+                                 const uint16_t *b1, const uint16_t *pw2, const uint16_t *b2, const uint16_t *w3, const uint16_t *b3,
+                                 const float *reference, int reference_is_logit, float eps, const uint16_t *pwc, const uint16_t *bc,
+                                 int C, long long M, float *out_a, float *out_b, uint16_t *out_cls, long long ldc, void *stream);
+
 /* The decoder layer's query position in one launch (models/bricks/relation_transformer.py:294-296, 343-347, 452-455):
  *     out_pos = ref_point_head(emb)                      MLP(512, 256, 256, 2) on the sine embedding of the reference boxes
  *     out_pos = out_pos * query_scale(query)             MLP(256, 256, 256, 2), layers >= 1 -- when pv1 / c1 / pv2 / c2 are given
@@ -550,6 +560,19 @@ int rdetr_query_pos_k256_bf16(const uint16_t *emb, long long lde, const uint16_t
                               const uint16_t *pw1b, const uint16_t *b1, const uint16_t *pw2, const uint16_t *b2, const uint16_t *pv1,
                               const uint16_t *c1, const uint16_t *pv2, const uint16_t *c2, long long M, uint16_t *out_pos,
                               uint16_t *out_qpp, void *stream);
+
+/* rdetr_query_pos_k256_bf16 plus the in-projection of the layer's self-attention (nn.MultiheadAttention's in_proj_weight [768, 256],
+ * in_proj_bias [768]; relation_transformer.py:452-455 calls it with q = k = query + query_pos, value = query) in the same launch:
+ *     out_qk [M, 512] = out_qpp [Wq ; Wk]^T + bias[:512]          computed from out_qpp as stored (bf16)
+ *     out_v  [M, 256] = query Wv^T + bias[512:]
+ * pwq / pwk / pwv = in_proj_weight[:256] / [256:512] / [512:], each packed by rdetr_linear_pack_k256_bf16; bias bf16 [768]; outputs
+ * bf16 with row strides ldqk >= 512 / ldv >= 256 elements (multiples of 8, 16-byte aligned bases).  out_pos / out_qpp are bit for bit
+ * what rdetr_query_pos_k256_bf16 writes. */
+int rdetr_query_pos_inproj_k256_bf16(const uint16_t *emb, long long lde, const uint16_t *query, long long ldq, const uint16_t *pw1a,
+                                     const uint16_t *pw1b, const uint16_t *b1, const uint16_t *pw2, const uint16_t *b2, const uint16_t *pv1,
+                                     const uint16_t *c1, const uint16_t *pv2, const uint16_t *c2, const uint16_t *pwq, const uint16_t *pwk,
+                                     const uint16_t *pwv, const uint16_t *bias, long long M, uint16_t *out_pos, uint16_t *out_qpp,
+                                     uint16_t *out_qk, long long ldqk, uint16_t *out_v, long long ldv, void *stream);
 
 /* The three input projections of an ENCODER layer's MultiScaleDeformableAttention in one launch
  * (models/bricks/ms_deform_attn.py:315-327; called from relation_transformer.py:262-269 with value = query, query = query + pos):

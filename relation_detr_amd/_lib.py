@@ -64,7 +64,10 @@ SIGNATURES = {
     "rdetr_topk_workspace_bytes": [_c_int, _c_int, _c_int],
     "rdetr_topk": [_vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp, _vp, _vp],
     "rdetr_box_head_k256_bf16": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_float, _c_ll, _vp, _vp, _vp],
+    "rdetr_box_head_cls_k256_bf16": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_int, _c_float, _vp, _vp, _c_int, _c_ll,
+                                     _vp, _vp, _vp, _c_ll, _vp],
     "rdetr_query_pos_k256_bf16": [_vp, _c_ll, _vp, _c_ll] + [_vp] * 9 + [_c_ll, _vp, _vp, _vp],
+    "rdetr_query_pos_inproj_k256_bf16": [_vp, _c_ll, _vp, _c_ll] + [_vp] * 13 + [_c_ll, _vp, _vp, _vp, _c_ll, _vp, _c_ll, _vp],
     "rdetr_encoder_proj_k256_bf16": [_vp, _c_ll, _vp, _c_ll] + [_vp] * 5 + [_c_int, _c_int, _c_int, _vp, _vp, _vp],
     "rdetr_detections_from_topk": [_vp, _vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _vp, _vp],
     "rdetr_scaled_pos": [_vp, _vp, _vp, _c_ll, _c_int, _vp, _vp, _vp],

@@ -19,6 +19,14 @@
 //              lane's B operand of the next layer's k-step u.  Both MLPs' first layers run first (they are independent), each
 //              wave writes its pairs to an LDS image [u][lane] (1-KiB rows, conflict-free), ONE __syncthreads(), every wave reads
 //              all 8 k-steps of both images.  Each image is written once per launch, so nothing can be overwritten under a reader.
+//   in-proj    (query_pos_inproj_k256_kernel, rdetr_query_pos_inproj_k256_bf16) the layer's self-attention projects exactly this
+//              kernel's outputs: q | k = (query + query_pos) [Wq ; Wk]^T + b, v = query Wv^T + b (relation_transformer.py:452-455),
+//              two library GEMMs of the decoder's chain.  Three more packed blocks in the same two register sets: Wv is fetched
+//              into the set the last ref_point_head block leaves, Wq into the one the last block before the sum leaves; every wave
+//              writes its columns of query + query_pos (bf16, as stored) to a third image, runs the v block on the `query`
+//              fragments it already holds while the others arrive (Wk fetched under it), ONE more __syncthreads(), then the q and
+//              k blocks on the image; bias, one rounding to bf16, one 16-byte store per lane and pair.  out_pos / out_qpp are bit
+//              for bit the plain kernel's.
 //   arithmetic every output accumulates the same v_mfma_f32_16x16x32_bf16 products in the same k-step order as the row-split
 //              kernel this replaces (s = 0 .. 7; K = 512 as half a then half b into one accumulator) with the same rounding
 //              points (hidden activations, query_pos, the scale, their product, the sum): results are bit-identical to it, and
@@ -31,8 +39,15 @@
 //              12.1 / 12.4 / 12.9 (layer 0, no scale branch: 8.5 / 8.7 / 9.1); the row-split kernel in the same call 21.6 / 21.7 /
 //              22.0 (14.6 / 14.8 / 15.0); the unfused sequence 20.8 / 22.7 / 29.1.  In the step (bench.py, both image groups'
 //              launches side by side) together with csrc/mlp.hip: 3.90-3.95 -> 3.76-3.79 ms (ab_stack_chain_kernels.txt).
+//              With the in-projection (profiles/r12/time_absorbed_kernels.txt, alternating, 5 runs each) rows 600 / 1,800 / 3,600:
+//              16.0 / 16.6 / 17.3 (layer 0: 13.7 / 14.3 / 15.2) against this kernel followed by the two library GEMMs it absorbs
+//              21.3 / 22.2 / 24.6 (17.7 / 18.5 / 21.0): about 1.4 us per extra block, 5.6 us less per layer at 1,800 rows.  In the step
+//              (profiles/r12/decoder_chain_by_kernel.txt, ab_stack.txt) 18.2 us against 13.7 + 7.0 + 6.2, 15 launches per decoder
+//              layer and image group instead of 18, and together with csrc/mlp.hip 3.725 -> 3.610 ms.
 //   resources  (hipcc -Rpass-analysis=kernel-resource-usage) scaled / layer 0: 242 / 204 VGPRs, no AGPRs, no scratch, no spills,
-//              16 / 8 KiB LDS, 2 waves per SIMD = one 8-wave workgroup per CU.
+//              16 / 8 KiB LDS, 2 waves per SIMD = one 8-wave workgroup per CU.  With the in-projection: 250 / 252 VGPRs, no AGPRs,
+//              no scratch, 24 / 16 KiB LDS, 2 waves per SIMD (layer 0 loads `query` only after emb's registers are free: loaded
+//              at the top it cost 116 bytes of scratch per lane).
 //   dropped    4 waves x 2 tile pairs (kQpWaves = 4): both 32-fragment sets no longer fit 256 VGPRs, hipcc parks 80-168 of them in
 //              AGPRs (v_accvgpr traffic, 1 wave per SIMD): 13.2 / 13.4 / 14.1 us and 0.5-1 % less in the step
 //              (ab_candidates.txt).  32 rows per workgroup (two N blocks sharing each A fragment) was not built: the second block's
@@ -53,14 +68,22 @@ constexpr int kQpFrags = kQpPairs * 16;                                       //
 constexpr int kQpImg = 8 * 64;                                                // one exchange image in u32x4: [u][lane], 8 KiB
 static_assert(kQpWaves == 4 || kQpWaves == 8, "the 8 tile pairs are dealt over 4 or 8 waves");
 
-template <bool kScaled>
-__global__ __launch_bounds__(kQpThreads) void query_pos_k256_kernel(
+// the self-attention in-projection a layer runs on the kernel's outputs (rdetr_query_pos_inproj_k256_bf16)
+struct QpInProj {
+    const uint16_t *pwq, *pwk, *pwv, *bias;                                   // three packed [256, 256] blocks; bias [768] = q | k | v
+    uint16_t *qk, *v;                                                         // [M, 512] = q | k and [M, 256]
+    long long ldqk, ldv;
+};
+
+template <bool kScaled, bool kInProj>
+__device__ __forceinline__ void query_pos_k256_body(
     const uint16_t *__restrict__ emb, long long lde, const uint16_t *__restrict__ query, long long ldq,
     const uint16_t *__restrict__ pw1a, const uint16_t *__restrict__ pw1b, const uint16_t *__restrict__ b1, const uint16_t *__restrict__ pw2,
     const uint16_t *__restrict__ b2, const uint16_t *__restrict__ pv1, const uint16_t *__restrict__ c1, const uint16_t *__restrict__ pv2,
-    const uint16_t *__restrict__ c2, long long M, uint16_t *__restrict__ out_pos, uint16_t *__restrict__ out_qpp)
+    const uint16_t *__restrict__ c2, long long M, uint16_t *__restrict__ out_pos, uint16_t *__restrict__ out_qpp, const QpInProj &ip)
 {
-    __shared__ __attribute__((aligned(16))) u32x4 img[(kScaled ? 2 : 1) * kQpImg];
+    __shared__ __attribute__((aligned(16))) u32x4 img[((kScaled ? 2 : 1) + (kInProj ? 1 : 0)) * kQpImg];
+    u32x4 *const img_qpp = img + (kScaled ? 2 : 1) * kQpImg;                  // kInProj: the third exchange image, query + query_pos
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int col = lane & 15, g = lane >> 4;
     const int u0 = kQpPairs * wave;                                           // this wave's first tile pair (uniform)
@@ -159,6 +182,10 @@ __global__ __launch_bounds__(kQpThreads) void query_pos_k256_kernel(
         finish(acc, cc1, true, y);
 #pragma unroll
         for (int uu = 0; uu < kQpPairs; ++uu) img[kQpImg + (u0 + uu) * 64 + lane] = y[uu];
+    } else if (kInProj) {                                                     // layer 0 reads `query` only now, in the registers emb has left
+        fetch(ip.pwv, wb);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) xq[s] = *reinterpret_cast<const u32x4 *>(query + lrow * ldq + 32 * s + 8 * g);
     }
     __syncthreads();                                                          // the one hand-over: every wave's columns of both hidden layers
     // ---- second layers -------------------------------------------------------------------------------------------------------
@@ -166,6 +193,7 @@ __global__ __launch_bounds__(kQpThreads) void query_pos_k256_kernel(
     for (int s = 0; s < 8; ++s) h[s] = img[s * 64 + lane];
     zero(acc);
     block(kScaled ? wb : wa, h, acc);
+    if (kInProj) fetch(kScaled ? ip.pwv : ip.pwq, kScaled ? wb : wa);         // in-projection: Wv into wb, Wq into wa, as each is freed
     finish(acc, bb2, false, pos);
     if (kScaled) {
         u32x4 sc[kQpPairs];
@@ -173,6 +201,7 @@ __global__ __launch_bounds__(kQpThreads) void query_pos_k256_kernel(
         for (int s = 0; s < 8; ++s) h[s] = img[kQpImg + s * 64 + lane];
         zero(acc);
         block(wa, h, acc);
+        if (kInProj) fetch(ip.pwq, wa);
         finish(acc, cc2, false, sc);
         // query_pos * scale, rounded to bf16 as torch's bf16 multiply (fp32 product of the two bf16 values, one rounding)
 #pragma unroll
@@ -186,20 +215,88 @@ __global__ __launch_bounds__(kQpThreads) void query_pos_k256_kernel(
             pos[uu] = u32x4{o[0], o[1], o[2], o[3]};
         }
     }
+    // query + query_pos of pair uu, rounded to bf16 as torch's bf16 add
+    auto sum_of = [&](int uu) {
+        const unsigned a[4] = {pos[uu].x, pos[uu].y, pos[uu].z, pos[uu].w}, q[4] = {qown[uu].x, qown[uu].y, qown[uu].z, qown[uu].w};
+        unsigned o[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            o[k] = pack_bf16x2(bf16_bits_to_f32(q[k] & 0xffffu) + bf16_bits_to_f32(a[k] & 0xffffu),
+                               __builtin_bit_cast(float, q[k] & 0xffff0000u) + __builtin_bit_cast(float, a[k] & 0xffff0000u));
+        return u32x4{o[0], o[1], o[2], o[3]};
+    };
+    if (!kInProj) {
+        if (rok) {
+#pragma unroll
+            for (int uu = 0; uu < kQpPairs; ++uu) {
+                const int u = u0 + uu;
+                *reinterpret_cast<u32x4 *>(out_pos + row * 256 + 32 * u + 8 * g) = pos[uu];
+                *reinterpret_cast<u32x4 *>(out_qpp + row * 256 + 32 * u + 8 * g) = sum_of(uu);
+            }
+        }
+        return;
+    }
+    u32x4 qpp[kQpPairs];                                                      // every lane's, rows >= M included: it is the next B operand
+#pragma unroll
+    for (int uu = 0; uu < kQpPairs; ++uu) qpp[uu] = sum_of(uu);
     if (rok) {
 #pragma unroll
         for (int uu = 0; uu < kQpPairs; ++uu) {
-            const int u = u0 + uu;
-            *reinterpret_cast<u32x4 *>(out_pos + row * 256 + 32 * u + 8 * g) = pos[uu];
-            const unsigned a[4] = {pos[uu].x, pos[uu].y, pos[uu].z, pos[uu].w}, q[4] = {qown[uu].x, qown[uu].y, qown[uu].z, qown[uu].w};
-            unsigned o[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                o[k] = pack_bf16x2(bf16_bits_to_f32(q[k] & 0xffffu) + bf16_bits_to_f32(a[k] & 0xffffu),
-                                   __builtin_bit_cast(float, q[k] & 0xffff0000u) + __builtin_bit_cast(float, a[k] & 0xffff0000u));
-            *reinterpret_cast<u32x4 *>(out_qpp + row * 256 + 32 * u + 8 * g) = u32x4{o[0], o[1], o[2], o[3]};
+            *reinterpret_cast<u32x4 *>(out_pos + row * 256 + 32 * (u0 + uu) + 8 * g) = pos[uu];
+            *reinterpret_cast<u32x4 *>(out_qpp + row * 256 + 32 * (u0 + uu) + 8 * g) = qpp[uu];
         }
     }
+    // ---- the layer's self-attention in-projection (relation_transformer.py:452-455 -> nn.MultiheadAttention): q | k = Wq | Wk
+    //      (query + query_pos) + b, v = Wv query + b.  v needs nothing of this kernel's, so its block runs while the other waves'
+    //      columns of query + query_pos arrive in the third image; Wk is fetched under it ---------------------------------------
+#pragma unroll
+    for (int uu = 0; uu < kQpPairs; ++uu) img_qpp[(u0 + uu) * 64 + lane] = qpp[uu];
+    u32x4 bq[kQpPairs], bk[kQpPairs], bv[kQpPairs];
+    bias_of(ip.bias, bq);
+    bias_of(ip.bias + 256, bk);
+    bias_of(ip.bias + 512, bv);
+    auto store = [&](uint16_t *out, long long ld, const u32x4 (&val)[kQpPairs]) {
+        if (rok) {
+#pragma unroll
+            for (int uu = 0; uu < kQpPairs; ++uu) *reinterpret_cast<u32x4 *>(out + row * ld + 32 * (u0 + uu) + 8 * g) = val[uu];
+        }
+    };
+    zero(acc);
+    block(wb, xq, acc);
+    fetch(ip.pwk, wb);
+    finish(acc, bv, false, y);
+    store(ip.v, ip.ldv, y);
+    __syncthreads();                                                          // every wave's columns of query + query_pos
+#pragma unroll
+    for (int s = 0; s < 8; ++s) h[s] = img_qpp[s * 64 + lane];
+    zero(acc);
+    block(wa, h, acc);
+    finish(acc, bq, false, y);
+    store(ip.qk, ip.ldqk, y);
+    zero(acc);
+    block(wb, h, acc);
+    finish(acc, bk, false, y);
+    store(ip.qk + 256, ip.ldqk, y);
+}
+
+template <bool kScaled>
+__global__ __launch_bounds__(kQpThreads) void query_pos_k256_kernel(
+    const uint16_t *__restrict__ emb, long long lde, const uint16_t *__restrict__ query, long long ldq,
+    const uint16_t *__restrict__ pw1a, const uint16_t *__restrict__ pw1b, const uint16_t *__restrict__ b1, const uint16_t *__restrict__ pw2,
+    const uint16_t *__restrict__ b2, const uint16_t *__restrict__ pv1, const uint16_t *__restrict__ c1, const uint16_t *__restrict__ pv2,
+    const uint16_t *__restrict__ c2, long long M, uint16_t *__restrict__ out_pos, uint16_t *__restrict__ out_qpp)
+{
+    query_pos_k256_body<kScaled, false>(emb, lde, query, ldq, pw1a, pw1b, b1, pw2, b2, pv1, c1, pv2, c2, M, out_pos, out_qpp, QpInProj{});
+}
+
+template <bool kScaled>
+__global__ __launch_bounds__(kQpThreads) void query_pos_inproj_k256_kernel(
+    const uint16_t *__restrict__ emb, long long lde, const uint16_t *__restrict__ query, long long ldq,
+    const uint16_t *__restrict__ pw1a, const uint16_t *__restrict__ pw1b, const uint16_t *__restrict__ b1, const uint16_t *__restrict__ pw2,
+    const uint16_t *__restrict__ b2, const uint16_t *__restrict__ pv1, const uint16_t *__restrict__ c1, const uint16_t *__restrict__ pv2,
+    const uint16_t *__restrict__ c2, long long M, uint16_t *__restrict__ out_pos, uint16_t *__restrict__ out_qpp, QpInProj ip)
+{
+    query_pos_k256_body<kScaled, true>(emb, lde, query, ldq, pw1a, pw1b, b1, pw2, b2, pv1, c1, pv2, c2, M, out_pos, out_qpp, ip);
 }
 
 }  // namespace
@@ -233,5 +330,39 @@ extern "C" int rdetr_query_pos_k256_bf16(const uint16_t *emb, long long lde, con
     else
         hipLaunchKernelGGL(query_pos_k256_kernel<false>, dim3((unsigned)nblk), dim3(kQpThreads), 0, static_cast<hipStream_t>(stream), emb, lde,
                            query, ldq, pw1a, pw1b, b1, pw2, b2, pv1, c1, pv2, c2, M, out_pos, out_qpp);
+    return launch_status();
+}
+
+// rdetr_query_pos_k256_bf16 plus the in-projection of the layer's self-attention on its outputs, in the same launch:
+//     out_qk [M, 512] = out_qpp [Wq ; Wk]^T + bias[:512],  out_v [M, 256] = query Wv^T + bias[512:]     (bf16, row strides ldqk / ldv)
+// pwq / pwk / pwv: in_proj_weight[:256] / [256:512] / [512:] packed by rdetr_linear_pack_k256_bf16; bias bf16 [768].  out_qk is
+// computed from out_qpp as stored (bf16); out_pos / out_qpp are bit for bit what rdetr_query_pos_k256_bf16 writes.
+extern "C" int rdetr_query_pos_inproj_k256_bf16(const uint16_t *emb, long long lde, const uint16_t *query, long long ldq, const uint16_t *pw1a,
+                                                const uint16_t *pw1b, const uint16_t *b1, const uint16_t *pw2, const uint16_t *b2,
+                                                const uint16_t *pv1, const uint16_t *c1, const uint16_t *pv2, const uint16_t *c2,
+                                                const uint16_t *pwq, const uint16_t *pwk, const uint16_t *pwv, const uint16_t *bias, long long M,
+                                                uint16_t *out_pos, uint16_t *out_qpp, uint16_t *out_qk, long long ldqk, uint16_t *out_v,
+                                                long long ldv, void *stream)
+{
+    if (M < 0 || lde < 512 || ldq < 256 || ldqk < 512 || ldv < 256) return RDETR_ERR_INVALID_ARG;
+    if ((lde & 7) || (ldq & 7) || (ldqk & 7) || (ldv & 7)) return RDETR_ERR_UNSUPPORTED;
+    if (M == 0) return RDETR_OK;
+    if (!emb || !query || !pw1a || !pw1b || !b1 || !pw2 || !b2 || !out_pos || !out_qpp || !pwq || !pwk || !pwv || !bias || !out_qk || !out_v)
+        return RDETR_ERR_INVALID_ARG;
+    const bool any = pv1 || c1 || pv2 || c2, all = pv1 && c1 && pv2 && c2;
+    if (any && !all) return RDETR_ERR_INVALID_ARG;
+    auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    if (!al(emb) || !al(query) || !al(pw1a) || !al(pw1b) || !al(pw2) || (all && (!al(pv1) || !al(pv2))) || !al(out_pos) || !al(out_qpp)
+        || !al(pwq) || !al(pwk) || !al(pwv) || !al(out_qk) || !al(out_v))
+        return RDETR_ERR_UNSUPPORTED;
+    const long long nblk = (M + kQpRows - 1) / kQpRows;
+    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    const QpInProj ip = {pwq, pwk, pwv, bias, out_qk, out_v, ldqk, ldv};
+    if (all)
+        hipLaunchKernelGGL(query_pos_inproj_k256_kernel<true>, dim3((unsigned)nblk), dim3(kQpThreads), 0, static_cast<hipStream_t>(stream),
+                           emb, lde, query, ldq, pw1a, pw1b, b1, pw2, b2, pv1, c1, pv2, c2, M, out_pos, out_qpp, ip);
+    else
+        hipLaunchKernelGGL(query_pos_inproj_k256_kernel<false>, dim3((unsigned)nblk), dim3(kQpThreads), 0, static_cast<hipStream_t>(stream),
+                           emb, lde, query, ldq, pw1a, pw1b, b1, pw2, b2, pv1, c1, pv2, c2, M, out_pos, out_qpp, ip);
     return launch_status();
 }

@@ -976,11 +976,27 @@ def box_head_k256_supported(x: torch.Tensor, layers) -> bool:
 
 
 def box_head_k256(xa: torch.Tensor, xb: Optional[torch.Tensor], layers, reference: torch.Tensor, eps: float = 1e-3,
-                  reference_is_logit: bool = False):
+                  reference_is_logit: bool = False, class_head: Optional[dict] = None):
     """``sigmoid(MLP3(x) + inverse_sigmoid(reference))`` for the decoder's box head (three nn.Linear: 256 -> 256 -> 256 -> 4, ReLU
     between) on one or two bf16 [..., 256] inputs sharing the fp32 reference boxes [..., 4]: one kernel instead of 3 (6) GEMMs
     and 1 (2) refine launches (relation_transformer.py:294, 363-381).  ``reference_is_logit``: the reference is added as it is
-    (the two-stage proposals, :88-90).  Returns fp32 boxes (a pair when ``xb`` is given)."""
+    (the two-stage proposals, :88-90).  Returns fp32 boxes (a pair when ``xb`` is given).
+
+    ``class_head``: ``{"linear": nn.Linear(256, C)}`` (bf16, 1 <= C <= 256, with bias), optionally ``"out"``: a bf16 [..., C]
+    destination with evenly strided rows.  The same launch then also computes ``linear(xa)`` (relation_transformer.py:358); the
+    logits are left in ``class_head["out"]`` (allocated here unless given).  The boxes are the same bits either way."""
+    if class_head is not None:
+        lin = class_head.get("linear")
+        wc, bc = getattr(lin, "weight", None), getattr(lin, "bias", None)
+        if not (torch.is_tensor(wc) and torch.is_tensor(bc) and wc.dim() == 2 and wc.shape[1] == 256 and 1 <= wc.shape[0] <= 256
+                and wc.dtype == torch.bfloat16 and bc.dtype == torch.bfloat16 and tuple(bc.shape) == (wc.shape[0],)
+                and wc.device == xa.device and bc.device == xa.device):
+            raise _lib.RdetrError("box_head_k256: class_head needs a bf16 Linear(256, C) with bias, 1 <= C <= 256, on the inputs' device")
+        C = wc.shape[0]
+        cls = class_head.get("out")
+        if cls is not None and not (torch.is_tensor(cls) and cls.dtype == torch.bfloat16 and cls.device == xa.device
+                  and tuple(cls.shape) == (*xa.shape[:-1], C)):
+            raise _lib.RdetrError("box_head_k256: class_head['out'] must be bf16 [..., C] with the inputs' leading shape and device")
     _require_device(xa, xb, reference)
     if not box_head_k256_supported(xa, layers) or reference.dtype != torch.float32 or reference.shape[-1] != 4:
         raise _lib.RdetrError("box_head_k256: bf16 [..., 256] inputs, Linear(256,256), Linear(256,256), Linear(256,4) in bf16, fp32 reference")
@@ -996,6 +1012,29 @@ def box_head_k256(xa: torch.Tensor, xb: Optional[torch.Tensor], layers, referenc
     pw1, pw2 = _packed_k256(layers[0].weight), _packed_k256(layers[1].weight)
     out_a = torch.empty_like(ref)
     out_b = torch.empty_like(ref) if xb is not None else None
+    if class_head is not None:
+        if cls is None:
+            cls = torch.empty(*xa.shape[:-1], C, dtype=torch.bfloat16, device=xa.device)
+        _, _, ldc = _rows_view(cls, "box_head_k256")
+
+        def build():                                     # [C, 256] zero-padded to [256, 256], in fragment order
+            padded = torch.zeros(256, 256, dtype=torch.bfloat16, device=wc.device)
+            padded[:C].copy_(wc.detach())
+            packed = torch.empty(256 * 256, dtype=torch.bfloat16, device=wc.device)
+            _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(padded.data_ptr(), packed.data_ptr(), _stream_ptr(wc)), "rdetr_linear_pack_k256_bf16")
+            if not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(wc.device).synchronize()
+            return packed
+        pwc = _LINEAR_PACKED.get((wc,), build)
+        bcc = bc.detach().contiguous()
+        st = _lib.load().rdetr_box_head_cls_k256_bf16(
+            xa.data_ptr(), lda, None if xb is None else xb.data_ptr(), ldb, pw1.data_ptr(), _cptr(layers[0].bias),
+            pw2.data_ptr(), _cptr(layers[1].bias), layers[2].weight.data_ptr(), _cptr(layers[2].bias),
+            ref.data_ptr(), int(reference_is_logit), float(eps), pwc.data_ptr(), bcc.data_ptr(), C, rows, out_a.data_ptr(),
+            None if out_b is None else out_b.data_ptr(), cls.data_ptr(), ldc, _stream_ptr(xa))
+        _lib.check(st, "rdetr_box_head_cls_k256_bf16")
+        class_head["out"] = cls
+        return out_a if xb is None else (out_a, out_b)
     st = _lib.load().rdetr_box_head_k256_bf16(
         xa.data_ptr(), lda, None if xb is None else xb.data_ptr(), ldb, pw1.data_ptr(), _cptr(layers[0].bias),
         pw2.data_ptr(), _cptr(layers[1].bias), layers[2].weight.data_ptr(), _cptr(layers[2].bias),
@@ -1031,10 +1070,34 @@ def _packed_k_halves(weight: torch.Tensor):
     return _LINEAR_PACKED.get((weight,), build)
 
 
-def query_pos_k256(emb: torch.Tensor, query: torch.Tensor, head_layers, scale_layers=None):
+def query_pos_k256(emb: torch.Tensor, query: torch.Tensor, head_layers, scale_layers=None, in_proj: Optional[dict] = None):
     """``(query_pos, query + query_pos)`` of a decoder layer in one kernel (csrc/qpos.hip): ``query_pos = ref_point_head(emb)``,
     multiplied by ``query_scale(query)`` when ``scale_layers`` is given (relation_transformer.py:343-347).  emb [..., 512], query
-    [..., 256] bf16; head_layers / scale_layers: the two nn.Linear of each MLP.  Inference only."""
+    [..., 256] bf16; head_layers / scale_layers: the two nn.Linear of each MLP.  Inference only.
+
+    ``in_proj``: ``{"weight": in_proj_weight [768, 256], "bias": in_proj_bias [768]}`` (bf16) of the layer's self-attention,
+    optionally ``"qk"`` / ``"v"``: bf16 [..., 512] / [..., 256] destinations with evenly strided, 16-byte aligned rows.  The same
+    launch then also computes ``qk = (query + query_pos) W[:512]^T + b[:512]`` (from the bf16 sum as returned) and ``v = query
+    W[512:]^T + b[512:]`` (relation_transformer.py:452-455); they are left in ``in_proj["qk"]`` / ``in_proj["v"]`` (allocated here
+    unless given).  The returned pair is the same bits either way."""
+    if in_proj is not None:
+        w, b = in_proj.get("weight"), in_proj.get("bias")
+        if not (torch.is_tensor(w) and torch.is_tensor(b) and tuple(w.shape) == (768, 256) and tuple(b.shape) == (768,)
+                and w.dtype == torch.bfloat16 and b.dtype == torch.bfloat16 and w.device == query.device and b.device == query.device):
+            raise _lib.RdetrError("query_pos_k256: in_proj needs a bf16 weight [768, 256] and bias [768] on the inputs' device")
+        dst = []
+        for key, n in (("qk", 512), ("v", 256)):
+            t = in_proj.get(key)
+            if t is None:
+                dst.append(None)
+                continue
+            if not (torch.is_tensor(t) and t.dtype == torch.bfloat16 and t.device == query.device
+                      and tuple(t.shape) == (*query.shape[:-1], n)):
+                raise _lib.RdetrError(f"query_pos_k256: in_proj['{key}'] must be bf16 [..., {n}] with the inputs' leading shape and device")
+            ld = _rows_view(t, "query_pos_k256")[2]
+            if ld % 8 or t.data_ptr() % 16:
+                raise _lib.RdetrError(f"query_pos_k256: in_proj['{key}'] rows must be 16-byte aligned")
+            dst.append((t, ld))
     _require_device(emb, query)
     if not query_pos_k256_supported(emb, query, head_layers, scale_layers):
         raise _lib.RdetrError("query_pos_k256: bf16 emb [..., 512] / query [..., 256], Linear(512,256), Linear(256,256) (x2) in bf16 with biases")
@@ -1052,6 +1115,28 @@ def query_pos_k256(emb: torch.Tensor, query: torch.Tensor, head_layers, scale_la
               _packed_k256(scale_layers[1].weight).data_ptr(), _cptr(scale_layers[1].bias)]
     pos = torch.empty(*query.shape, dtype=torch.bfloat16, device=query.device)
     qpp = torch.empty_like(pos)
+    if in_proj is not None:
+        def build():                                     # Wq, Wk, Wv: three [256, 256] row blocks, each in fragment order
+            blocks = []
+            for i in range(3):
+                blk = w.detach()[256 * i:256 * (i + 1)].contiguous()
+                packed = torch.empty(256 * 256, dtype=torch.bfloat16, device=w.device)
+                _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(blk.data_ptr(), packed.data_ptr(), _stream_ptr(w)), "rdetr_linear_pack_k256_bf16")
+                blocks.append(packed)
+            if not torch.cuda.is_current_stream_capturing():
+                torch.cuda.current_stream(w.device).synchronize()
+            return tuple(blocks)
+        pq, pk, pv = _LINEAR_PACKED.get((w,), build)
+        bias = b.detach().contiguous()
+        (qk, ldqk), (v, ldv) = (d if d is not None else (torch.empty(*query.shape[:-1], n, dtype=torch.bfloat16, device=query.device), n)
+                                for d, n in zip(dst, (512, 256)))
+        st = _lib.load().rdetr_query_pos_inproj_k256_bf16(
+            emb.data_ptr(), lde, query.data_ptr(), ldq, p1a.data_ptr(), p1b.data_ptr(), _cptr(head_layers[0].bias), p2.data_ptr(),
+            _cptr(head_layers[1].bias), sc[0], sc[1], sc[2], sc[3], pq.data_ptr(), pk.data_ptr(), pv.data_ptr(), bias.data_ptr(), rows,
+            pos.data_ptr(), qpp.data_ptr(), qk.data_ptr(), ldqk, v.data_ptr(), ldv, _stream_ptr(query))
+        _lib.check(st, "rdetr_query_pos_inproj_k256_bf16")
+        in_proj["qk"], in_proj["v"] = qk, v
+        return pos, qpp
     st = _lib.load().rdetr_query_pos_k256_bf16(emb.data_ptr(), lde, query.data_ptr(), ldq, p1a.data_ptr(), p1b.data_ptr(),
                                                _cptr(head_layers[0].bias), p2.data_ptr(),
                                                _cptr(head_layers[1].bias), sc[0], sc[1], sc[2], sc[3], rows,
@@ -1455,7 +1540,11 @@ def ffn_ln_k256(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.T
     return out if pos is None else (out, out2)
 
 
-_LINEAR_PACKED = _PackedWeightCache()     # (weight,) -> fragment-order copy
+# (weight,) -> fragment-order copy.  What the copy is depends on who packed the tensor: one [256, 256] block (_packed_k256), the two
+# K halves of a [256, 512] weight (_packed_k_halves), the three row blocks of an in_proj_weight [768, 256] (query_pos_k256) or a class
+# weight [C, 256] zero-padded to one block (box_head_k256).  The shapes tell the users apart -- each packs only the shape it checks
+# for, and a [256, 256] class weight gives the same single block either way -- so one tensor never gets two kinds of entry.
+_LINEAR_PACKED = _PackedWeightCache()
 _REL_PROJ_F32 = _PackedWeightCache()      # (pos_proj weight | bias,) -> fp32 copy
 
 

@@ -62,19 +62,29 @@ class RelationSelfAttention(nn.Module):
         self.options = options.get()
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, attn_mask: Optional[Tensor] = None,
-                need_weights: bool = False, key_padding_mask: Optional[Tensor] = None):
+                need_weights: bool = False, key_padding_mask: Optional[Tensor] = None, projected=None):
+        """``projected`` (not in nn.MultiheadAttention's signature, optional): ``(qk, v)``, the in-projections of ``query`` (= ``key``)
+        and ``value`` if the caller already has them (the decoder's query-position kernel, csrc/qpos.hip); used on the bf16
+        no-grad path when their shapes and dtypes fit, ignored otherwise."""
         if need_weights or key_padding_mask is not None:
             raise NotImplementedError("need_weights / key_padding_mask are not used on this path")
         B, N, C = query.shape
         M = key.shape[1]
         H, d = self.num_heads, self.head_dim
-        if key is query:                                   # the decoder call: q = k = query + pos, one GEMM for both
+        v = None
+        if (projected is not None and key is query and not torch.is_grad_enabled() and query.dtype == torch.bfloat16
+                and all(torch.is_tensor(t) and t.dtype == torch.bfloat16 and t.device == query.device for t in projected)
+                and tuple(projected[0].shape) == (B, N, 2 * C) and tuple(projected[1].shape) == (B, M, C)):
+            qk, v = projected
+            q, k = qk[..., :C], qk[..., C:]
+        elif key is query:                                 # the decoder call: q = k = query + pos, one GEMM for both
             qk = F.linear(query, self.in_proj_weight[:2 * C], self.in_proj_bias[:2 * C])
             q, k = qk[..., :C], qk[..., C:]
         else:
             q = F.linear(query, self.in_proj_weight[:C], self.in_proj_bias[:C])
             k = F.linear(key, self.in_proj_weight[C:2 * C], self.in_proj_bias[C:2 * C])
-        v = F.linear(value, self.in_proj_weight[2 * C:], self.in_proj_bias[2 * C:])
+        if v is None:
+            v = F.linear(value, self.in_proj_weight[2 * C:], self.in_proj_bias[2 * C:])
         needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)
         if isinstance(attn_mask, DeferredRelationBias):
             rel = attn_mask

@@ -241,11 +241,13 @@ class RelationTransformerDecoderLayer(nn.Module):
         nn.init.xavier_uniform_(self.linear2.weight)
 
     def forward(self, query, query_pos, reference_points, value, spatial_shapes, level_start_index, self_attn_mask=None,
-                key_padding_mask=None, query_plus_pos=None, projected_value=None):
+                key_padding_mask=None, query_plus_pos=None, projected_value=None, projected=None):
         """``query_plus_pos`` (not in the reference's signature, optional): ``query + query_pos`` if the caller already has it;
-        ``projected_value``: ``cross_attn.value_proj(value)`` if the caller already has it (see the decoder)."""
+        ``projected_value``: ``cross_attn.value_proj(value)`` if the caller already has it (see the decoder); ``projected``: the
+        self-attention's in-projections ``(qk, v)`` of ``query_plus_pos`` and ``query`` if the caller already has them."""
         qp = query + query_pos if query_plus_pos is None else query_plus_pos
-        attn = self.self_attn(query=qp, key=qp, value=query, attn_mask=self_attn_mask, need_weights=False)[0]
+        attn = self.self_attn(query=qp, key=qp, value=query, attn_mask=self_attn_mask, need_weights=False,
+                              **({} if projected is None else {"projected": projected}))[0]
         if (query.is_cuda and not torch.is_grad_enabled() and query.dtype in (torch.float32, torch.bfloat16)
                 and query_pos.dtype == query.dtype and query_pos.shape == query.shape and self.options.decoder_ln_pos):
             # inference: norm2 and the cross-attention's `query + query_pos` from one pass (csrc/layernorm.hip)
@@ -333,13 +335,25 @@ class RelationTransformerDecoder(nn.Module):
                     ratio_scale = torch.cat([valid_ratios, valid_ratios], -1)[:, None]
                 ref_in = reference_points.detach()[:, :, None] * ratio_scale        # [B,N,L,4]
                 emb = sine_pos_embed(ref_in[:, :, 0, :], self.embed_dim // 2).to(query.dtype)
-            qpp = None
+            qpp = projected = None
             scale_layers = None if idx == 0 else self.query_scale.layers
             if (self.options.decoder_tail and query.is_cuda and not torch.is_grad_enabled() and emb.dtype == torch.bfloat16
                     and ops.query_pos_k256_supported(emb, query, self.ref_point_head.layers, scale_layers)):
                 # bf16 inference: both MLPs, their product and query + query_pos in ONE launch (csrc/qpos.hip) instead of four
                 # GEMMs + one elementwise launch of the decoder's dependency chain
-                query_pos, qpp = ops.query_pos_k256(emb, query, self.ref_point_head.layers, scale_layers)
+                # ... and, for the layer's own self-attention module, its in-projection of query + query_pos (q, k) and of
+                # query (v) in the same launch instead of two more GEMMs
+                attn = layer.self_attn
+                in_proj = None
+                if (type(attn) is RelationSelfAttention and type(layer).forward is RelationTransformerDecoderLayer.forward
+                        and query.dtype == torch.bfloat16 and attn.embed_dim == 256 and attn.in_proj_weight.dtype == torch.bfloat16
+                        and attn.in_proj_bias.dtype == torch.bfloat16 and attn.in_proj_weight.is_contiguous()
+                        and attn.in_proj_weight.data_ptr() % 16 == 0):
+                    in_proj = {"weight": attn.in_proj_weight, "bias": attn.in_proj_bias}
+                query_pos, qpp = ops.query_pos_k256(emb, query, self.ref_point_head.layers, scale_layers,
+                                                    **({} if in_proj is None else {"in_proj": in_proj}))
+                if in_proj is not None and "qk" in in_proj:
+                    projected = (in_proj["qk"], in_proj["v"])
             else:
                 query_pos = self.ref_point_head(emb)
             if idx != 0 and qpp is None:
@@ -352,19 +366,33 @@ class RelationTransformerDecoder(nn.Module):
                           spatial_shapes=spatial_shapes, level_start_index=level_start_index,
                           key_padding_mask=key_padding_mask, self_attn_mask=pos_relation,
                           **({} if qpp is None else {"query_plus_pos": qpp}),
+                          **({} if projected is None else {"projected": projected}),
                           **({} if values_all is None else
                              {"projected_value": values_all[..., idx * self.embed_dim:(idx + 1) * self.embed_dim]}))
             normed = add_norm(self.norm, query)
-            out_class = self.class_head[idx](normed)
             last = idx == self.num_layers - 1
             # bf16 inference: the box head on `normed` (this layer's boxes) and on `query` (the next reference points) with both
             # refinements as ONE kernel (csrc/mlp.hip) instead of 6 GEMMs + 2 launches of the decoder's dependency chain
             fused_box = (query.is_cuda and not torch.is_grad_enabled() and reference_points.dtype == torch.float32
                          and self.options.box_head and ops.box_head_k256_supported(normed, self.bbox_head[idx].layers))
+            out_class = None
             if fused_box:
-                res = ops.box_head_k256(normed, None if last else query, self.bbox_head[idx].layers, reference_points.detach())
+                # ... and the class head on `normed` in the same launch instead of one more GEMM
+                head = self.class_head[idx]
+                cls = None
+                if (type(head) is nn.Linear and head.in_features == 256 and 1 <= head.out_features <= 256 and head.bias is not None
+                        and head.weight.dtype == torch.bfloat16 and head.bias.dtype == torch.bfloat16 and head.weight.is_contiguous()
+                        and head.weight.data_ptr() % 16 == 0):
+                    cls = {"linear": head}
+                res = ops.box_head_k256(normed, None if last else query, self.bbox_head[idx].layers, reference_points.detach(),
+                                        **({} if cls is None else {"class_head": cls}))
                 out_coord, next_reference = (res, None) if last else res
+                if cls is not None:
+                    out_class = cls.get("out")
+                if out_class is None:
+                    out_class = self.class_head[idx](normed)
             else:
+                out_class = self.class_head[idx](normed)
                 # boxes stay fp32 whatever the network dtype (a bf16 + fp32 add takes torch's slow mixed-dtype kernel)
                 out_coord = refine_boxes(self.bbox_head[idx](normed), reference_points)
             classes.append(out_class)
