@@ -476,6 +476,31 @@ int rdetr_add_layernorm_pos_bf16(const uint16_t *x, const uint16_t *residual, co
                                  long long ldr, long long ldo, long long ldp, long long ldo2, float eps, uint16_t *out,
                                  uint16_t *out2, void *stream);
 
+/* Training forms, C = 256 only (RDETR_ERR_UNSUPPORTED for any other C, or for operands off the 16-byte grid: pointers, and row
+ * strides in bytes; there is no generic-C route -- the caller keeps its own).
+ *   ..._train_*     the strided forward, same `out` bits, plus stats[rows, 2] fp32 = {mean, 1/sqrt(var + eps)} of every row.
+ *   ..._backward_*  from dy [rows, 256] (rows lddy apart), the forward's x / residual (nullable) and stats:
+ *                     xhat = (x + residual - mean) * rstd (the sum in fp32, unrounded),  g = dy * gamma,
+ *                     dx [rows, 256] (contiguous) = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat))  -- the gradient of x AND of
+ *                     residual;  dgamma = sum_rows dy * xhat,  dbeta = sum_rows dy  ([256], the operands' dtype).
+ *                   dgamma and dbeta may both be null (frozen parameters): no workspace is needed and one kernel runs.  Otherwise
+ *                   workspace holds per-workgroup fp32 partials that a second kernel adds in index order -- no atomics, the same bits
+ *                   on every run; size from the _workspace_bytes function, 16-byte aligned, contents are scratch. */
+int rdetr_add_layernorm_train_f32(const float *x, const float *residual, const float *gamma, const float *beta, long long rows,
+                                  int C, long long ldx, long long ldr, long long ldo, float eps, float *out, float *stats,
+                                  void *stream);
+int rdetr_add_layernorm_train_bf16(const uint16_t *x, const uint16_t *residual, const uint16_t *gamma, const uint16_t *beta,
+                                   long long rows, int C, long long ldx, long long ldr, long long ldo, float eps, uint16_t *out,
+                                   float *stats, void *stream);
+long long rdetr_add_layernorm_backward_workspace_bytes(long long rows);
+int rdetr_add_layernorm_backward_f32(const float *dy, long long lddy, const float *x, long long ldx, const float *residual,
+                                     long long ldr, const float *gamma, const float *stats, long long rows, int C, void *workspace,
+                                     long long workspace_bytes, float *dx, float *dgamma, float *dbeta, void *stream);
+int rdetr_add_layernorm_backward_bf16(const uint16_t *dy, long long lddy, const uint16_t *x, long long ldx,
+                                      const uint16_t *residual, long long ldr, const uint16_t *gamma, const float *stats,
+                                      long long rows, int C, void *workspace, long long workspace_bytes, uint16_t *dx,
+                                      uint16_t *dgamma, uint16_t *dbeta, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused elementwise steps of the decoder's box bookkeeping (each replaces ~8 torch launches on a [B,N,4] tensor).
  *   rdetr_box_refine_f32   out = sigmoid(delta + inverse_sigmoid(ref)),  inverse_sigmoid as util/misc.py:31-35 (eps 1e-3);

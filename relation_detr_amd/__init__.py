@@ -12,6 +12,7 @@ from .ops import (MultiScaleDeformableAttnFunction, MultiScaleDeformableAttnFuse
                   relation_attention_backward, relation_attention_train, relation_bias)
 from .attn_rel_train import RelationAttentionBoxesFunction, relation_attention_boxes_backward, relation_attention_boxes_train
 from .ffn_train import FeedForwardFunction, ffn_k256_backward, ffn_k256_train
+from .ln_train import AddLayerNormFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
 
 __all__ = [
@@ -21,6 +22,6 @@ __all__ = [
     "ms_deform_attn_forward_fused", "ms_deform_attn_backward", "ms_deform_attn_backward_fused", "relation_bias", "bias_softmax_",
     "RelationAttentionFunction", "relation_attention_train", "relation_attention_backward",
     "RelationAttentionBoxesFunction", "relation_attention_boxes_train", "relation_attention_boxes_backward",
-    "FeedForwardFunction", "ffn_k256_train", "ffn_k256_backward",
+    "FeedForwardFunction", "ffn_k256_train", "ffn_k256_backward", "AddLayerNormFunction",
     "MultiScaleDeformableAttnHeadMajorFunction", "ms_deform_attn_backward_fused_hm", "grad_value_from_head_major",
 ]

@@ -90,6 +90,11 @@ SIGNATURES = {
     "rdetr_add_layernorm_strided_bf16": [_vp] * 4 + [_c_ll, _c_int, _c_ll, _c_ll, _c_ll, _c_float, _vp, _vp],
     "rdetr_add_layernorm_pos_f32": [_vp] * 5 + [_c_ll, _c_int] + [_c_ll] * 5 + [_c_float, _vp, _vp, _vp],
     "rdetr_add_layernorm_pos_bf16": [_vp] * 5 + [_c_ll, _c_int] + [_c_ll] * 5 + [_c_float, _vp, _vp, _vp],
+    "rdetr_add_layernorm_train_f32": [_vp] * 4 + [_c_ll, _c_int, _c_ll, _c_ll, _c_ll, _c_float, _vp, _vp, _vp],
+    "rdetr_add_layernorm_train_bf16": [_vp] * 4 + [_c_ll, _c_int, _c_ll, _c_ll, _c_ll, _c_float, _vp, _vp, _vp],
+    "rdetr_add_layernorm_backward_workspace_bytes": [_c_ll],
+    "rdetr_add_layernorm_backward_f32": [_vp, _c_ll] * 3 + [_vp, _vp, _c_ll, _c_int, _vp, _c_ll] + [_vp] * 4,
+    "rdetr_add_layernorm_backward_bf16": [_vp, _c_ll] * 3 + [_vp, _vp, _c_ll, _c_int, _vp, _c_ll] + [_vp] * 4,
 }
 
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3            # rdetr_status (include/relation_detr_amd.h)

@@ -9,6 +9,9 @@
 //   Statistics in fp32, two-pass in registers (mean, then the variance of the centred values), biased variance and
 //   1/sqrt(var + eps) as torch.nn.functional.layer_norm; the sum x + r is NOT rounded to the storage type first.
 // Bound: HBM (3 x rows x C x sizeof(T) bytes per call).
+//
+// Training (C = 256 only, further down): the same forward body that also stores {mean, rstd} per row, and the backward from them --
+// dx for both operands in one pass over dy, x and r, dgamma / dbeta through per-workgroup partials summed in a fixed order.
 #include "common.h"
 
 namespace rdetr {
@@ -103,14 +106,13 @@ template <> struct LnIO8<uint16_t> {
 // C == 256: a half wave owns a row (a lane 8 consecutive channels = one 16-byte bf16 access), a wave works on 4 rows with
 // all of their loads issued before the first use (the one-row-per-wave version kept 1.5 KB in flight per wave and reached
 // 3.7 TB/s; HBM needs more outstanding bytes than that).
-template <typename T>
-__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_kernel(const T *__restrict__ x, const T *__restrict__ r,
-                                                                           const T *__restrict__ gamma,
-                                                                           const T *__restrict__ beta, long long rows,
-                                                                           long long ldx, long long ldr, long long ldo,
-                                                                           float eps, T *__restrict__ out,
-                                                                           const T *__restrict__ pos, long long ldp,
-                                                                           T *__restrict__ out2, long long ldo2)
+// kStats (the training forward): additionally the row's mean and 1/sqrt(var + eps) as fp32 into stats[row] = {mean, rstd}, what the
+// backward kernel below starts from.  The arithmetic is the one body, so `out` has the same bits with and without.
+template <typename T, bool kStats>
+__device__ __forceinline__ void add_layernorm256_body(const T *__restrict__ x, const T *__restrict__ r, const T *__restrict__ gamma,
+                                                      const T *__restrict__ beta, long long rows, long long ldx, long long ldr,
+                                                      long long ldo, float eps, T *__restrict__ out, const T *__restrict__ pos,
+                                                      long long ldp, T *__restrict__ out2, long long ldo2, float *__restrict__ stats)
 {
     const int lane = threadIdx.x & 63, half = lane >> 5, c = (lane & 31) * 8;
     const long long row0 = ((long long)blockIdx.x * kLnWaves + (threadIdx.x >> 6)) * kLnRowsPerWave + half;
@@ -160,6 +162,9 @@ __global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_kernel(const
         for (int k = 0; k < 8; ++k) y[k] = v[i][k] * rstd * g[k] + b[k];
         if (row < rows) {
             LnIO8<T>::store(out + row * ldo + c, y);
+            if constexpr (kStats) {
+                if ((lane & 31) == 0) *reinterpret_cast<f32x2 *>(stats + row * 2) = f32x2{mean, rstd};
+            }
             if (out2) {                      // out2 = out + pos, from the STORED (rounded) normalised values: the bits of a separate add
                 float pv[8];
                 LnIO8<T>::load(pos + row * ldp + c, pv);
@@ -169,6 +174,29 @@ __global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_kernel(const
             }
         }
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_kernel(const T *__restrict__ x, const T *__restrict__ r,
+                                                                           const T *__restrict__ gamma,
+                                                                           const T *__restrict__ beta, long long rows,
+                                                                           long long ldx, long long ldr, long long ldo,
+                                                                           float eps, T *__restrict__ out,
+                                                                           const T *__restrict__ pos, long long ldp,
+                                                                           T *__restrict__ out2, long long ldo2)
+{
+    add_layernorm256_body<T, false>(x, r, gamma, beta, rows, ldx, ldr, ldo, eps, out, pos, ldp, out2, ldo2, nullptr);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_train_kernel(const T *__restrict__ x, const T *__restrict__ r,
+                                                                                 const T *__restrict__ gamma,
+                                                                                 const T *__restrict__ beta, long long rows,
+                                                                                 long long ldx, long long ldr, long long ldo,
+                                                                                 float eps, T *__restrict__ out,
+                                                                                 float *__restrict__ stats)
+{
+    add_layernorm256_body<T, true>(x, r, gamma, beta, rows, ldx, ldr, ldo, eps, out, nullptr, 0, nullptr, 0, stats);
 }
 
 template <typename T>
@@ -225,7 +253,230 @@ static int add_layernorm(const T *x, const T *r, const T *gamma, const T *beta, 
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------- training
+// Forward with the row statistics kept, C == 256 only: the vectorised kernel or RDETR_ERR_UNSUPPORTED (no generic-C route).
+template <typename T>
+static int add_layernorm_train(const T *x, const T *r, const T *gamma, const T *beta, long long rows, int C, long long ldx,
+                               long long ldr, long long ldo, float eps, T *out, float *stats, hipStream_t stream)
+{
+    if (rows < 0 || C <= 0 || ldx < C || ldo < C || (r && ldr < C)) return RDETR_ERR_INVALID_ARG;
+    if (C != 256) return RDETR_ERR_UNSUPPORTED;
+    if (rows == 0) return RDETR_OK;
+    if (!x || !gamma || !beta || !out || !stats) return RDETR_ERR_INVALID_ARG;
+    const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave);
+    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    const long long a16 = 16 / (long long)sizeof(T);
+    if (!(al16(x) && al16(out) && al16(gamma) && al16(beta) && (!r || al16(r)) && ldx % a16 == 0 && ldo % a16 == 0 &&
+          (!r || ldr % a16 == 0) && reinterpret_cast<uintptr_t>(stats) % 8 == 0))
+        return RDETR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((add_layernorm256_train_kernel<T>), dim3((unsigned)nblk), dim3(kLnWaves * kWave), 0, stream, x, r, gamma, beta,
+                       rows, ldx, ldr, ldo, eps, out, stats);
+    return launch_status();
+}
+
+// Backward of out = LayerNorm(x + r) * gamma + beta from the saved {mean, rstd}, C == 256, the forward's layout (half a wave per
+// row, a lane 8 channels, a wave 4 rows with every load issued before the first use):
+//     xhat = (x + r - mean) * rstd   (the sum in fp32, not rounded, as the forward formed it)      g = dy * gamma
+//     dx = rstd * (g - mean_c(g) - xhat * mean_c(g * xhat))       -- ONE tensor: the gradient of x and of r
+//     dgamma = sum_rows dy * xhat                                 dbeta = sum_rows dy
+// A bounded grid (kLnBwdMaxBlocks) walks the 16-row blocks with a grid stride; a lane keeps its 8 + 8 fp32 partial sums of dgamma /
+// dbeta in registers across trips, the workgroup adds its 8 half-waves through LDS in index order and writes ONE [2, 256] partial;
+// ln_param_grad_kernel then adds the partials in index order.  No atomics: the same bits every run.
+// Bound: HBM (4 x rows x C x sizeof(T) bytes; the partials are at most 2 MiB).
+constexpr int kLnBwdMaxBlocks = 1024;      // 4 workgroups (16 waves) on each of the MI355X's 256 CUs: 24 KB of bf16 loads per CU and trip
+
+template <typename T, bool kParams>
+__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_kernel(const T *__restrict__ dy, long long lddy,
+                                                                               const T *__restrict__ x, long long ldx,
+                                                                               const T *__restrict__ r, long long ldr,
+                                                                               const T *__restrict__ gamma,
+                                                                               const float *__restrict__ stats, long long rows,
+                                                                               long long nblk, T *__restrict__ dx,
+                                                                               float *__restrict__ partial)
+{
+    __shared__ float red[kLnWaves * 2][2][256];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, c = (lane & 31) * 8;
+    float g[8], ag[8], ab[8];
+    LnIO8<T>::load(gamma + c, g);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ag[k] = ab[k] = 0.f;
+    for (long long blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+        const long long row0 = (blk * kLnWaves + wave) * kLnRowsPerWave + half;
+        float d[2][8], v[2][8], mean[2], rstd[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const long long row = row0 + 2 * i;
+            if (row < rows) {
+                LnIO8<T>::load(dy + row * lddy + c, d[i]);
+                LnIO8<T>::load(x + row * ldx + c, v[i]);
+                const f32x2 st = *reinterpret_cast<const f32x2 *>(stats + row * 2);
+                mean[i] = st.x;
+                rstd[i] = st.y;
+            } else {                         // a row past the end: dy = 0 adds nothing to the parameter sums, nothing is stored
+#pragma unroll
+                for (int k = 0; k < 8; ++k) d[i][k] = v[i][k] = 0.f;
+                mean[i] = rstd[i] = 0.f;
+            }
+        }
+        if (r) {
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const long long row = row0 + 2 * i;
+                if (row < rows) {
+                    float t[8];
+                    LnIO8<T>::load(r + row * ldr + c, t);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) v[i][k] += t[k];
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const long long row = row0 + 2 * i;
+            float gg[8], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                v[i][k] = (v[i][k] - mean[i]) * rstd[i];              // xhat
+                gg[k] = d[i][k] * g[k];
+                s1 += gg[k];
+                s2 += gg[k] * v[i][k];
+            }
+            const float m1 = ln_half_sum(s1) * (1.0f / 256.0f), m2 = ln_half_sum(s2) * (1.0f / 256.0f);
+            float o[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o[k] = rstd[i] * (gg[k] - m1 - v[i][k] * m2);
+            if (row < rows) LnIO8<T>::store(dx + row * 256 + c, o);
+            if constexpr (kParams) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    ag[k] += d[i][k] * v[i][k];
+                    ab[k] += d[i][k];
+                }
+            }
+        }
+    }
+    if constexpr (kParams) {
+        const int hw = wave * 2 + half;
+        *reinterpret_cast<f32x4 *>(&red[hw][0][c]) = f32x4{ag[0], ag[1], ag[2], ag[3]};
+        *reinterpret_cast<f32x4 *>(&red[hw][0][c + 4]) = f32x4{ag[4], ag[5], ag[6], ag[7]};
+        *reinterpret_cast<f32x4 *>(&red[hw][1][c]) = f32x4{ab[0], ab[1], ab[2], ab[3]};
+        *reinterpret_cast<f32x4 *>(&red[hw][1][c + 4]) = f32x4{ab[4], ab[5], ab[6], ab[7]};
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {                              // 256 threads, 512 sums: (which, channel) = (j, threadIdx.x)
+            float s = 0.f;
+#pragma unroll
+            for (int h = 0; h < kLnWaves * 2; ++h) s += red[h][j][threadIdx.x];
+            partial[(long long)blockIdx.x * 512 + j * 256 + threadIdx.x] = s;
+        }
+    }
+}
+
+// dgamma / dbeta from the workgroups' partials [n, 2, 256]: one workgroup, thread t owns (which, channel) = (t / 256, t % 256) and
+// adds the n values in index order.  One CU reads up to 2 MiB here, so the loop is bound by the loads it keeps in flight: 32 per
+// thread, and the next 32 are issued before the current ones are added (an index past the end reads the last partial and adds 0).
+constexpr int kLnGradBatch = 32;
+
+template <typename T>
+__global__ __launch_bounds__(512) void ln_param_grad_kernel(const float *__restrict__ partial, int n, T *__restrict__ dgamma,
+                                                            T *__restrict__ dbeta)
+{
+    const int t = threadIdx.x;
+    const float *col = partial + t;
+    float cur[kLnGradBatch], nxt[kLnGradBatch], s = 0.f;
+#pragma unroll
+    for (int j = 0; j < kLnGradBatch; ++j) cur[j] = col[(long long)(j < n ? j : n - 1) * 512];
+    for (int p0 = 0; p0 < n; p0 += kLnGradBatch) {
+        const int q0 = p0 + kLnGradBatch;
+        if (q0 < n) {
+#pragma unroll
+            for (int j = 0; j < kLnGradBatch; ++j) nxt[j] = col[(long long)(q0 + j < n ? q0 + j : n - 1) * 512];
+        }
+#pragma unroll
+        for (int j = 0; j < kLnGradBatch; ++j) s += p0 + j < n ? cur[j] : 0.f;
+#pragma unroll
+        for (int j = 0; j < kLnGradBatch; ++j) cur[j] = nxt[j];
+    }
+    LnIO<T>::store1((t < 256 ? dgamma : dbeta) + (t & 255), s);
+}
+
+static long long ln_backward_blocks(long long rows)
+{
+    const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave);
+    return nblk < kLnBwdMaxBlocks ? nblk : kLnBwdMaxBlocks;
+}
+
+template <typename T>
+static int add_layernorm_backward(const T *dy, long long lddy, const T *x, long long ldx, const T *r, long long ldr, const T *gamma,
+                                  const float *stats, long long rows, int C, void *workspace, long long workspace_bytes, T *dx,
+                                  T *dgamma, T *dbeta, hipStream_t stream)
+{
+    if (rows < 0 || C <= 0 || lddy < C || ldx < C || (r && ldr < C) || workspace_bytes < 0) return RDETR_ERR_INVALID_ARG;
+    if ((dgamma != nullptr) != (dbeta != nullptr)) return RDETR_ERR_INVALID_ARG;
+    if (C != 256) return RDETR_ERR_UNSUPPORTED;
+    if (rows == 0) return RDETR_OK;
+    if (!dy || !x || !gamma || !stats || !dx) return RDETR_ERR_INVALID_ARG;
+    const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave), grid = ln_backward_blocks(rows);
+    if (dgamma && (!workspace || workspace_bytes < grid * 512 * (long long)sizeof(float))) return RDETR_ERR_INVALID_ARG;
+    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
+    const long long a16 = 16 / (long long)sizeof(T);
+    if (!(al16(dy) && al16(x) && al16(dx) && al16(gamma) && (!r || al16(r)) && lddy % a16 == 0 && ldx % a16 == 0 &&
+          (!r || ldr % a16 == 0) && reinterpret_cast<uintptr_t>(stats) % 8 == 0 && (!dgamma || al16(workspace))))
+        return RDETR_ERR_UNSUPPORTED;
+    if (dgamma) {
+        float *partial = static_cast<float *>(workspace);
+        hipLaunchKernelGGL((add_layernorm256_bwd_kernel<T, true>), dim3((unsigned)grid), dim3(kLnWaves * kWave), 0, stream, dy, lddy, x,
+                           ldx, r, ldr, gamma, stats, rows, nblk, dx, partial);
+        if (launch_status() != RDETR_OK) return RDETR_ERR_LAUNCH;
+        hipLaunchKernelGGL((ln_param_grad_kernel<T>), dim3(1), dim3(512), 0, stream, partial, (int)grid, dgamma, dbeta);
+    } else {
+        hipLaunchKernelGGL((add_layernorm256_bwd_kernel<T, false>), dim3((unsigned)grid), dim3(kLnWaves * kWave), 0, stream, dy, lddy, x,
+                           ldx, r, ldr, gamma, stats, rows, nblk, dx, static_cast<float *>(nullptr));
+    }
+    return launch_status();
+}
+
 }  // namespace rdetr
+
+extern "C" int rdetr_add_layernorm_train_f32(const float *x, const float *residual, const float *gamma, const float *beta,
+                                             long long rows, int C, long long ldx, long long ldr, long long ldo, float eps, float *out,
+                                             float *stats, void *stream)
+{
+    return rdetr::add_layernorm_train<float>(x, residual, gamma, beta, rows, C, ldx, ldr, ldo, eps, out, stats,
+                                             static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rdetr_add_layernorm_train_bf16(const uint16_t *x, const uint16_t *residual, const uint16_t *gamma, const uint16_t *beta,
+                                              long long rows, int C, long long ldx, long long ldr, long long ldo, float eps,
+                                              uint16_t *out, float *stats, void *stream)
+{
+    return rdetr::add_layernorm_train<uint16_t>(x, residual, gamma, beta, rows, C, ldx, ldr, ldo, eps, out, stats,
+                                                static_cast<hipStream_t>(stream));
+}
+
+extern "C" long long rdetr_add_layernorm_backward_workspace_bytes(long long rows)
+{
+    return rows <= 0 ? 0 : rdetr::ln_backward_blocks(rows) * 512 * (long long)sizeof(float);
+}
+
+extern "C" int rdetr_add_layernorm_backward_f32(const float *dy, long long lddy, const float *x, long long ldx, const float *residual,
+                                                long long ldr, const float *gamma, const float *stats, long long rows, int C,
+                                                void *workspace, long long workspace_bytes, float *dx, float *dgamma, float *dbeta,
+                                                void *stream)
+{
+    return rdetr::add_layernorm_backward<float>(dy, lddy, x, ldx, residual, ldr, gamma, stats, rows, C, workspace, workspace_bytes, dx,
+                                                dgamma, dbeta, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rdetr_add_layernorm_backward_bf16(const uint16_t *dy, long long lddy, const uint16_t *x, long long ldx,
+                                                 const uint16_t *residual, long long ldr, const uint16_t *gamma, const float *stats,
+                                                 long long rows, int C, void *workspace, long long workspace_bytes, uint16_t *dx,
+                                                 uint16_t *dgamma, uint16_t *dbeta, void *stream)
+{
+    return rdetr::add_layernorm_backward<uint16_t>(dy, lddy, x, ldx, residual, ldr, gamma, stats, rows, C, workspace, workspace_bytes,
+                                                   dx, dgamma, dbeta, static_cast<hipStream_t>(stream));
+}
 
 extern "C" int rdetr_add_layernorm_f32(const float *x, const float *residual, const float *gamma, const float *beta,
                                        long long rows, int C, float eps, float *out, void *stream)

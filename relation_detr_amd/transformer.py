@@ -23,7 +23,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
-from . import ffn_train, ops
+from . import ffn_train, ln_train, ops
 from . import options as _options
 from .ms_deform_attn import MultiScaleDeformableAttention
 from .relation import PositionRelationEmbedding
@@ -58,15 +58,21 @@ def sine_pos_embed(pos: Tensor, num_pos_feats: int = 128, temperature: float = 1
     return torch.cat((emb[..., 1:2, :], emb[..., 0:1, :], emb[..., 2:, :]), dim=-2).flatten(-2)
 
 
-def add_norm(norm: nn.LayerNorm, x: Tensor, residual: Tensor = None, out: Tensor = None) -> Tensor:
+def add_norm(norm: nn.LayerNorm, x: Tensor, residual: Tensor = None, out: Tensor = None, opts: "_options.Options" = None) -> Tensor:
     """norm(x + residual).  On a ROCm device without autograd: one HIP kernel (rdetr_add_layernorm_*, csrc/layernorm.hip)
-    instead of an add pass and a normalisation pass; otherwise (CPU oracle harness, training) plain torch."""
+    instead of an add pass and a normalisation pass.  Where a gradient is needed, options.ln_train_fused sends fp32 / bf16 inputs
+    of 256 channels through the same kernel body and its backward (ln_train.AddLayerNormFunction); everything else -- the CPU
+    oracle harness, and training by default -- is plain torch."""
     needs_grad = torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad or
                                               (residual is not None and residual.requires_grad))
     if x.is_cuda and not needs_grad and x.dtype in (torch.float32, torch.bfloat16):
         from . import ops
         return ops.add_layer_norm(x, residual, norm.weight, norm.bias, norm.eps, out=out)
-    y = norm(x if residual is None else x + residual)
+    if (needs_grad and (opts or _options.get()).ln_train_fused
+            and ln_train.add_layer_norm_train_supported(x, residual, norm.weight, norm.bias)):
+        y = ln_train.AddLayerNormFunction.apply(x, residual, norm.weight, norm.bias, norm.eps)
+    else:
+        y = norm(x if residual is None else x + residual)
     if out is not None:
         out.copy_(y)
         return out
@@ -166,7 +172,7 @@ class RelationTransformerEncoderLayer(nn.Module):
             attn = self.self_attn(query=query_plus_pos, reference_points=reference_points,
                                   value=query, spatial_shapes=spatial_shapes, level_start_index=level_start_index,
                                   key_padding_mask=key_padding_mask)
-            query = add_norm(self.norm1, query, attn)
+            query = add_norm(self.norm1, query, attn, opts=self.options)
         if self.options.ffn_ln and _fused_ffn_applies(self.linear1, self.linear2, query, self.options):
             # opt-in: feed-forward block, residual, LayerNorm (and the next layer's query + pos) in ONE kernel (csrc/ffn.hip).
             # Correct (tests/test_gpu_glue.py) but 3-6 % slower in the stack than fused FFN + the add+LayerNorm kernel: the
@@ -176,7 +182,7 @@ class RelationTransformerEncoderLayer(nn.Module):
         ffn = feed_forward(self.linear1, self.linear2, query, self.options)
         if next_pos is not None:
             return ops.add_layer_norm(query, ffn, self.norm2.weight, self.norm2.bias, self.norm2.eps, out=out, pos=next_pos)
-        return add_norm(self.norm2, query, ffn, out=out)
+        return add_norm(self.norm2, query, ffn, out=out, opts=self.options)
 
 
 class RelationTransformerEncoder(nn.Module):
@@ -216,12 +222,12 @@ class RelationTransformerEncoder(nn.Module):
                             out=stacked[..., (i + 1) * d:(i + 2) * d], query_plus_pos=qpp,
                             next_pos=query_pos if fuse_pos and not last else None)
                 query, qpp = res if isinstance(res, tuple) else (res, None)
-            return add_norm(fuse[3], fuse[2](linear_relu(fuse[0], stacked, self.options)))
+            return add_norm(fuse[3], fuse[2](linear_relu(fuse[0], stacked, self.options)), opts=self.options)
         outs = [query]
         for layer in self.layers:
             query = layer(query, query_pos, reference_points, spatial_shapes, level_start_index, query_key_padding_mask)
             outs.append(query)
-        return add_norm(fuse[3], fuse[2](linear_relu(fuse[0], torch.cat(outs, -1), self.options)))
+        return add_norm(fuse[3], fuse[2](linear_relu(fuse[0], torch.cat(outs, -1), self.options)), opts=self.options)
 
 
 class RelationTransformerDecoderLayer(nn.Module):
@@ -253,14 +259,14 @@ class RelationTransformerDecoderLayer(nn.Module):
             # inference: norm2 and the cross-attention's `query + query_pos` from one pass (csrc/layernorm.hip)
             query, cross_q = ops.add_layer_norm(attn, query, self.norm2.weight, self.norm2.bias, self.norm2.eps, pos=query_pos)
         else:
-            query = add_norm(self.norm2, query, attn)
+            query = add_norm(self.norm2, query, attn, opts=self.options)
             cross_q = query + query_pos
         cross = self.cross_attn(query=cross_q, reference_points=reference_points, value=value,
                                 spatial_shapes=spatial_shapes, level_start_index=level_start_index,
                                 key_padding_mask=key_padding_mask,
                                 **({} if projected_value is None else {"projected_value": projected_value}))
-        query = add_norm(self.norm1, query, cross)
-        return add_norm(self.norm3, query, feed_forward(self.linear1, self.linear2, query, self.options))
+        query = add_norm(self.norm1, query, cross, opts=self.options)
+        return add_norm(self.norm3, query, feed_forward(self.linear1, self.linear2, query, self.options), opts=self.options)
 
 
 class RelationTransformerDecoder(nn.Module):
@@ -369,7 +375,7 @@ class RelationTransformerDecoder(nn.Module):
                           **({} if projected is None else {"projected": projected}),
                           **({} if values_all is None else
                              {"projected_value": values_all[..., idx * self.embed_dim:(idx + 1) * self.embed_dim]}))
-            normed = add_norm(self.norm, query)
+            normed = add_norm(self.norm, query, opts=self.options)
             last = idx == self.num_layers - 1
             # bf16 inference: the box head on `normed` (this layer's boxes) and on `query` (the next reference points) with both
             # refinements as ONE kernel (csrc/mlp.hip) instead of 6 GEMMs + 2 launches of the decoder's dependency chain
@@ -518,7 +524,7 @@ class RelationTransformer(nn.Module):
         logit = logit.masked_fill(padding_mask.unsqueeze(-1) | ~valid, float("inf"))
         keep = (~padding_mask.unsqueeze(-1)) & valid                                 # one pass over memory instead of two
         out = memory * keep.to(memory.dtype)
-        return add_norm(self.enc_output_norm, self.enc_output(out)), logit
+        return add_norm(self.enc_output_norm, self.enc_output(out), opts=self.options), logit
 
     def forward(self, multi_level_feats: Sequence[Tensor], multi_level_masks: Sequence[Tensor],
                 multi_level_pos_embeds: Sequence[Tensor], noised_label_query: Tensor = None, noised_box_query: Tensor = None,
@@ -556,7 +562,7 @@ class RelationTransformer(nn.Module):
                               level_start_index=start, reference_points=reference, fusion_buffer=fusion_buffer)
 
         if fast:
-            out_memory = add_norm(self.enc_output_norm, self.enc_output(memory * keep.unsqueeze(-1)))
+            out_memory = add_norm(self.enc_output_norm, self.enc_output(memory * keep.unsqueeze(-1)), opts=self.options)
         else:
             out_memory, out_proposals = self.encoder_output(memory, proposals, mask)
         enc_class, enc_coord = self._top_proposals(out_memory, out_proposals, self.encoder_class_head, self.encoder_bbox_head,
