@@ -1,13 +1,16 @@
 """Shadow checks of every kernel launch on a forward (or training step) of the stack.
 
-``Shadow(monkeypatch)`` replaces the module-level functions of ``relation_detr_amd.ops`` with wrappers.  Every call site in
-transformer.py, ms_deform_attn.py, self_attn.py and relation.py looks them up as ``ops.<name>``, and the autograd Functions in
-ops.py reach them through the module's globals, so a wrapper sees every launch of the stack.  A wrapper copies the tensor
+``Shadow(monkeypatch)`` replaces the module-level functions of ``relation_detr_amd.ops`` with wrappers, and those of the four
+training modules that call the library themselves (``ffn_train``, ``ln_train``, ``attn_rel_train``, ``msda_train_hm``).  Every call
+site in transformer.py, ms_deform_attn.py, self_attn.py and relation.py looks the former up as ``ops.<name>``; the autograd
+Functions in ops.py and in the training modules reach their entries through their own module's globals, so a wrapper sees every
+launch of the stack, forward or training step, whichever opt-in training route is on.  A wrapper copies the tensor
 arguments BEFORE the call (some entries work in place, some write ``out=`` slices of wider buffers), calls the kernel, then
 computes a reference from the copies and RECORDS the result (op, call index, worst err / bound ratio, failing elements, where
 the worst one is).  ``Shadow.report()`` prints the per-op table; ``Shadow.assert_ok()`` fails on any bad record.
 
-Every function of ``ops`` is classified in ``KERNEL_ENTRIES`` (a checker each) or ``HOST_ONLY``; a call to a function in
+Every function of ``ops`` is classified in ``KERNEL_ENTRIES`` (a checker each) or ``HOST_ONLY``, every function of the training
+modules in ``TRAIN_ENTRIES`` (keyed "module.function", the op name of its records) or ``TRAIN_HOST_ONLY``; a call to a function in
 neither is recorded as "kernel `<name>` ran without a shadow reference".  At the C boundary every launching ``rdetr_*`` symbol
 of the library object is replaced by a counting tripwire that fails unless a checked entry is active (depth > 0), so no launch
 can get past the harness through an unclassified helper.
@@ -55,6 +58,30 @@ Bounds (err = |kernel - reference|; "exact" = bit equality; each from the unit t
                                   fp32 pixel coordinates the kernel forms
   ms_deform_attn_backward_fused   fp32: as above;  bf16: 2^-8 |ref| + 1e-3 max(1, max|ref|),   test_gpu_msda_train_fused (close_bf16)
                                   offsets / reference points away from kinks
+
+Training entries outside ops.py ("bf16 form" = 2^-8 |ref| + 1e-3 max(1, max|ref|) against the float64 value: the one rounding
+to bf16 the kernel makes, plus its fp32 accumulation; tests/test_shadow_train_host.py holds the checkers themselves on the CPU):
+
+  ffn_train.ffn_k256_train        out as ffn_k256;  hid = relu(x W1^T + b1): bf16 form          test_gpu_ffn_train (within_bf16_form)
+  ffn_train.ffn_k256_backward     dH = dy W2 where the handed hid > 0: bf16 form, bit-zero     test_gpu_ffn_train::test_backward_kernel_rounding_points
+                                  elsewhere;  dx = dH W1 from the RETURNED dH: bf16 form
+  ln_train.add_layer_norm_train   out as add_layer_norm;  mean, rstd of x + residual:           test_gpu_ln_train (stats 1e-5)
+                                  1e-5 max(1, |ref|) per row
+  ln_train.add_layer_norm_backward  statistics recomputed in float64.  bf16: dx, dgamma, dbeta  test_gpu_ln_train::test_accuracy_against_float64
+                                  bf16 form;  fp32: dx 1e-5 max(1, max|ref|), dgamma / dbeta
+                                  (1e-6 + 4 2^-24 sqrt(rows)) max(1, max|ref|)
+  attn_rel_train._relation_attention_boxes_train   out as relation_attention_boxes, lse as      test_gpu_attn_rel_train, test_gpu_attn_train
+                                  _relation_attention_train
+  attn_rel_train._relation_attention_boxes_backward   dq, dk, dv as _relation_attention_backward  test_gpu_attn_rel_train (_check_all, TAU)
+                                  with the float64 relation bias;  grad_weight, grad_bias through
+                                  the float64 ReLU: 2^-7 |ref| + 2e-2 max|ref| + sum |dS_ref| |feature|
+                                  over the pairs with |pre-activation bias| < TAU = 8e-3 (the branch
+                                  the bf16 sine features may switch); those pairs, over images and
+                                  heads, at most 25 % of [N, M] and no complete row, or the call fails
+  msda_train_hm.ms_deform_attn_backward_fused_hm   ms_deform_attn_backward_fused's checker and    test_gpu_msda_train_hm
+                                  bf16 bounds on the [B,S,H,D] permutation of the value
+  msda_train_hm.grad_value_from_head_major   exact (the torch expression of its docstring)       test_gpu_msda_train_hm
+No constant was raised for the training step: profiles/r14/ has every entry's worst err / bound ratio there, all below 1.
 """
 from __future__ import annotations
 
@@ -113,6 +140,8 @@ class Cmp:
     ref: torch.Tensor
     bound: object = 0.0                      # tensor or scalar; 0 = exact (bit equality of the values)
     keep: Optional[torch.Tensor] = None      # bool: elements compared (others are kink points etc.)
+    gate: bool = False                       # a condition of the check, not an error: fails like any Cmp, but while it holds
+                                             # its ratio stays out of the record's worst err / bound
 
 
 @dataclasses.dataclass
@@ -330,11 +359,11 @@ def chk__relation_attention_train(a, res):
     return [_attn_cmp("out", res[0], ref), Cmp("lse", res[1].double() * math.log(2.0), lse, 1e-3)]
 
 
-def chk__relation_attention_backward(a, res):
+def _attention_backward64(a, bias):
     """The attention backward in float64 from the operands the kernel reads: P = softmax of the logits, dP = dout V^T, and the
     row term D = rowsum(dout * out) from the forward output `out` it is handed (bf16), as the flash-style backward defines it
     -- D from the exact output instead differs by the bf16 rounding of `out` times |dout|, which at full size, where the
-    dq / dk of most rows are small against dP, is several times the bound."""
+    dq / dk of most rows are small against dP, is several times the bound.  -> ({dq, dk, dv}, dS [B,H,N,M])."""
     H, scale = a["num_heads"], a["scale"]
     q, k, v, out = _d(a["q"]), _d(a["k"]), _d(a["v"]), _d(a["out"])
     dout = a["dout"].to(BF16).double()                         # the kernel reads dout in bf16
@@ -342,20 +371,29 @@ def chk__relation_attention_backward(a, res):
     M, D = k.shape[1], C // H
     scale = D ** -0.5 if scale is None else scale
     heads = lambda t, n: t.view(B, n, H, D).transpose(1, 2)                                          # noqa: E731
-    _, s = _attention(q, k, v, H, a["bias"], a["mask"], scale)
+    _, s = _attention(q, k, v, H, bias, a["mask"], scale)
     p = torch.nan_to_num(s.softmax(-1), nan=0.0)                                                      # fully masked rows: 0
     dp = heads(dout, N) @ heads(v, M).transpose(-1, -2)
     dterm = (heads(dout, N) * heads(out, N)).sum(-1, keepdim=True)
-    ds = p * (dp - dterm)
+    ds = torch.where(p > 0, p * (dp - dterm), torch.zeros_like(p))                                   # a dead row's `out` is NaN
     refs = {"dq": (ds @ heads(k, M) * scale).transpose(1, 2).reshape(B, N, C),
             "dk": (ds.transpose(-1, -2) @ heads(q, N) * scale).transpose(1, 2).reshape(B, M, C),
-            "dv": (p.transpose(-1, -2) @ heads(dout, N)).transpose(1, 2).reshape(B, M, C),
-            "dbias": ds.reshape(B * H, N, M) if a["bias"] is not None and a["need_dbias"] else None}
+            "dv": (p.transpose(-1, -2) @ heads(dout, N)).transpose(1, 2).reshape(B, M, C)}
+    return refs, ds
+
+
+def _attn_grad_bound(ref):
+    return 2.0 ** -7 * ref.abs() + 2e-2 * ref.abs().max() + 1e-30
+
+
+def chk__relation_attention_backward(a, res):
+    refs, ds = _attention_backward64(a, a["bias"])
+    refs["dbias"] = ds.reshape(-1, *ds.shape[2:]) if a["bias"] is not None and a["need_dbias"] else None
     cmps = []
     for name, got in zip(("dq", "dk", "dv", "dbias"), res[:4]):
         ref = refs[name]
         if ref is not None:
-            cmps.append(Cmp(name, got, ref.reshape(got.shape), 2.0 ** -7 * ref.abs().reshape(got.shape) + 2e-2 * ref.abs().max() + 1e-30))
+            cmps.append(Cmp(name, got, ref.reshape(got.shape), _attn_grad_bound(ref.reshape(got.shape))))
     return cmps
 
 
@@ -635,6 +673,167 @@ HOST_ONLY = frozenset({
 })
 
 
+# ------------------------------------------------------------------------------ training entries outside ops.py
+TRAIN_MODULES = ("ffn_train", "ln_train", "attn_rel_train", "msda_train_hm")
+LN_EPS = 1e-5                    # add_layer_norm_backward takes no eps: every norm of the network keeps nn.LayerNorm's default
+TAU = 8e-3                       # |pre-activation relation bias| below which the bf16 sine features may switch the ReLU branch
+
+
+def train_functions(module) -> List[str]:
+    """Every module-level function defined in one of the training modules, as "module.function"."""
+    short = module.__name__.rsplit(".", 1)[-1]
+    return sorted(f"{short}.{n}" for n, f in vars(module).items() if inspect.isfunction(f) and f.__module__ == module.__name__)
+
+
+def _bf16_form(ref):
+    """2^-8 |ref| (one rounding to bf16 of the float64 value) + 1e-3 max(1, max |ref|): tests/test_gpu_ffn_train.py::within_bf16_form"""
+    return 2.0 ** -8 * ref.abs() + 1e-3 * max(1.0, float(ref.abs().max()) if ref.numel() else 1.0)
+
+
+def chk_ffn_k256_train(a, res):
+    out, hid = res
+    ref_h = _linear(a["x"], a["w1"], a["b1"]).relu()
+    return chk_ffn_k256(a, out) + [Cmp("hid", hid, ref_h, _bf16_form(ref_h))]
+
+
+def chk_ffn_k256_backward(a, res):
+    """dH against bf16(dy W2) where the handed hid > 0 and bit-zero elsewhere; dx = dH W1 from the dH the kernel RETURNED, so
+    that a one-ulp difference in dH against the reference's own dH is not summed F times into dx."""
+    dx, dh = res
+    live = a["hid"] > 0
+    ref_dh = a["dy"].to(BF16).double() @ _d(a["w2"])                    # the kernel reads dy in bf16
+    ref_dx = _d(dh) @ _d(a["w1"])
+    ref_dh = ref_dh * live
+    return [Cmp("dH", dh, ref_dh, torch.where(live, _bf16_form(ref_dh), torch.zeros_like(ref_dh))), Cmp("dx", dx, ref_dx, _bf16_form(ref_dx))]
+
+
+def _ln_stats64(x, residual, eps):
+    s = _d(x) if residual is None else _d(x) + _d(residual)
+    mean = s.mean(-1, keepdim=True)
+    rstd = (s.var(-1, unbiased=False, keepdim=True) + eps).rsqrt()
+    return s, mean, rstd
+
+
+def chk_add_layer_norm_train(a, res):
+    out, stats = res
+    _, mean, rstd = _ln_stats64(a["x"], a["residual"], a["eps"])
+    mean, rstd = mean.reshape(-1), rstd.reshape(-1)
+    return chk_add_layer_norm(dict(a, pos=None), out) + [
+        Cmp("mean", stats[:, 0], mean, 1e-5 * mean.abs().clamp_min(1.0)), Cmp("rstd", stats[:, 1], rstd, 1e-5 * rstd.abs().clamp_min(1.0))]
+
+
+def chk_add_layer_norm_backward(a, res):
+    """float64 LayerNorm backward of x + residual with the statistics recomputed in float64 (not the handed fp32 ones)."""
+    dx, dgamma, dbeta = res
+    x = a["x"]
+    s, mean, rstd = _ln_stats64(x, a["residual"], LN_EPS)
+    dy = a["dy"].to(x.dtype).double()                                   # the kernel reads dy in x's dtype
+    xhat = (s - mean) * rstd
+    g = dy * _d(a["weight"]).reshape(-1)
+    ref_dx = rstd * (g - g.mean(-1, keepdim=True) - xhat * (g * xhat).mean(-1, keepdim=True))
+    ref_dg, ref_db = (dy * xhat).reshape(-1, 256).sum(0), dy.reshape(-1, 256).sum(0)
+    rows = x.numel() // 256
+    if x.dtype == BF16:
+        bx, bg, bb = _bf16_form(ref_dx), _bf16_form(ref_dg), _bf16_form(ref_db)
+    else:
+        top = lambda r: max(1.0, float(r.abs().max()))                                               # noqa: E731
+        par = 1e-6 + 4 * 2.0 ** -24 * math.sqrt(rows)
+        bx, bg, bb = 1e-5 * top(ref_dx), par * top(ref_dg), par * top(ref_db)
+    cmps = [Cmp("dx", dx, ref_dx, bx)]
+    if a["need_params"]:
+        cmps += [Cmp("dgamma", dgamma.reshape(-1), ref_dg, bg), Cmp("dbeta", dbeta.reshape(-1), ref_db, bb)]
+    else:
+        assert dgamma is None and dbeta is None
+    return cmps
+
+
+def _relation_pre64(a):
+    """float64 pre-activation relation bias [B,H,N,M] and the sine features [B,N,M,4F] it is projected from."""
+    feat = torch_ref.sine_embed(torch_ref.box_rel_encoding(_d(a["src_boxes"]), _d(a["tgt_boxes"]), a["eps"]), a["num_pos_feats"],
+                                a["temperature"], a["rel_scale"])
+    H = a["num_heads"]
+    pre = torch.einsum("bnmc,hc->bhnm", feat, _d(a["proj_weight"]).reshape(H, -1))
+    if a["proj_bias"] is not None:
+        pre = pre + _d(a["proj_bias"]).view(1, H, 1, 1)
+    return pre, feat
+
+
+def _boxes_bias64(a):
+    return torch_ref.relation_bias(_d(a["src_boxes"]), _d(a["tgt_boxes"]), _d(a["proj_weight"]), _d(a["proj_bias"]),
+                                   a["num_pos_feats"], a["temperature"], a["rel_scale"])
+
+
+def chk__relation_attention_boxes_train(a, res):
+    ref, s = _attention(a["q"], a["k"], a["v"], a["num_heads"], _boxes_bias64(a), a["mask"], a["scale"])
+    lse = torch.logsumexp(s, -1).reshape(-1, s.shape[2])
+    return [_attn_cmp("out", res[0], ref), Cmp("lse", res[1].double() * math.log(2.0), lse, 1e-3)]
+
+
+def chk__relation_attention_boxes_backward(a, res):
+    """dq, dk, dv as chk__relation_attention_backward with the float64 bias; grad_weight / grad_bias through the float64 ReLU.
+    The kernels round the sine features to bf16, so a pair whose pre-activation bias lies within TAU of zero may take the other
+    ReLU branch (tests/test_gpu_attn_rel_train.py).  The harness cannot mask the kernel's operands, so those pairs are not
+    removed: the two parameter-gradient bounds get sum |dS_ref| |feature| over exactly those pairs, which caps what a switched
+    branch can change.  The pairs must be at most 25 % of all and no complete row, or the call is recorded as failing."""
+    refs, ds = _attention_backward64(a, _boxes_bias64(a))
+    pre, feat = _relation_pre64(a)
+    H = a["num_heads"]
+    active, kink = pre > 0, pre.abs() < TAU
+    gw = torch.einsum("bhnm,bnmc->hc", ds * active, feat)
+    gb = (ds * active).sum(dim=(0, 2, 3))
+    allow_w = torch.einsum("bhnm,bnmc->hc", ds.abs() * kink, feat.abs())
+    allow_b = (ds.abs() * kink).sum(dim=(0, 2, 3))
+    pairs = kink.any(0).any(0)                                                                        # [N, M]
+    share = pairs.double().mean().reshape(1)
+    full_rows = pairs.all(1).sum().double().reshape(1)
+    cmps = [Cmp(n, got, refs[n].reshape(got.shape), _attn_grad_bound(refs[n].reshape(got.shape))) for n, got in zip(("dq", "dk", "dv"), res[:3])]
+    cmps.append(Cmp("grad_weight", res[3].reshape(H, -1), gw, _attn_grad_bound(gw) + allow_w))
+    if res[4] is not None:
+        cmps.append(Cmp("grad_bias", res[4].reshape(-1), gb, _attn_grad_bound(gb) + allow_b))
+    cmps += [Cmp("kink_pair_share", share, torch.zeros_like(share), 0.25, gate=True),
+             Cmp("kink_complete_rows", full_rows, torch.zeros_like(full_rows), gate=True)]
+    return cmps
+
+
+def chk_ms_deform_attn_backward_fused_hm(a, res):
+    """chk_ms_deform_attn_backward_fused on the [B,S,H,D] permutation of the value, grad_value permuted back: the module documents
+    the other gradients as the bits of that entry."""
+    b = dict(value=a["value_hm"].permute(0, 2, 1, 3).contiguous(), spatial_shapes=a["spatial_shapes"], sampling_offsets=a["sampling_offsets"],
+             attn_logits=a["attn_logits"], reference_points=a["reference_points"], grad_output=a["grad_output"])
+    return chk_ms_deform_attn_backward_fused(b, [res[0].permute(0, 2, 1, 3).contiguous(), res[1], res[2], res[3]])
+
+
+def chk_grad_value_from_head_major(a, res):
+    g = a["grad_hm"]
+    B, _, S, _ = g.shape
+    ref = g.permute(0, 2, 1, 3).reshape(B, S, 256).to(BF16)
+    if a["key_padding_mask"] is not None:
+        ref = ref.masked_fill(a["key_padding_mask"].bool()[..., None], 0)
+    return [Cmp("out", res, ref)]
+
+
+TRAIN_ENTRIES: Dict[str, Callable] = {
+    "ffn_train.ffn_k256_train": chk_ffn_k256_train,
+    "ffn_train.ffn_k256_backward": chk_ffn_k256_backward,
+    "ln_train.add_layer_norm_train": chk_add_layer_norm_train,
+    "ln_train.add_layer_norm_backward": chk_add_layer_norm_backward,
+    "attn_rel_train._relation_attention_boxes_train": chk__relation_attention_boxes_train,
+    "attn_rel_train._relation_attention_boxes_backward": chk__relation_attention_boxes_backward,
+    "msda_train_hm.ms_deform_attn_backward_fused_hm": chk_ms_deform_attn_backward_fused_hm,
+    "msda_train_hm.grad_value_from_head_major": chk_grad_value_from_head_major,
+}
+
+# the rest of the four modules: routing predicates and argument helpers that launch nothing; ffn_train._pack, which launches a
+# re-layout only from inside a checked entry (as the ops packers); and the two public natural-log wrappers of attn_rel_train,
+# whose one launch is the checked private entry
+TRAIN_HOST_ONLY = frozenset({
+    "ffn_train.ffn_train_supported", "ffn_train._pack", "ffn_train._aligned_rows",
+    "ln_train._aligned", "ln_train._rows", "ln_train.add_layer_norm_train_supported", "ln_train._param", "ln_train._entry",
+    "attn_rel_train._f32", "attn_rel_train.relation_attention_boxes_train", "attn_rel_train.relation_attention_boxes_backward",
+    "msda_train_hm._merged_slices", "msda_train_hm.split_merged_projection",
+})
+
+
 # ----------------------------------------------------------------------------------------------------------------- harness
 def _copy(x):
     if torch.is_tensor(x):
@@ -645,10 +844,13 @@ def _copy(x):
 
 
 class Shadow:
-    """``Shadow(monkeypatch, fault=None)``; ``fault(name, call, bound_args, result, rerun) -> result`` may replace a kernel's
-    result before the check (the harness's own fault-injection test)."""
+    """``Shadow(monkeypatch, fault=None, check=True)``; ``fault(name, call, bound_args, result, rerun) -> result`` may replace a
+    kernel's result before the check (the harness's own fault-injection test).  ``check=False`` installs only the counting
+    tripwires at the C boundary (``launches``): no wrapper, no reference, no error for a launch outside an entry."""
 
-    def __init__(self, monkeypatch, fault: Optional[Callable] = None):
+    def __init__(self, monkeypatch, fault: Optional[Callable] = None, check: bool = True):
+        import importlib
+
         from relation_detr_amd import _lib, ops
         self.records: List[Record] = []
         self.calls: collections.Counter = collections.Counter()
@@ -657,11 +859,16 @@ class Shadow:
         self.launches: collections.Counter = collections.Counter()
         self.depth = 0
         self.fault = fault
-        for name in ops_functions(ops):
-            if name in HOST_ONLY:
+        self.check = check
+        targets = [(ops, name, name, KERNEL_ENTRIES, HOST_ONLY) for name in ops_functions(ops)]
+        for short in TRAIN_MODULES:
+            module = importlib.import_module(f"relation_detr_amd.{short}")
+            targets += [(module, key.split(".", 1)[1], key, TRAIN_ENTRIES, TRAIN_HOST_ONLY) for key in train_functions(module)]
+        for module, attr, key, entries, host_only in targets if check else ():
+            if key in host_only:
                 continue
-            fn = getattr(ops, name)
-            monkeypatch.setattr(ops, name, self._checked(name, fn) if name in KERNEL_ENTRIES else self._unclassified(name, fn))
+            fn = getattr(module, attr)
+            monkeypatch.setattr(module, attr, self._checked(key, fn, entries[key]) if key in entries else self._unclassified(key, fn))
         lib = _lib.load()
         for sym in launching_symbols(_lib.SIGNATURES):
             monkeypatch.setattr(lib, sym, self._tripwire(sym, getattr(lib, sym)))
@@ -669,7 +876,7 @@ class Shadow:
     def _tripwire(self, sym, fn):
         def wrapper(*args):
             self.launches[sym] += 1
-            if self.depth <= 0:
+            if self.check and self.depth <= 0:
                 self.errors.append(f"{sym} launched outside any checked ops entry")
             return fn(*args)
         return wrapper
@@ -680,9 +887,8 @@ class Shadow:
             return fn(*args, **kwargs)
         return wrapper
 
-    def _checked(self, name, fn):
+    def _checked(self, name, fn, checker):
         sig = inspect.signature(fn)
-        checker = KERNEL_ENTRIES[name]
 
         def wrapper(*args, **kwargs):
             call = self.calls[name]
@@ -697,8 +903,15 @@ class Shadow:
                     result = self.fault(name, call, bound.arguments, result, fn)
             finally:
                 self.depth -= 1
-            with torch.no_grad():
-                self._record(name, call, checker(copies, result))
+            # the references are torch's own float64 operators, some of which have no deterministic variant (grid_sample's
+            # backward): a step run under torch.use_deterministic_algorithms(True) is for the kernels, not for them
+            strict, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
+            torch.use_deterministic_algorithms(False)
+            try:
+                with torch.no_grad():
+                    self._record(name, call, checker(copies, result))
+            finally:
+                torch.use_deterministic_algorithms(strict, warn_only=warn)
             return result
         return wrapper
 
@@ -708,7 +921,7 @@ class Shadow:
             r, f, n, w = _compare(c)
             failing += f
             checked += n
-            if r >= worst:
+            if r >= worst and (f or not c.gate):
                 worst, where = r, w
         self.checked[name] += checked
         self.records.append(Record(name, call, worst, failing, checked, where))

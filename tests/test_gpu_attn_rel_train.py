@@ -16,7 +16,6 @@ this removes at most 25 % of the pairs and no complete row.  The all-active test
 Bounds: dq, dk, dv, grad_weight, grad_bias each |err| <= 2^-7 |ref| + 2e-2 max|ref| per element; dq, dk, dv normwise within
 1.25 x the old route's error + 1e-3 (old route = _RelationBiasFunction + RelationAttentionFunction on the same inputs);
 grad_weight / grad_bias normwise <= 1e-2 against float64 (five times the 2e-3 the simulation gives for the bf16 features alone).
-The shadow harness (tests/shadow.py) does not know these entry points; this file carries the float64 checks itself.
 """
 import math
 
