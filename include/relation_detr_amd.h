@@ -501,6 +501,21 @@ int rdetr_add_layernorm_backward_bf16(const uint16_t *dy, long long lddy, const 
                                       long long rows, int C, void *workspace, long long workspace_bytes, uint16_t *dx,
                                       uint16_t *dgamma, uint16_t *dbeta, void *stream);
 
+/* Mixed-precision training forms (bf16 autocast over fp32 parameters), C = 256 only: x and residual (nullable) are each fp32
+ * (x_is_bf16 / r_is_bf16 = 0) or bf16 (1), rows ldx / ldr elements of their own type apart; gamma, beta, out (rows ldo apart), dy,
+ * stats, dgamma and dbeta are fp32.  The sum x + residual is formed in fp32 and never stored; the arithmetic is that of the
+ * same-dtype forms.  ..._backward_mixed writes dx [rows, 256] fp32 (contiguous) and, in the same pass, dx_bf16 [rows, 256]: the same
+ * values rounded to bf16 (RNE) -- each operand's gradient in its own type.  dx_bf16 may be null only when no operand is bf16, dx
+ * only when none is fp32 (RDETR_ERR_INVALID_ARG otherwise).  Workspace, the parameter-gradient reduction, its null form and the
+ * 16-byte rules are those of rdetr_add_layernorm_backward_f32. */
+int rdetr_add_layernorm_train_mixed(const void *x, int x_is_bf16, long long ldx, const void *residual, int r_is_bf16, long long ldr,
+                                    const float *gamma, const float *beta, long long rows, int C, float eps, float *out,
+                                    long long ldo, float *stats, void *stream);
+int rdetr_add_layernorm_backward_mixed(const float *dy, long long lddy, const void *x, int x_is_bf16, long long ldx,
+                                       const void *residual, int r_is_bf16, long long ldr, const float *gamma, const float *stats,
+                                       long long rows, int C, void *workspace, long long workspace_bytes, float *dx,
+                                       uint16_t *dx_bf16, float *dgamma, float *dbeta, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Fused elementwise steps of the decoder's box bookkeeping (each replaces ~8 torch launches on a [B,N,4] tensor).
  *   rdetr_box_refine_f32   out = sigmoid(delta + inverse_sigmoid(ref)),  inverse_sigmoid as util/misc.py:31-35 (eps 1e-3);
@@ -694,6 +709,27 @@ int rdetr_ffn_k256_train_bf16(const uint16_t *x, long long ldx, const uint16_t *
                               long long M, int F, uint16_t *out, long long ldo, uint16_t *hid, long long ldh, void *stream);
 int rdetr_ffn_k256_backward_bf16(const uint16_t *dy, long long lddy, const uint16_t *packed_t, const uint16_t *hid, long long ldh,
                                  long long M, int F, uint16_t *dh, long long ldd, uint16_t *dx, long long lddx, void *stream);
+/* The training route with fp32 at either end of the block (bf16 autocast over fp32 parameters and an fp32 residual stream).
+ *   rdetr_ffn_k256_pack_f32             rdetr_ffn_k256_pack_bf16 from fp32 matrices given by element strides (row, column; >= 1),
+ *                                       rounded to bf16 (RNE) on the way: w1 is read as [F, 256], w2 as [256, F].  With the strides
+ *                                       exchanged the backward's (w2^T, w1^T) are read in place.  b1 [F], b2 [256] (fp32, contiguous)
+ *                                       are rounded into biases_bf16 [F + 256] = (b1, b2); the three are given together or not at all.
+ *   rdetr_ffn_k256_train_xf32_bf16      rdetr_ffn_k256_train_bf16 on fp32 rows x (ldx a multiple of 4): they are rounded to bf16 (RNE)
+ *                                       as they are loaded and the rounded rows also stored as xlp [M, 256] bf16 (rows ldxl apart, a
+ *                                       multiple of 8) -- out and hid have the bits of rdetr_ffn_k256_train_bf16 on xlp.
+ *   rdetr_ffn_k256_backward_dxf32_bf16  rdetr_ffn_k256_backward_bf16 whose dx [M, 256] (rows lddx apart, a multiple of 4) is the fp32
+ *                                       sum over all of F, not rounded; dh as there.
+ * Every base is 16-byte aligned (the fp32 weights and biases of the pack: 4-byte); the limits on F, M * ldh and M * ldd and the
+ * status conventions are those of the bf16 entries. */
+int rdetr_ffn_k256_pack_f32(const float *w1, long long w1_row_stride, long long w1_col_stride, const float *w2,
+                            long long w2_row_stride, long long w2_col_stride, const float *b1, const float *b2, int F,
+                            uint16_t *packed, uint16_t *biases_bf16, void *stream);
+int rdetr_ffn_k256_train_xf32_bf16(const float *x, long long ldx, const uint16_t *packed, const uint16_t *b1, const uint16_t *b2,
+                                   long long M, int F, uint16_t *out, long long ldo, uint16_t *hid, long long ldh, uint16_t *xlp,
+                                   long long ldxl, void *stream);
+int rdetr_ffn_k256_backward_dxf32_bf16(const uint16_t *dy, long long lddy, const uint16_t *packed_t, const uint16_t *hid,
+                                       long long ldh, long long M, int F, uint16_t *dh, long long ldd, float *dx, long long lddx,
+                                       void *stream);
 
 #ifdef __cplusplus
 }

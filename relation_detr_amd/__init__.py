@@ -13,6 +13,7 @@ from .ops import (MultiScaleDeformableAttnFunction, MultiScaleDeformableAttnFuse
 from .attn_rel_train import RelationAttentionBoxesFunction, relation_attention_boxes_backward, relation_attention_boxes_train
 from .ffn_train import FeedForwardFunction, ffn_k256_backward, ffn_k256_train
 from .ln_train import AddLayerNormFunction
+from .amp_train import AddLayerNormMixedFunction, FeedForwardMixedFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
 
 __all__ = [
@@ -24,4 +25,5 @@ __all__ = [
     "RelationAttentionBoxesFunction", "relation_attention_boxes_train", "relation_attention_boxes_backward",
     "FeedForwardFunction", "ffn_k256_train", "ffn_k256_backward", "AddLayerNormFunction",
     "MultiScaleDeformableAttnHeadMajorFunction", "ms_deform_attn_backward_fused_hm", "grad_value_from_head_major",
+    "AddLayerNormMixedFunction", "FeedForwardMixedFunction",
 ]

@@ -82,6 +82,9 @@ SIGNATURES = {
     "rdetr_ffn_ln_k256_bf16": [_vp, _c_ll, _vp, _vp, _vp, _vp, _vp, _c_float, _vp, _c_ll, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp],
     "rdetr_ffn_k256_train_bf16": [_vp, _c_ll, _vp, _vp, _vp, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp],
     "rdetr_ffn_k256_backward_bf16": [_vp, _c_ll, _vp, _vp, _c_ll, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp],
+    "rdetr_ffn_k256_pack_f32": [_vp, _c_ll, _c_ll, _vp, _c_ll, _c_ll, _vp, _vp, _c_int, _vp, _vp, _vp],
+    "rdetr_ffn_k256_train_xf32_bf16": [_vp, _c_ll, _vp, _vp, _vp, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp, _c_ll, _vp],
+    "rdetr_ffn_k256_backward_dxf32_bf16": [_vp, _c_ll, _vp, _vp, _c_ll, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp],
     "rdetr_nchw_to_tokens": [_vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp],
     "rdetr_nchw_levels_to_tokens": [_vp, _vp, _vp, _c_int, _c_int, _c_int, _c_int, _c_ll, _c_ll, _vp, _vp],
     "rdetr_add_layernorm_f32": [_vp] * 4 + [_c_ll, _c_int, _c_float, _vp, _vp],
@@ -95,6 +98,9 @@ SIGNATURES = {
     "rdetr_add_layernorm_backward_workspace_bytes": [_c_ll],
     "rdetr_add_layernorm_backward_f32": [_vp, _c_ll] * 3 + [_vp, _vp, _c_ll, _c_int, _vp, _c_ll] + [_vp] * 4,
     "rdetr_add_layernorm_backward_bf16": [_vp, _c_ll] * 3 + [_vp, _vp, _c_ll, _c_int, _vp, _c_ll] + [_vp] * 4,
+    "rdetr_add_layernorm_train_mixed": [_vp, _c_int, _c_ll, _vp, _c_int, _c_ll, _vp, _vp, _c_ll, _c_int, _c_float, _vp, _c_ll, _vp, _vp],
+    "rdetr_add_layernorm_backward_mixed": [_vp, _c_ll, _vp, _c_int, _c_ll, _vp, _c_int, _c_ll, _vp, _vp, _c_ll, _c_int, _vp, _c_ll]
+                                          + [_vp] * 5,
 }
 
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3            # rdetr_status (include/relation_detr_amd.h)

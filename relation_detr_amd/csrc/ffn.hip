@@ -75,8 +75,11 @@ __global__ __launch_bounds__(kFfnThreads) void ffn_k256_kernel(const uint16_t *_
                                                                uint16_t *__restrict__ out2, long long ldo2)
 {
     constexpr int MODE = kFfnInfer;
-    uint16_t *const hid = nullptr, *const dhid = nullptr;
-    constexpr long long ldh = 0, ldd = 0;
+    constexpr bool XF32 = false, DXF32 = false;
+    uint16_t *const hid = nullptr, *const dhid = nullptr, *const xlp = nullptr;
+    constexpr long long ldh = 0, ldd = 0, ldxl = 0;
+    const float *const xf = nullptr;
+    float *const outf = nullptr;
 #include "ffn_k256_body.h"
 }
 
@@ -95,6 +98,35 @@ __global__ __launch_bounds__(kFfnThreads) __attribute__((amdgpu_waves_per_eu(2, 
     constexpr long long ldp = 0, ldo2 = 0;
     const uint16_t *const gamma = nullptr, *const beta = nullptr, *const pos = nullptr;
     uint16_t *const out2 = nullptr;
+    constexpr bool XF32 = false, DXF32 = false;
+    uint16_t *const xlp = nullptr;
+    constexpr long long ldxl = 0;
+    const float *const xf = nullptr;
+    float *const outf = nullptr;
+#include "ffn_k256_body.h"
+}
+
+// The training kernels with fp32 at one end of the block (bf16 autocast over an fp32 residual stream).  MODE = kFfnTrain: the rows
+// are read as fp32 (xin), rounded to bf16 on the way into the registers and stored as xlp [M, 256]; from there on the kernel above,
+// so out and hid have its bits on the rounded x.  MODE = kFfnBwd: dX leaves as the unrounded fp32 accumulators (outp); dH as above.
+template <int MODE>
+__global__ __launch_bounds__(kFfnThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void ffn_k256_train_f32_kernel(const void *__restrict__ xin, long long ldx,
+                                                                     const uint16_t *__restrict__ packed, const uint16_t *__restrict__ b1,
+                                                                     const uint16_t *__restrict__ b2, long long M, int F,
+                                                                     void *__restrict__ outp, long long ldo, uint16_t *hid, long long ldh,
+                                                                     uint16_t *dhid, long long ldd, uint16_t *__restrict__ xlp, long long ldxl)
+{
+    constexpr bool LN = false;
+    [[maybe_unused]] constexpr int dbg_arg = 0;
+    constexpr float eps = 0.f;
+    constexpr long long ldp = 0, ldo2 = 0;
+    const uint16_t *const gamma = nullptr, *const beta = nullptr, *const pos = nullptr;
+    uint16_t *const out2 = nullptr;
+    constexpr bool XF32 = MODE == kFfnTrain, DXF32 = MODE == kFfnBwd;
+    const uint16_t *const x = static_cast<const uint16_t *>(xin);
+    const float *const xf = static_cast<const float *>(xin);
+    uint16_t *const out = static_cast<uint16_t *>(outp);
+    float *const outf = static_cast<float *>(outp);
 #include "ffn_k256_body.h"
 }
 
@@ -114,6 +146,61 @@ __global__ __launch_bounds__(256) void ffn_pack_kernel(const uint16_t *__restric
     packed[idx] = *reinterpret_cast<const u32x4 *>(src);
 }
 
+// The same fragment order from fp32 weights read through element strides (rows, columns), rounded to bf16 (RNE) on the way: the
+// forward's (w1, w2) as they lie, and the backward's (w2^T, w1^T) read in place -- no bf16 copies, no transposes.
+//   workgroup (c, half)  one chunk's 64 x 256 slice of W1 (half 0) or 256 x 64 slice of W2 (half 1), through LDS:
+//   load    consecutive threads walk the dimension whose stride is smaller (`row_fast`: a transposed view), so a wave reads whole
+//           256-byte runs either way; rows that are contiguous, 16-byte aligned floats (`vec`) take 16-byte loads.  The values are
+//           rounded here and kept as bf16 [rows][cols + 2]: an odd number of banks per row, whichever way the tile is written
+//   store   a thread gathers its 16-byte pieces (8 consecutive columns of one row) from LDS: the stores stay the 1-KiB fragments
+// The workgroups behind the last chunk round the biases: dst[0 .. F) = b1, dst[F .. F + 256) = b2.
+constexpr int kFfnPackLd1 = kFfnK + 2, kFfnPackLd2 = kFfnHC + 2;           // bf16 elements per LDS row of the W1 / W2 tile
+
+__global__ __launch_bounds__(256) void ffn_pack_f32_kernel(const float *__restrict__ w1, long long rs1, long long cs1, int mode1,
+                                                           const float *__restrict__ w2, long long rs2, long long cs2, int mode2,
+                                                           const float *__restrict__ b1, const float *__restrict__ b2, int F,
+                                                           u32x4 *__restrict__ packed, uint16_t *__restrict__ biases)
+{
+    __shared__ __attribute__((aligned(16))) uint16_t tile[kFfnK * kFfnPackLd2];            // >= 64 * kFfnPackLd1
+    static_assert(kFfnK * kFfnPackLd2 >= kFfnHC * kFfnPackLd1, "one LDS tile serves both halves");
+    const int t = threadIdx.x, nchunks = F / kFfnHC;
+    if ((int)blockIdx.x >= 2 * nchunks) {
+        const int i = ((int)blockIdx.x - 2 * nchunks) * 256 + t;
+        if (biases && i < F + kFfnK) biases[i] = (uint16_t)f32_to_bf16_bits(i < F ? b1[i] : b2[i - F]);
+        return;
+    }
+    const int c = blockIdx.x >> 1, half = blockIdx.x & 1;
+    // the tile: `rows` x `cols` elements from (row0, col0) of the matrix; cols = 1 << lc, rows = 1 << lr
+    const float *src = half ? w2 + (long long)c * kFfnHC * cs2 : w1 + (long long)c * kFfnHC * rs1;
+    const long long rs = half ? rs2 : rs1, cs = half ? cs2 : cs1;
+    const int mode = half ? mode2 : mode1, lc = half ? 6 : 8, lr = half ? 8 : 6, ld = half ? kFfnPackLd2 : kFfnPackLd1;
+    if (mode == 2) {                                                      // contiguous, aligned rows: 16-byte loads
+#pragma unroll 4
+        for (int i = 0; i < 16; ++i) {
+            const int e = i * 256 + t, row = e >> (lc - 2), col = (e & ((1 << (lc - 2)) - 1)) * 4;
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(src + row * rs + col);
+            unsigned *q = reinterpret_cast<unsigned *>(&tile[row * ld + col]);             // 4-byte aligned only: two stores
+            q[0] = pack_bf16x2(v.x, v.y);
+            q[1] = pack_bf16x2(v.z, v.w);
+        }
+    } else {
+#pragma unroll 8
+        for (int i = 0; i < 64; ++i) {
+            const int e = i * 256 + t;
+            const int row = mode == 1 ? e & ((1 << lr) - 1) : e >> lc, col = mode == 1 ? e >> lr : e & ((1 << lc) - 1);
+            tile[row * ld + col] = (uint16_t)f32_to_bf16_bits(src[row * rs + col * cs]);
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int p = j * 256 + t, f = p >> 6, l = p & 63, m = l & 15, kb = l >> 4;          // fragment f of this half, lane l
+        const int row = half ? ffn_index(f >> 1, m) : ffn_index(f >> 3, m), col = half ? 32 * (f & 1) + 8 * kb : 32 * (f & 7) + 8 * kb;
+        const unsigned *q = reinterpret_cast<const unsigned *>(&tile[row * ld + col]);     // 4-byte aligned: ld and col are even
+        packed[(size_t)c * 4096 + half * 2048 + p] = u32x4{q[0], q[1], q[2], q[3]};
+    }
+}
+
 }  // namespace rdetr
 
 using namespace rdetr;
@@ -128,6 +215,32 @@ extern "C" int rdetr_ffn_k256_pack_bf16(const uint16_t *w1, const uint16_t *w2, 
     const int total = (F / kFfnHC) * 64 * 64;
     hipLaunchKernelGGL(ffn_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w1, w2, F,
                        reinterpret_cast<u32x4 *>(packed));
+    return launch_status();
+}
+
+// packed <- fp32 (w1 [F, 256], w2 [256, F]) given by element strides (row, column), rounded to bf16: the bits of
+// rdetr_ffn_k256_pack_bf16 on the rounded, contiguous matrices.  b1 [F], b2 [256] (fp32, contiguous) -> biases_bf16 [F + 256]
+// = (b1, b2); the three are given together or not at all.
+extern "C" int rdetr_ffn_k256_pack_f32(const float *w1, long long w1_row_stride, long long w1_col_stride, const float *w2,
+                                       long long w2_row_stride, long long w2_col_stride, const float *b1, const float *b2, int F,
+                                       uint16_t *packed, uint16_t *biases_bf16, void *stream)
+{
+    if (F <= 0 || w1_row_stride < 1 || w1_col_stride < 1 || w2_row_stride < 1 || w2_col_stride < 1) return RDETR_ERR_INVALID_ARG;
+    if ((F % kFfnHC) || F > 4096) return RDETR_ERR_UNSUPPORTED;
+    if (!w1 || !w2 || !packed) return RDETR_ERR_INVALID_ARG;
+    if ((b1 != nullptr) != (b2 != nullptr) || (b1 != nullptr) != (biases_bf16 != nullptr)) return RDETR_ERR_INVALID_ARG;
+    if ((reinterpret_cast<uintptr_t>(packed) & 15) || ((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) & 3) ||
+        (b1 && ((reinterpret_cast<uintptr_t>(b1) | reinterpret_cast<uintptr_t>(b2)) & 3)) || (reinterpret_cast<uintptr_t>(biases_bf16) & 1))
+        return RDETR_ERR_UNSUPPORTED;
+    // how a tile is walked: 2 = rows of contiguous 16-byte aligned floats, 1 = down the columns (a transposed view), 0 = along the rows
+    auto mode = [](const float *w, long long rs, long long cs) {
+        if (cs == 1 && reinterpret_cast<uintptr_t>(w) % 16 == 0 && rs % 4 == 0) return 2;
+        return rs < cs ? 1 : 0;
+    };
+    const int blocks = 2 * (F / kFfnHC) + (biases_bf16 ? (F + kFfnK + 255) / 256 : 0);
+    hipLaunchKernelGGL(ffn_pack_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), w1, w1_row_stride,
+                       w1_col_stride, mode(w1, w1_row_stride, w1_col_stride), w2, w2_row_stride, w2_col_stride,
+                       mode(w2, w2_row_stride, w2_col_stride), b1, b2, F, reinterpret_cast<u32x4 *>(packed), biases_bf16);
     return launch_status();
 }
 
@@ -191,34 +304,50 @@ extern "C" int rdetr_ffn_ln_k256_bf16(const uint16_t *x, long long ldx, const ui
     return ffn_launch(x, ldx, packed, b1, b2, M, F, out, ldo, gamma, beta, eps, pos, ldp, out2, ldo2, stream);
 }
 
-// Shared argument checks and launch of the two training kernels (the status conventions of ffn_launch: refusal before any HIP call)
-static int ffn_train_launch(bool bwd, const uint16_t *x, long long ldx, const uint16_t *packed, const uint16_t *b1, const uint16_t *b2,
-                            long long M, int F, uint16_t *out, long long ldo, uint16_t *hid, long long ldh, uint16_t *dhid,
-                            long long ldd, void *stream)
+// Shared argument checks and launch of the training kernels (the status conventions of ffn_launch: refusal before any HIP call).
+// f32: the forward reads fp32 x and also writes xlp; the backward writes fp32 dx (`out`) -- ld in elements of the respective type
+static int ffn_train_launch(bool bwd, bool f32, const void *x, long long ldx, const uint16_t *packed, const uint16_t *b1, const uint16_t *b2,
+                            long long M, int F, void *out, long long ldo, uint16_t *hid, long long ldh, uint16_t *dhid,
+                            long long ldd, uint16_t *xlp, long long ldxl, void *stream)
 {
-    if (M < 0 || F <= 0 || ldx < kFfnK || ldo < kFfnK || ldh < F || (bwd && ldd < F)) return RDETR_ERR_INVALID_ARG;
-    if ((F % kFfnHC) || F > 4096 || (ldx & 7) || (ldo & 7) || (ldh & 7) || (bwd && (ldd & 7))) return RDETR_ERR_UNSUPPORTED;
+    const bool xf32 = f32 && !bwd, of32 = f32 && bwd;
+    if (M < 0 || F <= 0 || ldx < kFfnK || ldo < kFfnK || ldh < F || (bwd && ldd < F) || (xf32 && ldxl < kFfnK)) return RDETR_ERR_INVALID_ARG;
+    if ((F % kFfnHC) || F > 4096 || (ldx & (xf32 ? 3 : 7)) || (ldo & (of32 ? 3 : 7)) || (ldh & 7) || (bwd && (ldd & 7)) || (xf32 && (ldxl & 7)))
+        return RDETR_ERR_UNSUPPORTED;
     if (M == 0) return RDETR_OK;
-    if (!x || !packed || !out || !hid || (bwd ? !dhid : (!b1 || !b2))) return RDETR_ERR_INVALID_ARG;
+    if (!x || !packed || !out || !hid || (bwd ? !dhid : (!b1 || !b2)) || (xf32 && !xlp)) return RDETR_ERR_INVALID_ARG;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(out) |
-         reinterpret_cast<uintptr_t>(hid) | reinterpret_cast<uintptr_t>(dhid)) & 15)
+         reinterpret_cast<uintptr_t>(hid) | reinterpret_cast<uintptr_t>(dhid) | reinterpret_cast<uintptr_t>(xlp)) & 15)
         return RDETR_ERR_UNSUPPORTED;
     // H / dH are addressed with 32-bit byte offsets whose top bit marks "no such row" (kFfnNoRow)
     if (M * ldh * 2 > 0x7fffffffLL || (bwd && M * ldd * 2 > 0x7fffffffLL)) return RDETR_ERR_UNSUPPORTED;
     const int lds = 2 * kFfnBufBytes + (F + 3 * kFfnK) * 4;
+    constexpr int max_lds = 2 * kFfnBufBytes + (4096 + 3 * kFfnK) * 4;
     static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_kernel<kFfnTrain>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kFfnBufBytes + (4096 + 3 * kFfnK) * 4);
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
     static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_kernel<kFfnBwd>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kFfnBufBytes + (4096 + 3 * kFfnK) * 4);
-    if (attr0 != hipSuccess || attr1 != hipSuccess) return RDETR_ERR_LAUNCH;
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    static const hipError_t attr2 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_f32_kernel<kFfnTrain>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    static const hipError_t attr3 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_f32_kernel<kFfnBwd>),
+                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    if (attr0 != hipSuccess || attr1 != hipSuccess || attr2 != hipSuccess || attr3 != hipSuccess) return RDETR_ERR_LAUNCH;
     const long long ntiles = (M + kFfnWaves * kFfnRows - 1) / (kFfnWaves * kFfnRows);
     const long long gx = ntiles < 256 ? ntiles : 256;
-    if (bwd)
-        hipLaunchKernelGGL(ffn_k256_train_kernel<kFfnBwd>, dim3((unsigned)gx), dim3(kFfnThreads), (size_t)lds, static_cast<hipStream_t>(stream),
-                           x, ldx, packed, b1, b2, M, F, out, ldo, hid, ldh, dhid, ldd);
+    const dim3 grid((unsigned)gx), block(kFfnThreads);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint16_t *xb = static_cast<const uint16_t *>(x);
+    uint16_t *ob = static_cast<uint16_t *>(out);
+    if (f32 && bwd)
+        hipLaunchKernelGGL(ffn_k256_train_f32_kernel<kFfnBwd>, grid, block, (size_t)lds, s, x, ldx, packed, b1, b2, M, F, out, ldo, hid, ldh,
+                           dhid, ldd, xlp, ldxl);
+    else if (f32)
+        hipLaunchKernelGGL(ffn_k256_train_f32_kernel<kFfnTrain>, grid, block, (size_t)lds, s, x, ldx, packed, b1, b2, M, F, out, ldo, hid, ldh,
+                           dhid, ldd, xlp, ldxl);
+    else if (bwd)
+        hipLaunchKernelGGL(ffn_k256_train_kernel<kFfnBwd>, grid, block, (size_t)lds, s, xb, ldx, packed, b1, b2, M, F, ob, ldo, hid, ldh, dhid, ldd);
     else
-        hipLaunchKernelGGL(ffn_k256_train_kernel<kFfnTrain>, dim3((unsigned)gx), dim3(kFfnThreads), (size_t)lds, static_cast<hipStream_t>(stream),
-                           x, ldx, packed, b1, b2, M, F, out, ldo, hid, ldh, dhid, ldd);
+        hipLaunchKernelGGL(ffn_k256_train_kernel<kFfnTrain>, grid, block, (size_t)lds, s, xb, ldx, packed, b1, b2, M, F, ob, ldo, hid, ldh, dhid, ldd);
     return launch_status();
 }
 
@@ -227,7 +356,7 @@ static int ffn_train_launch(bool bwd, const uint16_t *x, long long ldx, const ui
 extern "C" int rdetr_ffn_k256_train_bf16(const uint16_t *x, long long ldx, const uint16_t *packed, const uint16_t *b1, const uint16_t *b2,
                                          long long M, int F, uint16_t *out, long long ldo, uint16_t *hid, long long ldh, void *stream)
 {
-    return ffn_train_launch(false, x, ldx, packed, b1, b2, M, F, out, ldo, hid, ldh, nullptr, 0, stream);
+    return ffn_train_launch(false, false, x, ldx, packed, b1, b2, M, F, out, ldo, hid, ldh, nullptr, 0, nullptr, 0, stream);
 }
 
 // Data gradient of the block: dh[M, F] = bf16(dy w2) where hid > 0, else 0;  dx[M, 256] = dh w1 (fp32 over all of F, rounded once).
@@ -236,5 +365,23 @@ extern "C" int rdetr_ffn_k256_backward_bf16(const uint16_t *dy, long long lddy, 
                                             long long ldh, long long M, int F, uint16_t *dh, long long ldd, uint16_t *dx, long long lddx,
                                             void *stream)
 {
-    return ffn_train_launch(true, dy, lddy, packed_t, nullptr, nullptr, M, F, dx, lddx, const_cast<uint16_t *>(hid), ldh, dh, ldd, stream);
+    return ffn_train_launch(true, false, dy, lddy, packed_t, nullptr, nullptr, M, F, dx, lddx, const_cast<uint16_t *>(hid), ldh, dh, ldd, nullptr, 0, stream);
+}
+
+// rdetr_ffn_k256_train_bf16 for fp32 rows x [M, 256] (ldx % 4 == 0): they are rounded to bf16 (RNE) as they are loaded, and the
+// rounded rows are also stored as xlp [M, 256] bf16 (ldxl % 8 == 0) -- out and hid have the bits of rdetr_ffn_k256_train_bf16 on xlp.
+extern "C" int rdetr_ffn_k256_train_xf32_bf16(const float *x, long long ldx, const uint16_t *packed, const uint16_t *b1, const uint16_t *b2,
+                                              long long M, int F, uint16_t *out, long long ldo, uint16_t *hid, long long ldh, uint16_t *xlp,
+                                              long long ldxl, void *stream)
+{
+    return ffn_train_launch(false, true, x, ldx, packed, b1, b2, M, F, out, ldo, hid, ldh, nullptr, 0, xlp, ldxl, stream);
+}
+
+// rdetr_ffn_k256_backward_bf16 whose dx [M, 256] (lddx % 4 == 0) is the fp32 sum over all of F, not rounded; dh as there.
+extern "C" int rdetr_ffn_k256_backward_dxf32_bf16(const uint16_t *dy, long long lddy, const uint16_t *packed_t, const uint16_t *hid,
+                                                  long long ldh, long long M, int F, uint16_t *dh, long long ldd, float *dx, long long lddx,
+                                                  void *stream)
+{
+    return ffn_train_launch(true, true, dy, lddy, packed_t, nullptr, nullptr, M, F, dx, lddx, const_cast<uint16_t *>(hid), ldh, dh, ldd, nullptr, 0,
+                            stream);
 }

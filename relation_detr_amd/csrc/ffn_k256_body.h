@@ -2,6 +2,9 @@
 // code they had before the training variants existed: wrapped in a function the same statements allocate registers differently).
 // The including kernel provides, as parameters or constants:
 //   LN, MODE, x, ldx, packed, b1, b2, M, F, out, ldo, dbg_arg, gamma, beta, eps, pos, ldp, out2, ldo2, hid, ldh, dhid, ldd
+// and, for fp32 at either end of the block (the mixed-precision training kernels; false / null everywhere else):
+//   XF32: the rows are read from xf (float, ldx) instead of x, rounded to bf16 (RNE) and also stored as xlp [M, 256] (ldxl)
+//   DXF32: the accumulators are stored unrounded to outf (float, ldo) instead of out
 #ifdef RDETR_DEV
     const int dbg = dbg_arg;                 // development builds: component-timing mask (1 no weight stream, 2 no barrier, 4 / 8 no GEMM 2 / 1)
 #else
@@ -58,8 +61,24 @@
         u32x4 xr[2][8];                                                       // X^T fragments: B operand of GEMM 1, all of K
 #pragma unroll
         for (int s = 0; s < 8; ++s) {
+            if constexpr (XF32) {
+                // 8 floats where the bf16 kernel loads 8 bf16: rounded into the same packed registers, which are also stored -- the
+                // bf16 copy of x the weight gradient dW1 = dH^T x reads (autocast would write it in a pass of its own)
+                const long long rows2[2] = {row_a, row_b};
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb) {
+                    xr[cb][s] = u32x4{0u, 0u, 0u, 0u};
+                    if (rows2[cb] < M) {
+                        const float *src = xf + rows2[cb] * ldx + 32 * s + 8 * g;
+                        const f32x4 lo = *reinterpret_cast<const f32x4 *>(src), hi = *reinterpret_cast<const f32x4 *>(src + 4);
+                        xr[cb][s] = u32x4{pack_bf16x2(lo.x, lo.y), pack_bf16x2(lo.z, lo.w), pack_bf16x2(hi.x, hi.y), pack_bf16x2(hi.z, hi.w)};
+                        *reinterpret_cast<u32x4 *>(xlp + rows2[cb] * ldxl + 32 * s + 8 * g) = xr[cb][s];
+                    }
+                }
+            } else {
             xr[0][s] = row_a < M ? *reinterpret_cast<const u32x4 *>(x + row_a * ldx + 32 * s + 8 * g) : u32x4{0u, 0u, 0u, 0u};
             xr[1][s] = row_b < M ? *reinterpret_cast<const u32x4 *>(x + row_b * ldx + 32 * s + 8 * g) : u32x4{0u, 0u, 0u, 0u};
+            }
         }
         // H / dH slots of this wave's two 16-row blocks: the block's first row is part of the SCALAR offset, rows left in the block
         // decide per lane between its (tile-independent) offset and kFfnNoRow -- selected where it is used, so that one register
@@ -256,7 +275,16 @@
                     hi.x = hi.x * rstd * g1.x + c1.x; hi.y = hi.y * rstd * g1.y + c1.y; hi.z = hi.z * rstd * g1.z + c1.z; hi.w = hi.w * rstd * g1.w + c1.w;
                 }
             }
-            if (row < M) {
+            if constexpr (DXF32) {
+                if (row < M) {
+                    float *o = outf + row * ldo + 8 * g;
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        *reinterpret_cast<f32x4 *>(o + 32 * u) = acc2[2 * u][cb];
+                        *reinterpret_cast<f32x4 *>(o + 32 * u + 4) = acc2[2 * u + 1][cb];
+                    }
+                }
+            } else if (row < M) {
                 uint16_t *o = out + row * ldo + 8 * g;
 #pragma unroll
                 for (int u = 0; u < 8; ++u) {

@@ -108,11 +108,13 @@ template <> struct LnIO8<uint16_t> {
 // 3.7 TB/s; HBM needs more outstanding bytes than that).
 // kStats (the training forward): additionally the row's mean and 1/sqrt(var + eps) as fp32 into stats[row] = {mean, rstd}, what the
 // backward kernel below starts from.  The arithmetic is the one body, so `out` has the same bits with and without.
-template <typename T, bool kStats>
-__device__ __forceinline__ void add_layernorm256_body(const T *__restrict__ x, const T *__restrict__ r, const T *__restrict__ gamma,
-                                                      const T *__restrict__ beta, long long rows, long long ldx, long long ldr,
-                                                      long long ldo, float eps, T *__restrict__ out, const T *__restrict__ pos,
-                                                      long long ldp, T *__restrict__ out2, long long ldo2, float *__restrict__ stats)
+// TR / TP / TO (the mixed-precision training forward): the residual's, the parameters' and the output's storage type where they
+// differ from x's; every value is widened to fp32 as it is loaded, so the arithmetic below is the same for every combination.
+template <typename T, bool kStats, typename TR = T, typename TP = T, typename TO = T>
+__device__ __forceinline__ void add_layernorm256_body(const T *__restrict__ x, const TR *__restrict__ r, const TP *__restrict__ gamma,
+                                                      const TP *__restrict__ beta, long long rows, long long ldx, long long ldr,
+                                                      long long ldo, float eps, TO *__restrict__ out, const TO *__restrict__ pos,
+                                                      long long ldp, TO *__restrict__ out2, long long ldo2, float *__restrict__ stats)
 {
     const int lane = threadIdx.x & 63, half = lane >> 5, c = (lane & 31) * 8;
     const long long row0 = ((long long)blockIdx.x * kLnWaves + (threadIdx.x >> 6)) * kLnRowsPerWave + half;
@@ -133,15 +135,15 @@ __device__ __forceinline__ void add_layernorm256_body(const T *__restrict__ x, c
             const long long row = row0 + 2 * i;
             if (row < rows) {
                 float t[8];
-                LnIO8<T>::load(r + row * ldr + c, t);
+                LnIO8<TR>::load(r + row * ldr + c, t);
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[i][k] += t[k];
             }
         }
     }
     float g[8], b[8];
-    LnIO8<T>::load(gamma + c, g);
-    LnIO8<T>::load(beta + c, b);
+    LnIO8<TP>::load(gamma + c, g);
+    LnIO8<TP>::load(beta + c, b);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const long long row = row0 + 2 * i;
@@ -161,16 +163,16 @@ __device__ __forceinline__ void add_layernorm256_body(const T *__restrict__ x, c
 #pragma unroll
         for (int k = 0; k < 8; ++k) y[k] = v[i][k] * rstd * g[k] + b[k];
         if (row < rows) {
-            LnIO8<T>::store(out + row * ldo + c, y);
+            LnIO8<TO>::store(out + row * ldo + c, y);
             if constexpr (kStats) {
                 if ((lane & 31) == 0) *reinterpret_cast<f32x2 *>(stats + row * 2) = f32x2{mean, rstd};
             }
             if (out2) {                      // out2 = out + pos, from the STORED (rounded) normalised values: the bits of a separate add
                 float pv[8];
-                LnIO8<T>::load(pos + row * ldp + c, pv);
+                LnIO8<TO>::load(pos + row * ldp + c, pv);
 #pragma unroll
-                for (int k = 0; k < 8; ++k) pv[k] += ln_round<T>(y[k]);
-                LnIO8<T>::store(out2 + row * ldo2 + c, pv);
+                for (int k = 0; k < 8; ++k) pv[k] += ln_round<TO>(y[k]);
+                LnIO8<TO>::store(out2 + row * ldo2 + c, pv);
             }
         }
     }
@@ -196,7 +198,19 @@ __global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_train_kernel
                                                                                  float eps, T *__restrict__ out,
                                                                                  float *__restrict__ stats)
 {
-    add_layernorm256_body<T, true>(x, r, gamma, beta, rows, ldx, ldr, ldo, eps, out, nullptr, 0, nullptr, 0, stats);
+    add_layernorm256_body<T, true, T, T, T>(x, r, gamma, beta, rows, ldx, ldr, ldo, eps, out, nullptr, 0, nullptr, 0, stats);
+}
+
+// Mixed-precision training forward (bf16 autocast over fp32 parameters): x and the residual each fp32 or bf16, gamma / beta / out fp32
+template <typename TX, typename TR>
+__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_train_mixed_kernel(const TX *__restrict__ x, const TR *__restrict__ r,
+                                                                                       const float *__restrict__ gamma,
+                                                                                       const float *__restrict__ beta, long long rows,
+                                                                                       long long ldx, long long ldr, long long ldo,
+                                                                                       float eps, float *__restrict__ out,
+                                                                                       float *__restrict__ stats)
+{
+    add_layernorm256_body<TX, true, TR, float, float>(x, r, gamma, beta, rows, ldx, ldr, ldo, eps, out, nullptr, 0, nullptr, 0, stats);
 }
 
 template <typename T>
@@ -286,14 +300,15 @@ static int add_layernorm_train(const T *x, const T *r, const T *gamma, const T *
 // Bound: HBM (4 x rows x C x sizeof(T) bytes; the partials are at most 2 MiB).
 constexpr int kLnBwdMaxBlocks = 1024;      // 4 workgroups (16 waves) on each of the MI355X's 256 CUs: 24 KB of bf16 loads per CU and trip
 
-template <typename T, bool kParams>
-__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_kernel(const T *__restrict__ dy, long long lddy,
-                                                                               const T *__restrict__ x, long long ldx,
-                                                                               const T *__restrict__ r, long long ldr,
-                                                                               const T *__restrict__ gamma,
-                                                                               const float *__restrict__ stats, long long rows,
-                                                                               long long nblk, T *__restrict__ dx,
-                                                                               float *__restrict__ partial)
+// T is the type of dy, gamma and dx; TX / TR those of x and the residual (all T in the same-dtype kernels).  kTwin (the
+// mixed-precision backward, T = float): dx may be null, and dxb, where it is not null, receives the same values rounded to bf16 (RNE)
+// in the same pass -- the gradient of a bf16 operand beside the fp32 one.
+template <typename T, bool kParams, typename TX, typename TR, bool kTwin>
+__device__ __forceinline__ void add_layernorm256_bwd_body(const T *__restrict__ dy, long long lddy, const TX *__restrict__ x,
+                                                          long long ldx, const TR *__restrict__ r, long long ldr,
+                                                          const T *__restrict__ gamma, const float *__restrict__ stats, long long rows,
+                                                          long long nblk, T *__restrict__ dx, uint16_t *__restrict__ dxb,
+                                                          float *__restrict__ partial)
 {
     __shared__ float red[kLnWaves * 2][2][256];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5, c = (lane & 31) * 8;
@@ -309,7 +324,7 @@ __global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_kernel(c
             const long long row = row0 + 2 * i;
             if (row < rows) {
                 LnIO8<T>::load(dy + row * lddy + c, d[i]);
-                LnIO8<T>::load(x + row * ldx + c, v[i]);
+                LnIO8<TX>::load(x + row * ldx + c, v[i]);
                 const f32x2 st = *reinterpret_cast<const f32x2 *>(stats + row * 2);
                 mean[i] = st.x;
                 rstd[i] = st.y;
@@ -325,7 +340,7 @@ __global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_kernel(c
                 const long long row = row0 + 2 * i;
                 if (row < rows) {
                     float t[8];
-                    LnIO8<T>::load(r + row * ldr + c, t);
+                    LnIO8<TR>::load(r + row * ldr + c, t);
 #pragma unroll
                     for (int k = 0; k < 8; ++k) v[i][k] += t[k];
                 }
@@ -346,7 +361,14 @@ __global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_kernel(c
             float o[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] = rstd[i] * (gg[k] - m1 - v[i][k] * m2);
-            if (row < rows) LnIO8<T>::store(dx + row * 256 + c, o);
+            if constexpr (kTwin) {
+                if (row < rows) {
+                    if (dx) LnIO8<T>::store(dx + row * 256 + c, o);
+                    if (dxb) LnIO8<uint16_t>::store(dxb + row * 256 + c, o);
+                }
+            } else {
+                if (row < rows) LnIO8<T>::store(dx + row * 256 + c, o);
+            }
             if constexpr (kParams) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -371,6 +393,31 @@ __global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_kernel(c
             partial[(long long)blockIdx.x * 512 + j * 256 + threadIdx.x] = s;
         }
     }
+}
+
+template <typename T, bool kParams>
+__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_kernel(const T *__restrict__ dy, long long lddy,
+                                                                               const T *__restrict__ x, long long ldx,
+                                                                               const T *__restrict__ r, long long ldr,
+                                                                               const T *__restrict__ gamma,
+                                                                               const float *__restrict__ stats, long long rows,
+                                                                               long long nblk, T *__restrict__ dx,
+                                                                               float *__restrict__ partial)
+{
+    add_layernorm256_bwd_body<T, kParams, T, T, false>(dy, lddy, x, ldx, r, ldr, gamma, stats, rows, nblk, dx, nullptr, partial);
+}
+
+template <typename TX, typename TR, bool kParams>
+__global__ __launch_bounds__(kLnWaves *kWave) void add_layernorm256_bwd_mixed_kernel(const float *__restrict__ dy, long long lddy,
+                                                                                     const TX *__restrict__ x, long long ldx,
+                                                                                     const TR *__restrict__ r, long long ldr,
+                                                                                     const float *__restrict__ gamma,
+                                                                                     const float *__restrict__ stats, long long rows,
+                                                                                     long long nblk, float *__restrict__ dx,
+                                                                                     uint16_t *__restrict__ dxb,
+                                                                                     float *__restrict__ partial)
+{
+    add_layernorm256_bwd_body<float, kParams, TX, TR, true>(dy, lddy, x, ldx, r, ldr, gamma, stats, rows, nblk, dx, dxb, partial);
 }
 
 // dgamma / dbeta from the workgroups' partials [n, 2, 256]: one workgroup, thread t owns (which, channel) = (t / 256, t % 256) and
@@ -437,6 +484,84 @@ static int add_layernorm_backward(const T *dy, long long lddy, const T *x, long 
     return launch_status();
 }
 
+// ------------------------------------------------------------------------------------------------- mixed-precision training
+// The routes above under bf16 autocast over fp32 parameters: x and the residual are each fp32 or bf16 (the residual stream is
+// fp32, a sublayer's linear output bf16), gamma / beta / out / dy fp32.  One launcher per direction, instantiated for the four
+// operand-type pairs; the argument checks are those of the same-dtype routes with each operand on its own 16-byte grid.
+static bool ln_rows_ok(const void *p, bool is_bf16, long long ld)
+{
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % (is_bf16 ? 8 : 4) == 0;
+}
+
+template <typename TX, typename TR>
+static void ln_train_mixed_launch(const void *x, const void *r, const float *gamma, const float *beta, long long rows, long long ldx,
+                                  long long ldr, long long ldo, float eps, float *out, float *stats, unsigned nblk, hipStream_t stream)
+{
+    hipLaunchKernelGGL((add_layernorm256_train_mixed_kernel<TX, TR>), dim3(nblk), dim3(kLnWaves * kWave), 0, stream,
+                       static_cast<const TX *>(x), static_cast<const TR *>(r), gamma, beta, rows, ldx, ldr, ldo, eps, out, stats);
+}
+
+static int add_layernorm_train_mixed(const void *x, bool xb, long long ldx, const void *r, bool rb, long long ldr, const float *gamma,
+                                     const float *beta, long long rows, int C, float eps, float *out, long long ldo, float *stats,
+                                     hipStream_t stream)
+{
+    if (rows < 0 || C <= 0 || ldx < C || ldo < C || (r && ldr < C)) return RDETR_ERR_INVALID_ARG;
+    if (C != 256) return RDETR_ERR_UNSUPPORTED;
+    if (rows == 0) return RDETR_OK;
+    if (!x || !gamma || !beta || !out || !stats) return RDETR_ERR_INVALID_ARG;
+    const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave);
+    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!(ln_rows_ok(x, xb, ldx) && ln_rows_ok(out, false, ldo) && (!r || ln_rows_ok(r, rb, ldr)) && aligned_to(gamma, 16) &&
+          aligned_to(beta, 16) && aligned_to(stats, 8)))
+        return RDETR_ERR_UNSUPPORTED;
+    auto *launch = xb ? (rb ? ln_train_mixed_launch<uint16_t, uint16_t> : ln_train_mixed_launch<uint16_t, float>)
+                      : (rb ? ln_train_mixed_launch<float, uint16_t> : ln_train_mixed_launch<float, float>);
+    launch(x, r, gamma, beta, rows, ldx, ldr, ldo, eps, out, stats, (unsigned)nblk, stream);
+    return launch_status();
+}
+
+template <typename TX, typename TR>
+static void ln_bwd_mixed_launch(const float *dy, long long lddy, const void *x, long long ldx, const void *r, long long ldr,
+                                const float *gamma, const float *stats, long long rows, long long nblk, float *dx, uint16_t *dxb,
+                                float *partial, unsigned grid, hipStream_t stream)
+{
+    if (partial)
+        hipLaunchKernelGGL((add_layernorm256_bwd_mixed_kernel<TX, TR, true>), dim3(grid), dim3(kLnWaves * kWave), 0, stream, dy, lddy,
+                           static_cast<const TX *>(x), ldx, static_cast<const TR *>(r), ldr, gamma, stats, rows, nblk, dx, dxb, partial);
+    else
+        hipLaunchKernelGGL((add_layernorm256_bwd_mixed_kernel<TX, TR, false>), dim3(grid), dim3(kLnWaves * kWave), 0, stream, dy, lddy,
+                           static_cast<const TX *>(x), ldx, static_cast<const TR *>(r), ldr, gamma, stats, rows, nblk, dx, dxb, partial);
+}
+
+static int add_layernorm_backward_mixed(const float *dy, long long lddy, const void *x, bool xb, long long ldx, const void *r, bool rb,
+                                        long long ldr, const float *gamma, const float *stats, long long rows, int C, void *workspace,
+                                        long long workspace_bytes, float *dx, uint16_t *dxb, float *dgamma, float *dbeta,
+                                        hipStream_t stream)
+{
+    if (rows < 0 || C <= 0 || lddy < C || ldx < C || (r && ldr < C) || workspace_bytes < 0) return RDETR_ERR_INVALID_ARG;
+    if ((dgamma != nullptr) != (dbeta != nullptr)) return RDETR_ERR_INVALID_ARG;
+    if (C != 256) return RDETR_ERR_UNSUPPORTED;
+    if (rows == 0) return RDETR_OK;
+    if (!dy || !x || !gamma || !stats) return RDETR_ERR_INVALID_ARG;
+    // a gradient for every operand in its own type: the bf16 twin where an operand is bf16, the fp32 tensor where one is fp32
+    const bool any_bf16 = xb || (r && rb), any_f32 = !xb || (r && !rb);
+    if ((any_bf16 && !dxb) || (any_f32 && !dx)) return RDETR_ERR_INVALID_ARG;
+    const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave), grid = ln_backward_blocks(rows);
+    if (dgamma && (!workspace || workspace_bytes < grid * 512 * (long long)sizeof(float))) return RDETR_ERR_INVALID_ARG;
+    if (!(ln_rows_ok(dy, false, lddy) && ln_rows_ok(x, xb, ldx) && (!r || ln_rows_ok(r, rb, ldr)) && aligned_to(gamma, 16) &&
+          (!dx || aligned_to(dx, 16)) && (!dxb || aligned_to(dxb, 16)) && aligned_to(stats, 8) && (!dgamma || aligned_to(workspace, 16))))
+        return RDETR_ERR_UNSUPPORTED;
+    float *partial = dgamma ? static_cast<float *>(workspace) : nullptr;
+    auto *launch = xb ? (rb ? ln_bwd_mixed_launch<uint16_t, uint16_t> : ln_bwd_mixed_launch<uint16_t, float>)
+                      : (rb ? ln_bwd_mixed_launch<float, uint16_t> : ln_bwd_mixed_launch<float, float>);
+    launch(dy, lddy, x, ldx, r, ldr, gamma, stats, rows, nblk, dx, dxb, partial, (unsigned)grid, stream);
+    if (dgamma) {
+        if (launch_status() != RDETR_OK) return RDETR_ERR_LAUNCH;
+        hipLaunchKernelGGL((ln_param_grad_kernel<float>), dim3(1), dim3(512), 0, stream, partial, (int)grid, dgamma, dbeta);
+    }
+    return launch_status();
+}
+
 }  // namespace rdetr
 
 extern "C" int rdetr_add_layernorm_train_f32(const float *x, const float *residual, const float *gamma, const float *beta,
@@ -476,6 +601,23 @@ extern "C" int rdetr_add_layernorm_backward_bf16(const uint16_t *dy, long long l
 {
     return rdetr::add_layernorm_backward<uint16_t>(dy, lddy, x, ldx, residual, ldr, gamma, stats, rows, C, workspace, workspace_bytes,
                                                    dx, dgamma, dbeta, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rdetr_add_layernorm_train_mixed(const void *x, int x_is_bf16, long long ldx, const void *residual, int r_is_bf16,
+                                               long long ldr, const float *gamma, const float *beta, long long rows, int C, float eps,
+                                               float *out, long long ldo, float *stats, void *stream)
+{
+    return rdetr::add_layernorm_train_mixed(x, x_is_bf16 != 0, ldx, residual, r_is_bf16 != 0, ldr, gamma, beta, rows, C, eps, out, ldo,
+                                            stats, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int rdetr_add_layernorm_backward_mixed(const float *dy, long long lddy, const void *x, int x_is_bf16, long long ldx,
+                                                  const void *residual, int r_is_bf16, long long ldr, const float *gamma,
+                                                  const float *stats, long long rows, int C, void *workspace, long long workspace_bytes,
+                                                  float *dx, uint16_t *dx_bf16, float *dgamma, float *dbeta, void *stream)
+{
+    return rdetr::add_layernorm_backward_mixed(dy, lddy, x, x_is_bf16 != 0, ldx, residual, r_is_bf16 != 0, ldr, gamma, stats, rows, C,
+                                               workspace, workspace_bytes, dx, dx_bf16, dgamma, dbeta, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int rdetr_add_layernorm_f32(const float *x, const float *residual, const float *gamma, const float *beta,

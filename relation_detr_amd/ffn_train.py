@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from .ops import _cptr, _require_device, _rows_view, _stream_ptr, ffn_k256_supported
 
+# _GRAD_BLOCK, _OFFSET_LIMIT and _aligned_rows are also used by amp_train.py (the mixed-precision form of this route): rename them there too
 _GRAD_BLOCK = 512                # hidden units per library call of the weight / bias gradient of linear1
 _OFFSET_LIMIT = 1 << 31          # H / dH are addressed with 32-bit byte offsets whose top bit marks a row beyond the last
 

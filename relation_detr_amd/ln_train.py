@@ -28,6 +28,9 @@ MAX_PARTIALS = 1024              # grid cap of the backward kernel = most [2, 25
 _DTYPES = (torch.float32, torch.bfloat16)
 
 
+# _rows and _param are also used by amp_train.py (the mixed-precision form of this route): rename them there too
+
+
 def _aligned(t: torch.Tensor, ld: int) -> bool:
     return t.data_ptr() % 16 == 0 and (ld * t.element_size()) % 16 == 0
 

@@ -16,7 +16,7 @@ import warnings
 import torch
 from torch import Tensor, nn
 
-from . import ln_train, msda_train_hm, ops
+from . import amp_train, ln_train, msda_train_hm, ops
 from . import options as _options
 
 
@@ -268,7 +268,9 @@ class MultiScaleDeformableAttention(nn.Module):
         if out.is_cuda and not torch.is_grad_enabled() and out.dtype in (torch.float32, torch.bfloat16):
             return ops.add_layer_norm(out, residual, norm.weight, norm.bias, norm.eps)
         if (self.options.ln_train_fused and torch.is_grad_enabled()
-                and (out.requires_grad or residual.requires_grad or (norm.weight is not None and norm.weight.requires_grad))
-                and ln_train.add_layer_norm_train_supported(out, residual, norm.weight, norm.bias)):
-            return ln_train.AddLayerNormFunction.apply(out, residual, norm.weight, norm.bias, norm.eps)
+                and (out.requires_grad or residual.requires_grad or (norm.weight is not None and norm.weight.requires_grad))):
+            if ln_train.add_layer_norm_train_supported(out, residual, norm.weight, norm.bias):
+                return ln_train.AddLayerNormFunction.apply(out, residual, norm.weight, norm.bias, norm.eps)
+            if amp_train.autocast_bf16_active() and amp_train.add_layer_norm_mixed_supported(out, residual, norm.weight, norm.bias):
+                return amp_train.AddLayerNormMixedFunction.apply(out, residual, norm.weight, norm.bias, norm.eps)   # bf16 out, fp32 stream
         return norm(residual + out)

@@ -27,14 +27,23 @@ class Options:
     ffn_ln: bool = False             # ... with the closing add+LayerNorm in its epilogue (opt-in: 3-6 % slower in the stack)
     ffn_train_fused: bool = False    # training, tall bf16 inputs: the block's forward (hidden activations saved) and its data gradient as
                                      # one kernel each (FeedForwardFunction, csrc/ffn.hip) instead of two library GEMMs + ReLU passes per
-                                     # direction; weight gradients stay library GEMMs (opt-in; profiles/r10/)
+                                     # direction; weight gradients stay library GEMMs (opt-in; profiles/r10/).  Under bf16 autocast
+                                     # over fp32 parameters: the mixed-precision form (amp_train.FeedForwardMixedFunction: fp32 x rounded
+                                     # inside the kernel, fp32 dx, weights packed straight from the fp32 parameters).  MEASURED SLOWER there: the encoder layer's
+                                     # norm1 -> FFN -> norm2 chain, forward + backward with both switches on, takes 1.25 / 1.16 / 1.01x
+                                     # the device time of autocast on the torch route at the R50 encoder's B = 1 / 2 / 4 although its
+                                     # two norms alone gain (profiles/r15/amp_train_ab.txt))
     ln_train_fused: bool = False     # training, fp32 / bf16, 256 channels: LayerNorm(x + residual) as one kernel each way
                                      # (AddLayerNormFunction, csrc/layernorm.hip) instead of add pass + LayerNorm + its two backward passes;
                                      # the sum stays fp32, one dx serves both operands, dgamma / dbeta summed in a fixed order (opt-in; no
                                      # effect without grad; device time of forward + backward 0.47 / 0.35 / 0.30x the torch route's at the
                                      # R50 encoder's B = 1 / 2 / 4, 0.67-0.71x at decoder height, fp32 0.65x; from an idle device the host
                                      # path costs 230 us against 140-170 us, so a launch-bound step loses below ~89,000 rows;
-                                     # profiles/r13/ln_train_ab.txt)
+                                     # profiles/r13/ln_train_ab.txt).  Under bf16 autocast over fp32 parameters: the mixed-precision
+                                     # form (amp_train.AddLayerNormMixedFunction: x / residual each fp32 or bf16, fp32 result, each
+                                     # operand's gradient in its own dtype from one pass; device time of forward + backward 0.26 / 0.24x
+                                     # autocast on the torch route at 1,800 / 4,000 rows, from an idle device 1.34 / 1.12x;
+                                     # profiles/r15/amp_train_ab.txt)
     ln_pos: bool = True              # encoder: norm2 also emits the next layer's query + pos
     decoder_ln_pos: bool = True      # decoder: norm2 also emits the cross-attention's query + query_pos
     decoder_entry: bool = True       # decoder layer entry (reference scaling + sine embedding, scaled query_pos) as 2 kernels

@@ -23,7 +23,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
-from . import ffn_train, ln_train, ops
+from . import amp_train, ffn_train, ln_train, ops
 from . import options as _options
 from .ms_deform_attn import MultiScaleDeformableAttention
 from .relation import PositionRelationEmbedding
@@ -61,16 +61,20 @@ def sine_pos_embed(pos: Tensor, num_pos_feats: int = 128, temperature: float = 1
 def add_norm(norm: nn.LayerNorm, x: Tensor, residual: Tensor = None, out: Tensor = None, opts: "_options.Options" = None) -> Tensor:
     """norm(x + residual).  On a ROCm device without autograd: one HIP kernel (rdetr_add_layernorm_*, csrc/layernorm.hip)
     instead of an add pass and a normalisation pass.  Where a gradient is needed, options.ln_train_fused sends fp32 / bf16 inputs
-    of 256 channels through the same kernel body and its backward (ln_train.AddLayerNormFunction); everything else -- the CPU
-    oracle harness, and training by default -- is plain torch."""
+    of 256 channels through the same kernel body and its backward (ln_train.AddLayerNormFunction) and, under bf16 autocast, operands
+    of mixed dtypes with fp32 parameters through its mixed-precision form (amp_train.AddLayerNormMixedFunction); everything else --
+    the CPU oracle harness, and training by default -- is plain torch."""
     needs_grad = torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad or
                                               (residual is not None and residual.requires_grad))
     if x.is_cuda and not needs_grad and x.dtype in (torch.float32, torch.bfloat16):
         from . import ops
         return ops.add_layer_norm(x, residual, norm.weight, norm.bias, norm.eps, out=out)
-    if (needs_grad and (opts or _options.get()).ln_train_fused
-            and ln_train.add_layer_norm_train_supported(x, residual, norm.weight, norm.bias)):
+    fused = needs_grad and (opts or _options.get()).ln_train_fused
+    if fused and ln_train.add_layer_norm_train_supported(x, residual, norm.weight, norm.bias):
         y = ln_train.AddLayerNormFunction.apply(x, residual, norm.weight, norm.bias, norm.eps)
+    elif (fused and amp_train.autocast_bf16_active()
+          and amp_train.add_layer_norm_mixed_supported(x, residual, norm.weight, norm.bias)):
+        y = amp_train.AddLayerNormMixedFunction.apply(x, residual, norm.weight, norm.bias, norm.eps)
     else:
         y = norm(x if residual is None else x + residual)
     if out is not None:
@@ -104,24 +108,34 @@ def _fused_ffn_applies(linear1: nn.Linear, linear2: nn.Linear, x: Tensor, opts: 
             and ops.ffn_k256_supported(x, linear1.weight, linear2.weight))
 
 
-def _fused_ffn_train_applies(linear1: nn.Linear, linear2: nn.Linear, x: Tensor, opts: "_options.Options" = None) -> bool:
+def _fused_ffn_train_applies(linear1: nn.Linear, linear2: nn.Linear, x: Tensor, opts: "_options.Options" = None):
+    """The autograd Function of the fused training route that applies to this call, or None: the same-dtype one first, then,
+    under bf16 autocast, the mixed-precision one."""
     if not ((opts or _options.get()).ffn_train_fused and x.is_cuda and torch.is_grad_enabled()
             and linear1.bias is not None and linear2.bias is not None and x.numel() // x.shape[-1] >= _K256_MIN_ROWS):
-        return False
+        return None
     params = (linear1.weight, linear1.bias, linear2.weight, linear2.bias)
-    return ((x.requires_grad or any(p.requires_grad for p in params))
-            and ffn_train.ffn_train_supported(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias))
+    if not (x.requires_grad or any(p.requires_grad for p in params)):
+        return None
+    if ffn_train.ffn_train_supported(x, *params):
+        return ffn_train.FeedForwardFunction
+    if amp_train.autocast_bf16_active() and amp_train.ffn_mixed_supported(x, *params):
+        return amp_train.FeedForwardMixedFunction
+    return None
 
 
 def feed_forward(linear1: nn.Linear, linear2: nn.Linear, x: Tensor, opts: "_options.Options" = None) -> Tensor:
     """linear2(relu(linear1(x))) (relation_transformer.py:226-233, 272-275).  Tall bf16 inputs at inference go through the fused
     kernel (csrc/ffn.hip: the [rows, d_ffn] activations never reach HBM); options.ffn_fused = False keeps the two library GEMMs.
     In training, options.ffn_train_fused sends tall bf16 inputs with bf16 parameters through the same kernel body and its data
-    gradient (ffn_train.FeedForwardFunction); everything else -- and the default -- is the two library GEMMs under autograd."""
+    gradient (ffn_train.FeedForwardFunction) and, under bf16 autocast, tall fp32 / bf16 inputs with fp32 parameters through its
+    mixed-precision form (amp_train.FeedForwardMixedFunction); everything else -- and the default -- is the two library GEMMs under
+    autograd."""
     if _fused_ffn_applies(linear1, linear2, x, opts):
         return ops.ffn_k256(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
-    if _fused_ffn_train_applies(linear1, linear2, x, opts):
-        return ffn_train.FeedForwardFunction.apply(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
+    function = _fused_ffn_train_applies(linear1, linear2, x, opts)
+    if function is not None:
+        return function.apply(x, linear1.weight, linear1.bias, linear2.weight, linear2.bias)
     return linear2(linear_relu(linear1, x, opts))
 
 
