@@ -731,6 +731,45 @@ int rdetr_ffn_k256_backward_dxf32_bf16(const uint16_t *dy, long long lddy, const
                                        long long ldh, long long M, int F, uint16_t *dh, long long ldd, float *dx, long long lddx,
                                        void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training criterion (csrc/criterion.hip): the matcher's cost matrices and the set losses of a STACK of prediction sets.
+ * Replaces, per set and image, HungarianMatcher.calculate_cost (models/matcher/hungarian_matcher.py:41-70) and, per set,
+ * HybridSetCriterion.loss_labels + SetCriterion.loss_boxes with vari_sigmoid_focal_loss (models/bricks/set_criterion.py:84-106,
+ * 178-216, models/bricks/losses.py:15-21) and their autograd.  The assignment itself stays on the host.
+ *
+ * A stack is R rows of N queries; row r belongs to image r % B (rows = layers x images).  logits [R, N, C] fp32 or bf16 and
+ * boxes [R, N, 4] fp32 (cxcywh) are contiguous inside a row, rows ld_logits / ld_boxes ELEMENTS apart (>= N * C, >= N * 4), so a
+ * query slice of a taller tensor is taken in place.  The ground truth is padded per image: gt_boxes [B, Gmax, 4] fp32 cxcywh,
+ * gt_labels [B, Gmax] int32, gt_count [B] int32.  A label outside [0, C) is never used as an index: its class term is 0.
+ * fp32 math; boxes bases 16-byte aligned and ld_boxes a multiple of 4, Gmax <= 2048, R <= 65535 (else RDETR_ERR_UNSUPPORTED).
+ *
+ * rdetr_match_cost_*: cost [R, N, Gmax] fp32 = w_bbox * L1 + w_class * (focal positive - focal negative cost at the gt's class,
+ *   1e-6 inside the logs, 1 - p formed as sigmoid(-x)) + w_giou * (-GIoU); columns g >= gt_count[r % B] are written as 0.
+ *
+ * rdetr_set_loss_*: match [R, N] int32 holds each query's gt index in its image's table, or -1 (an index >= Gmax counts as -1).
+ *   Queries n < n_split form segment 0 (the denoising queries) and are scaled by inv_norm_a, the rest segment 1, by inv_norm_b.
+ *     sums      [R, 2, 3] fp32   per row and segment {varifocal class loss, L1, GIoU loss}, each times the segment's inv_norm
+ *     dlogits   [R, N, C]        d sums[r, seg, 0] / d logits, in the logits' dtype, contiguous
+ *     dbox_l1   [R, N, 4] fp32   d sums[r, seg, 1] / d boxes      dbox_giou [R, N, 4] fp32  d sums[r, seg, 2] / d boxes
+ *   (zero rows where unmatched).  The class target is the detached IoU of the matched pair, the focal weight is detached, as in
+ *   the reference, so these are the complete gradients.  ws: rdetr_set_loss_workspace_bytes(R, N) bytes of per-workgroup partial
+ *   sums, added in a fixed order by a second launch: no atomics, the same bits on every run. */
+int rdetr_match_cost_f32(const float *logits, long long ld_logits, const float *boxes, long long ld_boxes, const float *gt_boxes,
+                         const int *gt_labels, const int *gt_count, int R, int B, int N, int C, int Gmax, float alpha, float gamma,
+                         float w_class, float w_bbox, float w_giou, float *cost, void *stream);
+int rdetr_match_cost_bf16(const uint16_t *logits, long long ld_logits, const float *boxes, long long ld_boxes, const float *gt_boxes,
+                          const int *gt_labels, const int *gt_count, int R, int B, int N, int C, int Gmax, float alpha, float gamma,
+                          float w_class, float w_bbox, float w_giou, float *cost, void *stream);
+long long rdetr_set_loss_workspace_bytes(int R, int N);
+int rdetr_set_loss_f32(const float *logits, long long ld_logits, const float *boxes, long long ld_boxes, const int *match,
+                       const float *gt_boxes, const int *gt_labels, int R, int B, int N, int C, int Gmax, int n_split, float inv_norm_a,
+                       float inv_norm_b, float alpha, float gamma, void *ws, long long ws_bytes, float *sums, float *dlogits,
+                       float *dbox_l1, float *dbox_giou, void *stream);
+int rdetr_set_loss_bf16(const uint16_t *logits, long long ld_logits, const float *boxes, long long ld_boxes, const int *match,
+                        const float *gt_boxes, const int *gt_labels, int R, int B, int N, int C, int Gmax, int n_split, float inv_norm_a,
+                        float inv_norm_b, float alpha, float gamma, void *ws, long long ws_bytes, float *sums, uint16_t *dlogits,
+                        float *dbox_l1, float *dbox_giou, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

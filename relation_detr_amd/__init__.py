@@ -15,6 +15,7 @@ from .ffn_train import FeedForwardFunction, ffn_k256_backward, ffn_k256_train
 from .ln_train import AddLayerNormFunction
 from .amp_train import AddLayerNormMixedFunction, FeedForwardMixedFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
+from .criterion import RelationCriterion, SetLossFunction, hungarian_match, match_cost, set_loss
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -26,4 +27,5 @@ __all__ = [
     "FeedForwardFunction", "ffn_k256_train", "ffn_k256_backward", "AddLayerNormFunction",
     "MultiScaleDeformableAttnHeadMajorFunction", "ms_deform_attn_backward_fused_hm", "grad_value_from_head_major",
     "AddLayerNormMixedFunction", "FeedForwardMixedFunction",
+    "RelationCriterion", "SetLossFunction", "match_cost", "hungarian_match", "set_loss",
 ]

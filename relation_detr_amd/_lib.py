@@ -101,6 +101,11 @@ SIGNATURES = {
     "rdetr_add_layernorm_train_mixed": [_vp, _c_int, _c_ll, _vp, _c_int, _c_ll, _vp, _vp, _c_ll, _c_int, _c_float, _vp, _c_ll, _vp, _vp],
     "rdetr_add_layernorm_backward_mixed": [_vp, _c_ll, _vp, _c_int, _c_ll, _vp, _c_int, _c_ll, _vp, _vp, _c_ll, _c_int, _vp, _c_ll]
                                           + [_vp] * 5,
+    "rdetr_match_cost_f32": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 5 + [_c_float] * 5 + [_vp, _vp],
+    "rdetr_match_cost_bf16": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 5 + [_c_float] * 5 + [_vp, _vp],
+    "rdetr_set_loss_workspace_bytes": [_c_int, _c_int],
+    "rdetr_set_loss_f32": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float] * 4 + [_vp, _c_ll] + [_vp] * 5,
+    "rdetr_set_loss_bf16": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float] * 4 + [_vp, _c_ll] + [_vp] * 5,
 }
 
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3            # rdetr_status (include/relation_detr_amd.h)
