@@ -770,6 +770,54 @@ int rdetr_set_loss_bf16(const uint16_t *logits, long long ld_logits, const float
                         float inv_norm_b, float alpha, float gamma, void *ws, long long ws_bytes, float *sums, uint16_t *dlogits,
                         float *dbox_l1, float *dbox_giou, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Denoising query generator (csrc/denoising.hip, csrc/cdn_noise.h): GenerateCDNQueries.forward
+ * (models/bricks/denoising.py:180-331) without its loops over images and groups, its host-built index tensors and its two
+ * scatter assignments.  The caller allocates; nothing here allocates or waits for the device; zero work returns RDETR_OK without
+ * a launch.
+ *
+ * The ground truth of the B images is flat: gt_labels [G] int64, gt_boxes [G, 4] fp32 cxcywh, gt_offset [B + 1] int32 the
+ * exclusive prefix sum of the per-image counts G_b (gt_offset[B] = G; G is also passed by value).  max_gt = max G_b,
+ * Ndn = 2 * groups * max_gt queries per image, Q = 2 * groups * G flat rows.  Slot (b, j) with i = j / max_gt, t = j % max_gt is
+ * padding when t >= G_b (or when the offset table would lead outside [0, G)); else it belongs to flat row r = i * G +
+ * gt_offset[b] + t and gt gt_offset[b] + t, a positive copy for even i and a negative one for odd i.
+ *
+ * rdetr_cdn_queries_*: embed [C, d] fp32 or bf16, d a multiple of 4 (fp32) or 8 (bf16), rows moved as 16-byte vectors.
+ *     label_query  [B, Ndn, d]  embed[label], label = label_r[r] if label_u[r] < label_noise_prob * 0.5 else the gt label; a
+ *                               zero row for padding and for a label outside [0, C), which is never used as an index
+ *     box_query    [B, Ndn, 4]  fp32: corners +- noise, clamp to [0, 1], back to cxcywh, inverse_sigmoid with eps 1e-3, in the
+ *                               reference's operation order (only logf may differ from torch in fp32); zeros for padding
+ *     noised_label [B, Ndn]     int32, -1 for padding and for a label outside [0, C): what the backward reads
+ *   Every element of the three is written.  The noise is either the reference's four draws in its flat layout (keyed = 0):
+ *   label_u [Q] fp32 of rand_like, label_r [Q] int64 of randint_like(0, C), box_sign [Q, 4] fp32 in {0, 1} of randint_like(0, 2),
+ *   box_u [Q, 4] fp32 of rand_like -- the label pair may be NULL when label_noise_prob <= 0, the box pair when box_noise_scale
+ *   <= 0, which also skips the corner round trip -- or (keyed = 1) generated in registers from key as rdetr_cdn_noise writes it.
+ *
+ * rdetr_cdn_mask: mask [T, T] uint8 / bool, T = groups * group_size + num_queries, group_size = 2 * max_gt:
+ *   mask[r, c] = c < Ndn and (r >= Ndn or r / group_size != c / group_size); base 4-byte aligned, T <= 46340.
+ *
+ * rdetr_cdn_embed_backward_*: grad_embed [C, d] from grad_label_query [rows, d] (contiguous) and noised_label [rows].  All of
+ *   grad_embed is written, zero rows for unused classes.  No atomics: each class adds its rows in ascending order into an fp32
+ *   accumulator with Kahan compensation (bf16 rounded once at the end), so the result is the same bits on every run.
+ *
+ * rdetr_cdn_noise: the four draws of key.  Philox4x32-10 under the key's low and high words; counter (r, 0, 0, 0) gives a0..a3,
+ *   counter (r, 1, 0, 0) gives b0..b3; label_u = (a0 >> 8) * 2^-24, label_r = (uint64(a1) * C) >> 32, box_sign[k] = bit k of a2,
+ *   box_u[k] = (b_k >> 8) * 2^-24.  Q < 2^31. */
+int rdetr_cdn_queries_f32(const long long *gt_labels, const float *gt_boxes, const int *gt_offset, int B, int G, int max_gt, int groups,
+                          int C, int d, float label_noise_prob, float box_noise_scale, const float *embed, const float *label_u,
+                          const long long *label_r, const float *box_sign, const float *box_u, int keyed, unsigned long long key,
+                          float *label_query, float *box_query, int *noised_label, void *stream);
+int rdetr_cdn_queries_bf16(const long long *gt_labels, const float *gt_boxes, const int *gt_offset, int B, int G, int max_gt, int groups,
+                           int C, int d, float label_noise_prob, float box_noise_scale, const uint16_t *embed, const float *label_u,
+                           const long long *label_r, const float *box_sign, const float *box_u, int keyed, unsigned long long key,
+                           uint16_t *label_query, float *box_query, int *noised_label, void *stream);
+int rdetr_cdn_mask(int groups, int group_size, int num_queries, unsigned char *mask, void *stream);
+int rdetr_cdn_embed_backward_f32(const float *grad_label_query, const int *noised_label, int rows, int C, int d, float *grad_embed,
+                                 void *stream);
+int rdetr_cdn_embed_backward_bf16(const uint16_t *grad_label_query, const int *noised_label, int rows, int C, int d, uint16_t *grad_embed,
+                                  void *stream);
+int rdetr_cdn_noise(unsigned long long key, int Q, int C, float *label_u, long long *label_r, float *box_sign, float *box_u, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

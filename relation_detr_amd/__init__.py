@@ -16,6 +16,8 @@ from .ln_train import AddLayerNormFunction
 from .amp_train import AddLayerNormMixedFunction, FeedForwardMixedFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
 from .criterion import RelationCriterion, SetLossFunction, hungarian_match, match_cost, set_loss
+from .denoising import CdnQueryFunction, GenerateCDNQueries, cdn_noise, cdn_queries, denoising_mask
+from .detector import RelationDETRHead
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -28,4 +30,5 @@ __all__ = [
     "MultiScaleDeformableAttnHeadMajorFunction", "ms_deform_attn_backward_fused_hm", "grad_value_from_head_major",
     "AddLayerNormMixedFunction", "FeedForwardMixedFunction",
     "RelationCriterion", "SetLossFunction", "match_cost", "hungarian_match", "set_loss",
+    "GenerateCDNQueries", "CdnQueryFunction", "cdn_queries", "cdn_noise", "denoising_mask", "RelationDETRHead",
 ]

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RDETR_LIB_PATH") or os.path.join(_HERE, "librelation_detr_amd.so")    # override: A/B builds
 
 _c_int, _c_float, _vp, _c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_longlong
+_c_ull = ctypes.c_ulonglong
 
 # name -> argtypes (restype is int unless noted); mirrors include/relation_detr_amd.h one to one.
 SIGNATURES = {
@@ -106,6 +107,12 @@ SIGNATURES = {
     "rdetr_set_loss_workspace_bytes": [_c_int, _c_int],
     "rdetr_set_loss_f32": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float] * 4 + [_vp, _c_ll] + [_vp] * 5,
     "rdetr_set_loss_bf16": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float] * 4 + [_vp, _c_ll] + [_vp] * 5,
+    "rdetr_cdn_queries_f32": [_vp] * 3 + [_c_int] * 6 + [_c_float] * 2 + [_vp] * 5 + [_c_int, _c_ull] + [_vp] * 4,
+    "rdetr_cdn_queries_bf16": [_vp] * 3 + [_c_int] * 6 + [_c_float] * 2 + [_vp] * 5 + [_c_int, _c_ull] + [_vp] * 4,
+    "rdetr_cdn_mask": [_c_int] * 3 + [_vp, _vp],
+    "rdetr_cdn_embed_backward_f32": [_vp, _vp] + [_c_int] * 3 + [_vp, _vp],
+    "rdetr_cdn_embed_backward_bf16": [_vp, _vp] + [_c_int] * 3 + [_vp, _vp],
+    "rdetr_cdn_noise": [_c_ull] + [_c_int] * 2 + [_vp] * 5,
 }
 
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3            # rdetr_status (include/relation_detr_amd.h)

@@ -17,8 +17,9 @@ Two routes, chosen by the constructor's ``fused`` (CPU tensors always take the s
   against.
 
 ``match_cost``, ``hungarian_match`` and ``set_loss`` are the three pieces, usable alone.  Not built: the plain focal
-``SetCriterion``, ``ia_bce_loss``, ``two_stage_binary_cls``, ``mixed_match``, the denoising query generator and a device-side
-assignment solver.
+``SetCriterion``, ``ia_bce_loss``, ``two_stage_binary_cls``, ``mixed_match`` and a device-side assignment solver.  The denoising
+query generator whose ``dn_meta`` this takes is ``denoising.GenerateCDNQueries``; ``detector.RelationDETRHead`` chains the two
+around the transformer.
 """
 from __future__ import annotations
 
