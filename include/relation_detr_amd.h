@@ -818,6 +818,53 @@ int rdetr_cdn_embed_backward_bf16(const uint16_t *grad_label_query, const int *n
                                   void *stream);
 int rdetr_cdn_noise(unsigned long long key, int Q, int C, float *label_u, long long *label_r, float *box_sign, float *box_u, void *stream);
 
+/* ---- optimizer step: clip_grad_norm_ + AdamW over a whole parameter set (csrc/optim.hip) ---------------------------------------
+ * The rest of the reference's step (util/engine.py:57-61, configs/train_config.py:14,42-46) in three launches whatever the tensor
+ * count, fp32, no atomics, the same bits on every run.  Three tables in device memory, 8-byte aligned, drive the launches:
+ *
+ *   tensors   [n_tensors]  built once: addresses of param, exp_avg, exp_avg_sq (fp32, contiguous), numel, and aligned16 != 0 when all
+ *                          three addresses are 16-byte aligned
+ *   steps     [n_tensors]  rewritten every step: the gradient's address (NULL: no gradient, the tensor is skipped) and the scalars of
+ *                          the tensor's parameter group as torch's single-tensor AdamW forms them in doubles, rounded to fp32:
+ *                          decay = 1 - lr * wd, 1 - beta1, beta2, 1 - beta2, step_size = lr / (1 - beta1^t), bias2_sqrt =
+ *                          sqrt(1 - beta2^t), eps
+ *   chunk_map [n_chunks]   chunk c covers elements [first, min(first + chunk, numel)) of tensor `tensor`; first is a multiple of
+ *                          chunk, chunk a multiple of 4 (else RDETR_ERR_UNSUPPORTED), so a chunk never crosses a tensor.  An entry
+ *                          whose tensor is outside [0, n_tensors) is skipped, never used as an index.
+ *
+ * Tensors whose three addresses and gradient are 16-byte aligned move as 16-byte vectors with a scalar numel % 4 tail, the others
+ * element by element.  One workgroup owns a chunk; the grid is min(n_chunks, max_blocks) workgroups (max_blocks <= 0: 2048) that
+ * walk the chunks with a stride, which changes no result.
+ *
+ * rdetr_optim_workspace_bytes(n_chunks): (n_chunks + 2) floats, the partials and behind them {total_norm, coef}.
+ * rdetr_grad_sqnorm_f32: ws[c] = the sum of squares of chunk c's gradient elements (0 without a gradient): a chain per lane and
+ *   vector component, then the lanes by shuffle, then the waves through LDS.
+ * rdetr_grad_clip_coef: one workgroup adds ws[0 .. n_chunks) in index order in fp64 and writes ws[n_chunks] = total_norm,
+ *   ws[n_chunks + 1] = coef = min(1, max_norm / (total_norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s formula.  Nothing goes to the
+ *   host.
+ * rdetr_adamw_step_f32: per element g = grad * coef (norm_coef[1]; 1 when norm_coef is NULL), param *= decay, exp_avg += (1 - beta1)
+ *   (g - exp_avg), exp_avg_sq = exp_avg_sq beta2 + (1 - beta2) g g, param -= step_size exp_avg / (sqrt(exp_avg_sq) / bias2_sqrt + eps).
+ *   Writes param, exp_avg and exp_avg_sq; the gradient is only read and keeps its unclipped value. */
+typedef struct rdetr_optim_tensor {
+    void *param, *exp_avg, *exp_avg_sq;
+    long long numel;
+    int aligned16, reserved;
+} rdetr_optim_tensor;
+typedef struct rdetr_optim_step {
+    const void *grad;
+    float decay, one_minus_beta1, beta2, one_minus_beta2, step_size, bias2_sqrt, eps, reserved;
+} rdetr_optim_step;
+typedef struct rdetr_optim_chunk {
+    long long first;
+    int tensor, reserved;
+} rdetr_optim_chunk;
+long long rdetr_optim_workspace_bytes(int n_chunks);
+int rdetr_grad_sqnorm_f32(const rdetr_optim_tensor *tensors, const rdetr_optim_step *steps, const rdetr_optim_chunk *chunk_map, int n_tensors,
+                          int n_chunks, int chunk, int max_blocks, void *ws, long long ws_bytes, void *stream);
+int rdetr_grad_clip_coef(void *ws, long long ws_bytes, int n_chunks, float max_norm, void *stream);
+int rdetr_adamw_step_f32(const rdetr_optim_tensor *tensors, const rdetr_optim_step *steps, const rdetr_optim_chunk *chunk_map, int n_tensors,
+                         int n_chunks, int chunk, int max_blocks, const float *norm_coef, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value
 from .criterion import RelationCriterion, SetLossFunction, hungarian_match, match_cost, set_loss
 from .denoising import CdnQueryFunction, GenerateCDNQueries, cdn_noise, cdn_queries, denoising_mask
 from .detector import RelationDETRHead
+from .optim import FusedAdamW, relation_param_groups, train_step
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -31,4 +32,5 @@ __all__ = [
     "AddLayerNormMixedFunction", "FeedForwardMixedFunction",
     "RelationCriterion", "SetLossFunction", "match_cost", "hungarian_match", "set_loss",
     "GenerateCDNQueries", "CdnQueryFunction", "cdn_queries", "cdn_noise", "denoising_mask", "RelationDETRHead",
+    "FusedAdamW", "relation_param_groups", "train_step",
 ]

@@ -113,6 +113,10 @@ SIGNATURES = {
     "rdetr_cdn_embed_backward_f32": [_vp, _vp] + [_c_int] * 3 + [_vp, _vp],
     "rdetr_cdn_embed_backward_bf16": [_vp, _vp] + [_c_int] * 3 + [_vp, _vp],
     "rdetr_cdn_noise": [_c_ull] + [_c_int] * 2 + [_vp] * 5,
+    "rdetr_optim_workspace_bytes": [_c_int],
+    "rdetr_grad_sqnorm_f32": [_vp] * 3 + [_c_int] * 4 + [_vp, _c_ll, _vp],
+    "rdetr_grad_clip_coef": [_vp, _c_ll, _c_int, _c_float, _vp],
+    "rdetr_adamw_step_f32": [_vp] * 3 + [_c_int] * 4 + [_vp, _vp],
 }
 
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3            # rdetr_status (include/relation_detr_amd.h)
