@@ -681,6 +681,21 @@ int rdetr_linear_ln_k256_bf16(const uint16_t *x, long long ldx, const uint16_t *
                               const uint16_t *residual, long long ldr, const uint16_t *gamma, const uint16_t *beta, float eps,
                               long long M, uint16_t *out, long long ldo, void *stream);
 
+/* A decoder layer's attention output projection + residual + LayerNorm in one launch, for SHORT row counts (csrc/rowtail.hip; 32 rows
+ * per workgroup where the kernel above has 256-row tiles):
+ *   out    [M, 256] = LayerNorm(residual + bf16(x[M, 256] w[256, 256]^T + bias); gamma, beta, eps)
+ *   out_pos[M, 256] = out + pos                                   when pos != NULL      (relation_transformer.py:452-463)
+ * self_attn.out_proj + norm2 (+ query_pos) and cross_attn.output_proj + norm1 of the decoder layer.
+ *   packed  w re-ordered by the pack entry above; row strides in elements, multiples of 8; every base and parameter vector 16-byte
+ *   aligned (anything else: RDETR_ERR_UNSUPPORTED); bias nullable; all bf16, fp32 accumulation and statistics.  M == 0: RDETR_OK,
+ *   no launch.
+ * The projection is rounded to bf16 before the residual is added and the sum is not rounded again: for the same sums `out` has the
+ * bits of the add + LayerNorm entries. */
+int rdetr_linear_ln_rows_bf16(const uint16_t *x, long long ldx, const uint16_t *packed, const uint16_t *bias,
+                              const uint16_t *residual, long long ldr, const uint16_t *gamma, const uint16_t *beta, float eps,
+                              const uint16_t *pos, long long ldp, long long M, uint16_t *out, long long ldo, uint16_t *out_pos,
+                              long long ldop, void *stream);
+
 /* Fused feed-forward block (csrc/ffn.hip): out[M, 256] = relu(x[M, 256] w1[F, 256]^T + b1[F]) w2[256, F]^T + b2[256], i.e.
  * linear2(relu(linear1(x))) of the encoder / decoder layers (models/bricks/relation_transformer.py:226-233, 272-275) without the
  * [M, F] activations ever reaching HBM.  bf16 storage, fp32 accumulation, the hidden activations rounded to bf16 where the unfused

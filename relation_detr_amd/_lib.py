@@ -78,6 +78,7 @@ SIGNATURES = {
     "rdetr_linear_k256_hm_bf16": [_vp, _c_ll, _vp, _vp, _vp, _c_int, _c_int, _vp, _vp],
     "rdetr_linear_pack_k256_bf16": [_vp, _vp, _vp],
     "rdetr_linear_ln_k256_bf16": [_vp, _c_ll, _vp, _vp, _vp, _c_ll, _vp, _vp, _c_float, _c_ll, _vp, _c_ll, _vp],
+    "rdetr_linear_ln_rows_bf16": [_vp, _c_ll, _vp, _vp, _vp, _c_ll, _vp, _vp, _c_float, _vp, _c_ll, _c_ll, _vp, _c_ll, _vp, _c_ll, _vp],
     "rdetr_ffn_k256_pack_bf16": [_vp, _vp, _c_int, _vp, _vp],
     "rdetr_ffn_k256_bf16": [_vp, _c_ll, _vp, _vp, _vp, _c_ll, _c_int, _vp, _c_ll, _vp],
     "rdetr_ffn_ln_k256_bf16": [_vp, _c_ll, _vp, _vp, _vp, _vp, _vp, _c_float, _vp, _c_ll, _c_ll, _c_int, _vp, _c_ll, _vp, _c_ll, _vp],

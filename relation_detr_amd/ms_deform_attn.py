@@ -16,7 +16,7 @@ import warnings
 import torch
 from torch import Tensor, nn
 
-from . import amp_train, ln_train, msda_train_hm, ops
+from . import amp_train, ln_train, msda_train_hm, ops, rowtail
 from . import options as _options
 
 
@@ -141,7 +141,8 @@ class MultiScaleDeformableAttention(nn.Module):
         [L,2] (h,w); level_start_index [L]; key_padding_mask [B,S] bool or None -> [B,Nq,C].
         ``post_norm = (residual, layer_norm)`` (not in the reference's signature, optional): return
         ``layer_norm(residual + output)`` -- the caller's next two steps (relation_transformer.py:270-271) -- which tall bf16
-        inference inputs get from the output projection's own epilogue (csrc/linear.hip).
+        inference inputs get from the output projection's own epilogue (csrc/linear.hip); ``(residual, layer_norm, True)`` lets
+        short ones (the decoder's few thousand rows) have it too (csrc/rowtail.hip).
         ``projected_value`` (not in the reference's signature, optional; bf16 inference): ``value_proj(value)`` WITHOUT the padding
         fill, already computed by the caller -- a [B,S,C] view that may be a column slice of a wider buffer (the decoder runs the
         value projections of its six layers as one GEMM, transformer.py).  Ignored unless the fused kernel path applies."""
@@ -259,8 +260,12 @@ class MultiScaleDeformableAttention(nn.Module):
             core = core.to(vdt)
         if post_norm is None:
             return self.output_proj(core)
-        residual, norm = post_norm
-        if (core.is_cuda and not torch.is_grad_enabled() and core.numel() // core.shape[-1] >= 16384
+        residual, norm = post_norm[:2]
+        rows = core.numel() // core.shape[-1]
+        # tall inputs (the encoder): the 256-row-tile kernel of csrc/linear.hip; short ones, where the caller allows it with a third
+        # element (the decoder layer): the 32-row kernel of csrc/rowtail.hip.  Between the two, and for an encoder of a few thousand
+        # rows, the library GEMM + the add+LayerNorm kernel as before
+        if (core.is_cuda and not torch.is_grad_enabled() and (rows >= 16384 or (len(post_norm) == 3 and rowtail.takes(rows)))
                 and self.options.proj_ln and norm.weight is not None and norm.bias is not None
                 and ops.linear_ln_k256_supported(core, self.output_proj.weight, residual)):
             return ops.linear_ln_k256(core, self.output_proj.weight, self.output_proj.bias, residual, norm.weight, norm.bias, norm.eps)

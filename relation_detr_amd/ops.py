@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, rowtail
 
 
 _KEEP: "collections.deque" = collections.deque(maxlen=64)
@@ -1560,16 +1560,26 @@ def linear_ln_k256_supported(x: torch.Tensor, weight: torch.Tensor, residual: to
 
 
 def linear_ln_k256(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], residual: torch.Tensor,
-                   gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """``LayerNorm(residual + F.linear(x, weight, bias))`` for bf16 [..., 256] tensors and a [256, 256] weight in one kernel
-    (MSDA's output_proj + the layer's norm1, ms_deform_attn.py:372-376 / relation_transformer.py:262-271).  Inference only."""
+                   gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5, out: Optional[torch.Tensor] = None,
+                   extra: Optional[dict] = None) -> torch.Tensor:
+    """``LayerNorm(residual + F.linear(x, weight, bias))`` for bf16 [..., 256] tensors and a [256, 256] weight in one kernel; the
+    projection is rounded to bf16 before the residual is added, as the unfused route stores it.  Inference only.
+    More than ``rowtail.MAX_ROWS`` rows: MSDA's output_proj + the encoder layer's norm1 (ms_deform_attn.py:372-376 /
+    relation_transformer.py:262-271; csrc/linear.hip).  Fewer: the decoder layer's two attention tails (csrc/rowtail.hip), where
+    ``extra`` -- a dict -- carries what else the launch produces: ``"pos"`` in, ``"out_plus_pos"`` out (``out + pos``, the
+    cross-attention's query), and ``"out"``, the returned tensor.  A non-empty ``extra`` above the row threshold is not supported."""
     _require_device(x, weight, bias, residual, gamma, beta, out)
     if not linear_ln_k256_supported(x, weight, residual):
         raise _lib.RdetrError("linear_ln_k256: needs bf16 [..., 256] inputs with evenly strided 16-byte aligned rows and a [256, 256] weight")
+    rows, _, ldx = _rows_view(x, "linear_ln_k256")
+    if rowtail.takes(rows):
+        return rowtail.linear_ln_rows(x, weight, bias, residual, gamma, beta, eps, out, extra, rows_view=_rows_view,
+                                      packed=_packed_k256(weight), keep=_KEEP)
+    if extra:
+        raise _lib.RdetrError(f"linear_ln_k256: `extra` is not supported above {rowtail.MAX_ROWS} rows")
     for t in (bias, gamma, beta):
         if t is not None and (t.dtype != torch.bfloat16 or t.numel() != 256):
             raise _lib.RdetrError("linear_ln_k256: bias / gamma / beta must be bf16 [256]")
-    rows, _, ldx = _rows_view(x, "linear_ln_k256")
     _, _, ldr = _rows_view(residual, "linear_ln_k256")
     if out is None:
         out = torch.empty(x.shape, dtype=x.dtype, device=x.device)

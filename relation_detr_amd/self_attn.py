@@ -18,7 +18,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
-from . import ops, options
+from . import ops, options, rowtail
 from .attn_rel_train import RelationAttentionBoxesFunction
 from .relation import DeferredRelationBias
 
@@ -62,10 +62,15 @@ class RelationSelfAttention(nn.Module):
         self.options = options.get()
 
     def forward(self, query: Tensor, key: Tensor, value: Tensor, attn_mask: Optional[Tensor] = None,
-                need_weights: bool = False, key_padding_mask: Optional[Tensor] = None, projected=None):
+                need_weights: bool = False, key_padding_mask: Optional[Tensor] = None, projected=None, post_norm=None):
         """``projected`` (not in nn.MultiheadAttention's signature, optional): ``(qk, v)``, the in-projections of ``query`` (= ``key``)
         and ``value`` if the caller already has them (the decoder's query-position kernel, csrc/qpos.hip); used on the bf16
-        no-grad path when their shapes and dtypes fit, ignored otherwise."""
+        no-grad path when their shapes and dtypes fit, ignored otherwise.
+        ``post_norm = (residual, layer_norm, extra)`` (not in nn.MultiheadAttention's signature, optional): on the bf16 inference
+        branches, where `ops.linear_ln_k256` has a short-row kernel for the operands, return ``layer_norm(residual + output)`` --
+        the caller's next two steps (relation_transformer.py:456-459) -- from the output projection's own launch
+        (csrc/rowtail.hip); ``extra`` is that entry's dict and holds ``"out"`` afterwards.  Left untouched otherwise: the caller
+        tells by the key whether the norm has been applied."""
         if need_weights or key_padding_mask is not None:
             raise NotImplementedError("need_weights / key_padding_mask are not used on this path")
         B, N, C = query.shape
@@ -97,7 +102,7 @@ class RelationSelfAttention(nn.Module):
                 ctx = ops.relation_attention_boxes(q, k, v, H, rel.src_boxes, rel.tgt_boxes, conv.weight, conv.bias, rel.attn_mask,
                                                    1.0 / math.sqrt(d), rel.module.num_pos_feats, rel.module.temperature,
                                                    rel.module.scale)
-                return self.out_proj(ctx), None
+                return self._inference_output(ctx, post_norm), None
             if (self.options.rel_train_fused and torch.is_grad_enabled() and (needs_grad or conv.weight.requires_grad)
                     and q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and v.dtype == torch.bfloat16
                     and d == 32 and H == 8 and rel.module.num_pos_feats == 16 and (self.dropout == 0.0 or not self.training)
@@ -131,7 +136,7 @@ class RelationSelfAttention(nn.Module):
             is_bool = attn_mask is not None and attn_mask.dtype == torch.bool
             ctx = ops.relation_attention(q, k, v, H, None if attn_mask is None or is_bool else attn_mask.float(),
                                          attn_mask if is_bool else None, 1.0 / math.sqrt(d))
-            return self.out_proj(ctx), None
+            return self._inference_output(ctx, post_norm), None
         # The library's batched GEMMs get DENSE per-head operands [B, H, N, d].  As views of the packed projections (q / k:
         # column slices with row stride 2C, heads interleaved inside a row) the batch of one image folds into a strided-
         # batched GEMM with batch stride d and leading dimension 2C, i.e. matrices that OVERLAP in memory -- legal for the
@@ -156,3 +161,14 @@ class RelationSelfAttention(nn.Module):
             probs = F.dropout(probs, self.dropout)
         ctx = torch.matmul(probs.view(B, H, N, M).to(v.dtype), v).transpose(1, 2).reshape(B, N, C)
         return self.out_proj(ctx), None
+
+    def _inference_output(self, ctx: Tensor, post_norm) -> Tensor:
+        """``out_proj(ctx)`` or, with ``post_norm``, the projection, the caller's residual and its LayerNorm in one launch."""
+        if post_norm is not None and self.options.proj_ln:
+            residual, norm, extra = post_norm
+            proj = self.out_proj
+            if (type(norm) is nn.LayerNorm and norm.elementwise_affine and norm.bias is not None and proj.bias is not None
+                    and rowtail.takes(ctx.numel() // ctx.shape[-1]) and ops.linear_ln_k256_supported(ctx, proj.weight, residual)
+                    and all(p.dtype == torch.bfloat16 for p in (proj.bias, norm.weight, norm.bias))):
+                return ops.linear_ln_k256(ctx, proj.weight, proj.bias, residual, norm.weight, norm.bias, norm.eps, extra=extra)
+        return self.out_proj(ctx)

@@ -23,7 +23,7 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
-from . import amp_train, ffn_train, ln_train, ops
+from . import amp_train, ffn_train, ln_train, ops, rowtail
 from . import options as _options
 from .ms_deform_attn import MultiScaleDeformableAttention
 from .relation import PositionRelationEmbedding
@@ -266,20 +266,38 @@ class RelationTransformerDecoderLayer(nn.Module):
         ``projected_value``: ``cross_attn.value_proj(value)`` if the caller already has it (see the decoder); ``projected``: the
         self-attention's in-projections ``(qk, v)`` of ``query_plus_pos`` and ``query`` if the caller already has them."""
         qp = query + query_pos if query_plus_pos is None else query_plus_pos
+        ln_pos = (query.is_cuda and not torch.is_grad_enabled() and query.dtype in (torch.float32, torch.bfloat16)
+                  and query_pos.dtype == query.dtype and query_pos.shape == query.shape and self.options.decoder_ln_pos)
+        # bf16 inference: the two "attention output projection -> + residual -> LayerNorm" tails of the layer as ONE launch each
+        # (csrc/rowtail.hip) instead of a library GEMM and an add+LayerNorm pass over what it has just written -- 15 -> 13 launches
+        # on the decoder's dependent chain.  options.proj_ln = False keeps the GEMMs and the passes.  (linear2 + norm3 + the
+        # decoder's norm stay three launches: one kernel for them measured slower, csrc/rowtail.hip "dropped")
+        tails = (query.is_cuda and not torch.is_grad_enabled() and query.dtype == torch.bfloat16 and query.shape[-1] == 256
+                 and self.options.proj_ln and rowtail.takes(query.numel() // 256))
+        # norm2 with the cross-attention's `query + query_pos` (without decoder_ln_pos: the unfused pair, as before)
+        post = {"pos": query_pos} if tails and ln_pos and type(self.self_attn) is RelationSelfAttention else None
         attn = self.self_attn(query=qp, key=qp, value=query, attn_mask=self_attn_mask, need_weights=False,
-                              **({} if projected is None else {"projected": projected}))[0]
-        if (query.is_cuda and not torch.is_grad_enabled() and query.dtype in (torch.float32, torch.bfloat16)
-                and query_pos.dtype == query.dtype and query_pos.shape == query.shape and self.options.decoder_ln_pos):
+                              **({} if projected is None else {"projected": projected}),
+                              **({} if post is None else {"post_norm": (query, self.norm2, post)}))[0]
+        if post is not None and "out" in post:
+            query, cross_q = attn, post["out_plus_pos"]
+        elif ln_pos:
             # inference: norm2 and the cross-attention's `query + query_pos` from one pass (csrc/layernorm.hip)
             query, cross_q = ops.add_layer_norm(attn, query, self.norm2.weight, self.norm2.bias, self.norm2.eps, pos=query_pos)
         else:
             query = add_norm(self.norm2, query, attn, opts=self.options)
             cross_q = query + query_pos
-        cross = self.cross_attn(query=cross_q, reference_points=reference_points, value=value,
-                                spatial_shapes=spatial_shapes, level_start_index=level_start_index,
-                                key_padding_mask=key_padding_mask,
-                                **({} if projected_value is None else {"projected_value": projected_value}))
-        query = add_norm(self.norm1, query, cross, opts=self.options)
+        if tails and type(self.cross_attn).forward is MultiScaleDeformableAttention.forward:        # not a subclass with its own forward
+            query = self.cross_attn(query=cross_q, reference_points=reference_points, value=value,
+                                    spatial_shapes=spatial_shapes, level_start_index=level_start_index,
+                                    key_padding_mask=key_padding_mask, post_norm=(query, self.norm1, True),     # norm1(query + cross)
+                                    **({} if projected_value is None else {"projected_value": projected_value}))
+        else:
+            cross = self.cross_attn(query=cross_q, reference_points=reference_points, value=value,
+                                    spatial_shapes=spatial_shapes, level_start_index=level_start_index,
+                                    key_padding_mask=key_padding_mask,
+                                    **({} if projected_value is None else {"projected_value": projected_value}))
+            query = add_norm(self.norm1, query, cross, opts=self.options)
         return add_norm(self.norm3, query, feed_forward(self.linear1, self.linear2, query, self.options), opts=self.options)
 
 
