@@ -786,6 +786,28 @@ int rdetr_set_loss_bf16(const uint16_t *logits, long long ld_logits, const float
                         float *dbox_l1, float *dbox_giou, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The matcher's assignment on the device (csrc/assign.hip).  Replaces, per set and image, scipy's linear_sum_assignment in
+ * HungarianMatcher.forward (models/matcher/hungarian_matcher.py:72-100) and the host-built match table of the criterion.
+ *
+ * cost [R, N, Gmax] fp32 contiguous is what rdetr_match_cost_* fills; row r belongs to image r % B (R a multiple of B) and uses
+ * the first g = gt_count[r % B] columns (clamped to [0, Gmax]).  One workgroup solves the rectangular assignment of the
+ * N x (g * repeat) matrix whose column k is cost column k % g (the hybrid branch's repeated targets, never materialised), by the
+ * shortest-augmenting-path method scipy runs, in its arithmetic (fp64 duals and path costs over the fp32 costs): min(N, g *
+ * repeat) pairs of minimal total cost, scipy's own pairs wherever the optimum is unique.  Among equal minima a search prefers a
+ * free column, then the lower index; the result depends on the inputs alone.  No atomics, no workspace.
+ *
+ *   match  [R, >= skip + N] int32, rows ld_match elements apart; all of a row's first skip + N entries are written, nothing else:
+ *          entry skip + q the gt index (modulo g) of query q or -1; entry grp * dn_max_gt + t of the first skip = dn_groups *
+ *          dn_max_gt (the fixed matches of the denoising queries) t where t < g, else -1.  g = 0: the whole row -1.
+ *   status [R] int32: 0, or 1 where a cost of the row's used columns is NaN or an infinity (scipy raises there): the row's
+ *          matcher entries are then all -1, its denoising entries as above, and every other row is unaffected.
+ *
+ * Every loop of the kernel is bounded by the sizes, whatever the cost bits.  N <= 2048 and Gmax * repeat <= 2048 (else
+ * RDETR_ERR_UNSUPPORTED, nothing launched); bases 4-byte aligned; R = 0 returns RDETR_OK without a launch. */
+int rdetr_assign_match(const float *cost, const int *gt_count, int R, int B, int N, int Gmax, int repeat, int skip, int dn_groups,
+                       int dn_max_gt, int *match, long long ld_match, int *status, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Denoising query generator (csrc/denoising.hip, csrc/cdn_noise.h): GenerateCDNQueries.forward
  * (models/bricks/denoising.py:180-331) without its loops over images and groups, its host-built index tensors and its two
  * scatter assignments.  The caller allocates; nothing here allocates or waits for the device; zero work returns RDETR_OK without

@@ -15,7 +15,7 @@ from .ffn_train import FeedForwardFunction, ffn_k256_backward, ffn_k256_train
 from .ln_train import AddLayerNormFunction
 from .amp_train import AddLayerNormMixedFunction, FeedForwardMixedFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
-from .criterion import RelationCriterion, SetLossFunction, hungarian_match, match_cost, set_loss
+from .criterion import RelationCriterion, SetLossFunction, assign_match, hungarian_match, match_cost, set_loss
 from .denoising import CdnQueryFunction, GenerateCDNQueries, cdn_noise, cdn_queries, denoising_mask
 from .detector import RelationDETRHead
 from .optim import FusedAdamW, relation_param_groups, train_step
@@ -30,7 +30,7 @@ __all__ = [
     "FeedForwardFunction", "ffn_k256_train", "ffn_k256_backward", "AddLayerNormFunction",
     "MultiScaleDeformableAttnHeadMajorFunction", "ms_deform_attn_backward_fused_hm", "grad_value_from_head_major",
     "AddLayerNormMixedFunction", "FeedForwardMixedFunction",
-    "RelationCriterion", "SetLossFunction", "match_cost", "hungarian_match", "set_loss",
+    "RelationCriterion", "SetLossFunction", "match_cost", "hungarian_match", "assign_match", "set_loss",
     "GenerateCDNQueries", "CdnQueryFunction", "cdn_queries", "cdn_noise", "denoising_mask", "RelationDETRHead",
     "FusedAdamW", "relation_param_groups", "train_step",
 ]

@@ -108,6 +108,7 @@ SIGNATURES = {
     "rdetr_set_loss_workspace_bytes": [_c_int, _c_int],
     "rdetr_set_loss_f32": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float] * 4 + [_vp, _c_ll] + [_vp] * 5,
     "rdetr_set_loss_bf16": [_vp, _c_ll, _vp, _c_ll, _vp, _vp, _vp] + [_c_int] * 6 + [_c_float] * 4 + [_vp, _c_ll] + [_vp] * 5,
+    "rdetr_assign_match": [_vp, _vp] + [_c_int] * 8 + [_vp, _c_ll, _vp, _vp],
     "rdetr_cdn_queries_f32": [_vp] * 3 + [_c_int] * 6 + [_c_float] * 2 + [_vp] * 5 + [_c_int, _c_ull] + [_vp] * 4,
     "rdetr_cdn_queries_bf16": [_vp] * 3 + [_c_int] * 6 + [_c_float] * 2 + [_vp] * 5 + [_c_int, _c_ull] + [_vp] * 4,
     "rdetr_cdn_mask": [_c_int] * 3 + [_vp, _vp],

@@ -7,17 +7,19 @@ hybrid branch with the targets repeated ``hybrid_assign`` times, and ``compute_d
 Two routes, chosen by the constructor's ``fused`` (CPU tensors always take the second):
 
 * fused -- every decoder layer's set is one row of a stack.  ``match_cost`` fills the cost matrices of a whole stack in one launch
-  (up to four per step: decoder, encoder proposals, hybrid decoder, hybrid proposals) into one buffer, which goes to the host in
-  one copy, the step's only synchronisation; scipy solves the assignments; the match tables, the fixed denoising matches among
-  them, come back in one copy; ``set_loss`` computes every loss and gradient of a stack in one pass.
+  (up to four per step: decoder, encoder proposals, hybrid decoder, hybrid proposals) into one buffer; ``assign_match`` turns it
+  into the match tables, the fixed denoising matches among them; ``set_loss`` computes every loss and gradient of a stack in one
+  pass.  The constructor's ``matcher`` says where the assignments are solved: ``"scipy"`` (the default) copies the buffer to the
+  host, the step's only synchronisation, solves there and copies the tables back; ``"device"`` solves every stack with one launch
+  of ``rdetr_assign_match`` (csrc/assign.hip) straight into the device table: no copy, and nothing waits for the device.
 * torch -- a restatement of the reference, set by set and image by image: ``HungarianMatcher.calculate_cost``
   (``models/matcher/hungarian_matcher.py:41-70``), ``HybridSetCriterion.loss_labels``, ``SetCriterion.loss_boxes``
   (``models/bricks/set_criterion.py:84-106,178-216``) and ``vari_sigmoid_focal_loss`` (``models/bricks/losses.py:15-21``), with
   the box IoU / GIoU written from their formulas.  It is what the fused route is timed against and, in float64, what it is checked
   against.
 
-``match_cost``, ``hungarian_match`` and ``set_loss`` are the three pieces, usable alone.  Not built: the plain focal
-``SetCriterion``, ``ia_bce_loss``, ``two_stage_binary_cls``, ``mixed_match`` and a device-side assignment solver.  The denoising
+``match_cost``, ``hungarian_match`` / ``assign_match`` and ``set_loss`` are the pieces, usable alone.  Not built: the plain focal
+``SetCriterion``, ``ia_bce_loss``, ``two_stage_binary_cls`` and ``mixed_match``.  The denoising
 query generator whose ``dn_meta`` this takes is ``denoising.GenerateCDNQueries``; ``detector.RelationDETRHead`` chains the two
 around the transformer.
 """
@@ -36,6 +38,7 @@ from .ops import _require_device, _stream_ptr
 
 _DTYPES = (torch.float32, torch.bfloat16)
 MAX_GT = 2048                    # kCostMaxGt: one image's gt table has to fit the cost kernel's LDS
+MAX_ASSIGN = 2048                # kAssignMaxSide: queries, and Gmax * repeat target copies, of one problem of the device matcher
 
 
 # ------------------------------------------------------------------------------------------------------------------ torch route
@@ -245,6 +248,83 @@ def hungarian_match(cost, gt_count: Sequence[int], repeat: int = 1) -> List[Tupl
     return pairs
 
 
+def _dn_groups(skip: int, dn_meta) -> Tuple[int, int]:
+    if not skip:
+        return 0, 0
+    if dn_meta is None or int(dn_meta[0]) * int(dn_meta[1]) != skip or skip < 0:
+        raise ValueError("assign_match: skip has to be dn_meta's groups * max_gt")
+    return int(dn_meta[0]), int(dn_meta[1])
+
+
+def assign_match(cost: Tensor, gt_count, repeat: int = 1, skip: int = 0, dn_meta=None, out: Optional[Tensor] = None,
+                 fused: bool = True) -> Tuple[Tensor, Tensor]:
+    """The match table ``set_loss`` reads, from a cost stack ``[R, N, Gmax]`` -> (match int32 [R, skip + N], status int32 [R]).
+
+    Row ``r`` is solved over the first ``gt_count[r % B]`` columns tiled ``repeat`` times, as ``hungarian_match`` solves it: entry
+    ``skip + q`` holds query q's gt index or -1.  The first ``skip = groups * max_gt`` entries (``dn_meta``) are the denoising
+    queries' fixed matches: entry ``grp * max_gt + t`` is ``t`` where ``t`` is below the image's count, else -1.  ``out``, when
+    given, is an int32 table of R rows and at least ``skip + N`` columns (a column slice of a wider one will do); only those
+    columns are written.  ``status[r]`` is 1 where the row's costs are not all finite (its matcher entries are then -1), else 0.
+
+    fp32 device tensors (cost contiguous, gt_count int32 [B]) go to ``rdetr_assign_match``, which enqueues one launch and never
+    waits for the device; CPU tensors, or ``fused=False``, go through scipy on the host (``gt_count`` may then be a sequence)."""
+    R, N, Gmax = cost.shape
+    groups, max_gt = _dn_groups(int(skip), dn_meta)
+    if repeat < 1:
+        raise ValueError("assign_match: repeat has to be at least 1")
+    if out is not None and (out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] != R or out.shape[1] < skip + N
+                            or (out.shape[1] > 1 and out.stride(1) != 1)):
+        raise _lib.RdetrError("assign_match: out has to be int32 [R, >= skip + N] with unit column stride")
+    if not (fused and cost.is_cuda):
+        counts = [int(c) for c in (gt_count.tolist() if torch.is_tensor(gt_count) else gt_count)]
+        B = len(counts)
+        if B < 1 or R % B:
+            raise ValueError(f"assign_match: the {R} rows are not a multiple of the {B} images")
+        host = cost.detach().cpu()
+        table = torch.empty(R, skip + N, dtype=torch.int32) if out is None or out.is_cuda else out
+        table[:, :skip + N] = -1
+        status = torch.zeros(R, dtype=torch.int32)
+        try:
+            pairs = hungarian_match(host, counts, repeat)
+        except ValueError:                                                    # scipy refuses a matrix with NaN or -inf: row by row
+            pairs = []
+            for r in range(R):
+                try:
+                    pairs += hungarian_match(host[r:r + 1], counts[r % B:r % B + 1], repeat)
+                except ValueError:
+                    pairs.append((torch.zeros(0, dtype=torch.int64),) * 2)
+                    status[r] = 1
+        for r, (src, tgt) in enumerate(pairs):
+            table[r, src + skip] = tgt.to(torch.int32)
+        if skip:                                                              # the denoising queries: group g, target t -> gt t
+            slot = torch.arange(max_gt, dtype=torch.int32)
+            for b in range(B):
+                fixed = torch.where(slot < counts[b], slot, slot.new_tensor(-1)).repeat(groups)
+                table[b::B, :skip] = fixed
+        if table is not out and out is not None:
+            out[:, :skip + N] = table.to(out.device)
+            table = out
+        return table[:, :skip + N], status.to(cost.device)
+    if not torch.is_tensor(gt_count):
+        raise _lib.RdetrError("assign_match: gt_count has to be a device tensor on the device route")
+    _require_device(cost, gt_count)
+    if cost.dtype != torch.float32 or not cost.is_contiguous():
+        raise _lib.RdetrError("assign_match: cost has to be a contiguous fp32 device tensor [R, N, Gmax]")
+    B = gt_count.numel()
+    if gt_count.dtype != torch.int32 or not gt_count.is_contiguous() or B < 1 or R % B:
+        raise _lib.RdetrError("assign_match: gt_count has to be contiguous int32 [B] with R a multiple of B")
+    if out is None:
+        out = torch.empty(R, skip + N, dtype=torch.int32, device=cost.device)
+    elif not out.is_cuda:
+        raise _lib.RdetrError("assign_match: out has to be a device tensor on the device route")
+    status = torch.empty(R, dtype=torch.int32, device=cost.device)
+    ld = out.stride(0) if R > 1 else max(out.shape[1], 1)
+    st = _lib.load().rdetr_assign_match(cost.data_ptr(), gt_count.data_ptr(), R, B, N, Gmax, int(repeat), int(skip), groups, max_gt,
+                                        out.data_ptr(), ld, status.data_ptr(), _stream_ptr(cost))
+    _lib.check(st, "rdetr_assign_match")
+    return out[:, :skip + N], status
+
+
 def set_loss_forward(logits: Tensor, boxes: Tensor, match: Tensor, gt_boxes: Tensor, gt_labels: Tensor, n_split: int, inv_norm_a: float,
                      inv_norm_b: float, alpha: float = 0.25, gamma: float = 2.0):
     """One pass of ``rdetr_set_loss_*`` -> (sums [R, 2, 3] fp32, dlogits [R, N, C] in the logits' dtype, dbox_l1, dbox_giou [R, N, 4]
@@ -330,12 +410,18 @@ class RelationCriterion(nn.Module):
     ``groups * max_gt`` queries of ``outputs[0]`` / ``outputs[1]`` are the denoising queries, query ``g * max_gt + t`` matched to
     gt ``t``.  Returns the weighted dict of ``relation_detr.py:124-141``: ``loss_{class,bbox,giou}`` of the last decoder layer, the
     same with ``_{i}`` per earlier layer and ``_enc`` for the encoder proposals; ``_dn`` / ``_dn_{i}`` with ``dn_meta``; all of the
-    first group again with ``_hybrid`` where the hybrid outputs are present."""
+    first group again with ``_hybrid`` where the hybrid outputs are present.
+
+    ``matcher`` ("scipy" or "device") chooses the fused route's assignment solver; a step whose shapes exceed ``MAX_ASSIGN``
+    takes the scipy path.  The device matcher's ``status`` is not read inside the step (that would be a wait for the device): a
+    cost that is not finite comes from predictions that are not finite, and those already give losses that are not finite."""
 
     def __init__(self, num_classes: int, cost_class: float = 2.0, cost_bbox: float = 5.0, cost_giou: float = 2.0, loss_class: float = 1.0,
                  loss_bbox: float = 5.0, loss_giou: float = 2.0, alpha: float = 0.25, gamma: float = 2.0, hybrid_assign: int = 6,
-                 fused: bool = True, two_stage_binary_cls: bool = False, mixed_match: bool = False):
+                 fused: bool = True, two_stage_binary_cls: bool = False, mixed_match: bool = False, matcher: str = "scipy"):
         super().__init__()
+        if matcher not in ("scipy", "device"):
+            raise ValueError(f"RelationCriterion: matcher has to be 'scipy' or 'device', got {matcher!r}")
         if two_stage_binary_cls or mixed_match:
             raise NotImplementedError("RelationCriterion: two_stage_binary_cls and mixed_match are not built")
         if cost_class == 0 and cost_bbox == 0 and cost_giou == 0:
@@ -346,6 +432,7 @@ class RelationCriterion(nn.Module):
         self.alpha, self.gamma = float(alpha), float(gamma)
         self.hybrid_assign = int(hybrid_assign)
         self.fused = bool(fused)
+        self.matcher = matcher
 
     # -- shared
     @staticmethod
@@ -467,30 +554,37 @@ class RelationCriterion(nn.Module):
                 match_cost(lg[:, skip:], bx[:, skip:], gt_boxes, gt_labels, gt_count, *self.costs, self.alpha, self.gamma,
                            out=cost_dev[start:start + size])
                 start += size
-        cost_host = torch.empty(cost_dev.shape, dtype=torch.float32, pin_memory=True)
-        cost_host.copy_(cost_dev, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(dev))
-        done.synchronize()                                                    # the step's only wait for the device
-
-        match_host = torch.full((sum(lg.shape[0] * lg.shape[1] for _, lg, *_ in stacks),), -1, dtype=torch.int32).pin_memory()
-        tables, start, at = [], 0, 0
-        for (_, lg, _, skip, rep, _), size in zip(stacks, sizes):
-            R, N = lg.shape[:2]
-            table = match_host[at:at + R * N].view(R, N)
-            pairs = hungarian_match(cost_host[start:start + size].view(R, N - skip, Gmax), counts, rep)
-            for r, (src, tgt) in enumerate(pairs):
-                table[r, src + skip] = tgt.to(torch.int32)
-            if skip:                                                          # the denoising queries: group g, target t -> gt t
-                groups, max_gt = int(dn_meta[0]), int(dn_meta[1])
-                slot = torch.arange(max_gt, dtype=torch.int32)
-                for b in range(B):
-                    fixed = torch.where(slot < counts[b], slot, slot.new_tensor(-1)).repeat(groups)
-                    table.view(R // B, B, N)[:, b, :skip] = fixed
-            tables.append((at, R, N))
-            start += size
-            at += R * N
-        match_dev = match_host.to(dev, non_blocking=True)
+        shapes = [(lg.shape[0], lg.shape[1]) for _, lg, *_ in stacks]
+        ats = [sum(R * N for R, N in shapes[:k]) for k in range(len(shapes))]
+        tables = [(at, R, N) for at, (R, N) in zip(ats, shapes)]
+        device = self.matcher == "device" and all(N - skip <= MAX_ASSIGN and Gmax * rep <= MAX_ASSIGN
+                                                  for (_, N), (_, _, _, skip, rep, _) in zip(shapes, stacks))
+        if device:                                                            # no copy, no wait: the tables are solved where they are
+            match_dev = torch.empty(sum(R * N for R, N in shapes), dtype=torch.int32, device=dev)
+            start = at = k = 0
+            while k < len(stacks):
+                (R, N), (_, _, _, skip, rep, _) = shapes[k], stacks[k]
+                # neighbours of one shape (a branch's layers and its proposals) are one taller stack, in both buffers: one launch,
+                # and twice the workgroups of a kernel that is latency-bound
+                while k + 1 < len(stacks) and (shapes[k + 1][1], *stacks[k + 1][3:5]) == (N, skip, rep):
+                    k += 1
+                    R += shapes[k][0]
+                assign_match(cost_dev[start:start + R * (N - skip) * Gmax].view(R, N - skip, Gmax), gt_count, rep, skip,
+                             dn_meta if skip else None, out=match_dev[at:at + R * N].view(R, N))
+                start, at, k = start + R * (N - skip) * Gmax, at + R * N, k + 1
+        else:
+            cost_host = torch.empty(cost_dev.shape, dtype=torch.float32, pin_memory=True)
+            cost_host.copy_(cost_dev, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+            done.synchronize()                                                # the step's only wait for the device
+            match_host = torch.empty(sum(R * N for R, N in shapes), dtype=torch.int32).pin_memory()
+            start = 0
+            for (_, _, _, skip, rep, _), size, (at, R, N) in zip(stacks, sizes, tables):
+                assign_match(cost_host[start:start + size].view(R, N - skip, Gmax), counts, rep, skip, dn_meta if skip else None,
+                             out=match_host[at:at + R * N].view(R, N))
+                start += size
+            match_dev = match_host.to(dev, non_blocking=True)
 
         losses: Dict[str, Tensor] = {}
         weights = torch.tensor(self.weights, dtype=torch.float32).pin_memory().to(dev, non_blocking=True)

@@ -1,11 +1,13 @@
-"""A/B of the training criterion: RelationCriterion(fused=True) against its torch route (fused=False, the reference's loops),
-forward + backward, same process, same inputs, alternating.
+"""A/B of the training criterion: RelationCriterion(fused=True) with scipy's solver on the host ("fused"), the same with the
+assignments solved on the device ("device", matcher="device": csrc/assign.hip) and the torch route (fused=False, the reference's
+loops), forward + backward, same process, same inputs, alternating.
 
 Shapes of the R50 configuration: 6 decoder layers, 900 matching + 200 denoising queries, 1500 hybrid queries, 91 classes; B = 2 and
 4 images with 7 and 20 boxes each.  Per route and shape:
   wall      host clock from an idle device (synchronised before) to the synchronise after backward, median and spread of the runs,
-            and the part of it spent inside scipy's linear_sum_assignment, which both routes call
-  device    sum of the kernel and copy durations of one step (torch.profiler, a pass of its own)
+            and the part of it spent inside scipy's linear_sum_assignment, which the fused and the torch route call
+  device    sum of the kernel and copy durations of one step (torch.profiler, a pass of its own); for the device matcher also
+            the part of it inside assign_match_kernel and that kernel's launches
   launches  kernels + device copies of that step;  syncs: runtime calls that wait for the device (synchronise calls and blocking copies)
 
 Run on the GPU:  python tools/time_criterion.py [--runs 20]      (--rehearse: tiny shapes on the CPU, torch route only, no timings)
@@ -33,6 +35,7 @@ def make_inputs(L, B, C, nq, n_dn, nh, boxes_per_image, device, seed=0):
 
 
 SOLVER = {"seconds": 0.0}
+ASSIGN = {"us": 0.0, "launches": 0}                 # the assignment kernel's share of the last profiled step
 
 
 def time_the_solver():
@@ -64,10 +67,15 @@ def profile_step(criterion, outs, targets, dn_meta):
         step(criterion, outs, targets, dn_meta)
         torch.cuda.synchronize()
     device_us, launches, waits = 0.0, 0, {}
+    ASSIGN["us"], ASSIGN["launches"] = 0.0, 0
     for e in prof.events():
         if str(e.device_type).endswith("CUDA"):
-            device_us += e.device_time if hasattr(e, "device_time") else e.cuda_time
+            us = e.device_time if hasattr(e, "device_time") else e.cuda_time
+            device_us += us
             launches += 1
+            if "assign_match_kernel" in e.name:
+                ASSIGN["us"] += us
+                ASSIGN["launches"] += 1
         elif "Synchronize" in e.name or e.name in ("hipMemcpyWithStream", "hipMemcpy"):
             waits[e.name] = waits.get(e.name, 0) + 1
     if "hipDeviceSynchronize" in waits:                                               # the synchronise that closes the window
@@ -97,7 +105,8 @@ def main():
             max_gt = 8 if G == 7 else 20                                              # 25 x 8 and 10 x 20 denoising queries: 200
             dn_meta = (200 // max_gt, max_gt)
             outs, targets = make_inputs(6, B, 91, 900, 200, 1500, G, dev)
-            routes = {"fused": RelationCriterion(91, fused=True), "torch": RelationCriterion(91, fused=False)}
+            routes = {"fused": RelationCriterion(91, fused=True), "device": RelationCriterion(91, fused=True, matcher="device"),
+                      "torch": RelationCriterion(91, fused=False)}
             values = {}
             for name, c in routes.items():
                 for _ in range(3):
@@ -115,10 +124,12 @@ def main():
                     torch.cuda.synchronize()
                     wall[name].append((time.perf_counter() - t0) * 1e3)
                     solver[name] += SOLVER["seconds"] * 1e3 / args.runs
-            print(f"B = {B}, {G} boxes per image, dn_meta = {dn_meta}: {len(values['torch'])} losses, worst |fused - torch| / max(1, |torch|) = {worst:.2e}")
+            same = all(torch.equal(values["device"][k], values["fused"][k]) for k in values["fused"])
+            print(f"B = {B}, {G} boxes per image, dn_meta = {dn_meta}: {len(values['torch'])} losses, worst |fused - torch| / max(1, |torch|) = {worst:.2e}, "
+                  f"device matcher's losses {'equal' if same else 'DIFFER from'} the scipy matcher's bit for bit")
             for name, c in routes.items():
                 w = wall[name]
-                line = f"  {name:5s} wall {statistics.median(w):8.2f} ms ({min(w):.2f} - {max(w):.2f}), of which scipy's solver {solver[name]:6.2f} ms (mean)"
+                line = f"  {name:6s} wall {statistics.median(w):8.2f} ms ({min(w):.2f} - {max(w):.2f}), of which scipy's solver {solver[name]:6.2f} ms (mean)"
                 try:
                     prof = profile_step(c, outs, targets, dn_meta)
                 except Exception as e:                                               # noqa: BLE001 -- the profiler is optional here
@@ -129,8 +140,11 @@ def main():
                 else:
                     line += f"   device {prof[0] / 1e3:7.3f} ms   launches {prof[1]:5d}   syncs {prof[2]:4d}"
                     line += " (" + ", ".join(f"{k} {v}" for k, v in sorted(prof[3].items())) + ")"
+                    if name == "device":
+                        line += f"   of the device time assign_match_kernel {ASSIGN['us'] / 1e3:.3f} ms in {ASSIGN['launches']} launches"
                 print(line, flush=True)
-            print(f"  wall: torch / fused = {statistics.median(wall['torch']) / statistics.median(wall['fused']):.2f}x", flush=True)
+            print(f"  wall: torch / fused = {statistics.median(wall['torch']) / statistics.median(wall['fused']):.2f}x, "
+                  f"fused / device = {statistics.median(wall['fused']) / statistics.median(wall['device']):.2f}x", flush=True)
 
 
 if __name__ == "__main__":
