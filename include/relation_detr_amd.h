@@ -902,6 +902,52 @@ int rdetr_grad_clip_coef(void *ws, long long ws_bytes, int n_chunks, float max_n
 int rdetr_adamw_step_f32(const rdetr_optim_tensor *tensors, const rdetr_optim_step *steps, const rdetr_optim_chunk *chunk_map, int n_tensors,
                          int n_chunks, int chunk, int max_blocks, const float *norm_coef, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The neck's GroupNorm over a whole pyramid, the per-level padding masks and the sine position encoding (csrc/neck.hip;
+ * models/necks/channel_mapper.py, models/detectors/base_detector.py:153-165, models/bricks/position_encoding.py:9-68).
+ *
+ * Every table argument is a HOST array of L <= 8 entries: pointers to the levels' DEVICE tensors, level_hw 2 L ints (h, w).  The
+ * tables travel in the kernels' argument blocks.
+ *
+ * GroupNorm.  x[l], y[l], dy[l], dx[l]: contiguous [B, C, h_l, w_l], fp32 or bf16; gamma[l], beta[l]: [C] fp32 (the bf16 entry
+ * points also take them in bf16, params_bf16 = 1); C % G == 0 and C / G <= 16, else RDETR_ERR_UNSUPPORTED.  mean, rstd: [L][B][G]
+ * fp32.  ws: rdetr_neck_workspace_bytes bytes (-1 for sizes the kernels refuse), shared by forward and backward.
+ *   forward   launch 1: one workgroup per 4096 elements of one (level, image, group) writes that chunk's (count, mean, M2), the mean
+ *             first and M2 about it.  Launch 2: every workgroup combines its group's triples in index order with Chan's formula,
+ *             writes y = (x - mean) rstd gamma[c] + beta[c] in x's type and, for chunk 0, mean and rstd = 1 / sqrt(M2 / n + eps).
+ *   backward  launch 1: per (level, image, channel, 4096-pixel chunk) sum dy and sum dy xhat, xhat = (x - mean) rstd.  Launch 2:
+ *             per group s1 = sum_c gamma_c sum dy, s2 = sum_c gamma_c sum dy xhat in index order, dx = rstd (dy gamma - (s1 + xhat
+ *             s2) / n); the workgroups behind them add the partials over chunks, then images, into dgamma, dbeta [L][C] fp32.
+ * No atomics and no hand-over inside a launch: the same call gives the same bits.
+ *
+ * Masks.  mask: the image-level padding mask [B, H, W], bool bytes or fp32 (mask_is_f32), non-zero = padded.  level_masks[l]: bool
+ * [B, h_l, w_l] by torch's nearest rule, src = min(floor(dst * (float(in) / float(out))), in - 1).  cum: int32, 2 * B * S entries
+ * (S the pixels of all levels): level l's [B, h_l, w_l] inclusive count of valid pixels down the columns at B * (pixels of the levels
+ * before l), and along the rows B * S entries further on.  One launch.
+ *
+ * Position encoding.  out[l]: [B, 2 F, h_l, w_l] fp32 or bf16, channels [0, F) from the column counts and [F, 2 F) from the row
+ * counts, 2 k the sine and 2 k + 1 the cosine of a = e / dim_t[k], e = float(count) + offset and, with normalize, e = e /
+ * (float(last count of the column / row) + eps) * scale, each step one fp32 operation.  dim_t: F / 2 floats on the device, F even.
+ * One launch. */
+long long rdetr_neck_workspace_bytes(const int *level_hw, int L, int B, int C, int G);
+int rdetr_group_norm_levels_f32(const void *const *x, const void *const *gamma, const void *const *beta, const int *level_hw, int L, int B,
+                                int C, int G, float eps, void *ws, long long ws_bytes, void *const *y, float *mean, float *rstd, void *stream);
+int rdetr_group_norm_levels_bf16(const void *const *x, const void *const *gamma, const void *const *beta, int params_bf16, const int *level_hw,
+                                 int L, int B, int C, int G, float eps, void *ws, long long ws_bytes, void *const *y, float *mean, float *rstd,
+                                 void *stream);
+int rdetr_group_norm_levels_backward_f32(const void *const *dy, const void *const *x, const void *const *gamma, const float *mean,
+                                         const float *rstd, const int *level_hw, int L, int B, int C, int G, void *ws, long long ws_bytes,
+                                         void *const *dx, float *dgamma, float *dbeta, void *stream);
+int rdetr_group_norm_levels_backward_bf16(const void *const *dy, const void *const *x, const void *const *gamma, int params_bf16,
+                                          const float *mean, const float *rstd, const int *level_hw, int L, int B, int C, int G, void *ws,
+                                          long long ws_bytes, void *const *dx, float *dgamma, float *dbeta, void *stream);
+int rdetr_pyramid_masks(const void *mask, int mask_is_f32, int B, int H, int W, const int *level_hw, int L, void *const *level_masks,
+                        int *cum, void *stream);
+int rdetr_pyramid_sine_pos_f32(const int *cum, const int *level_hw, int L, int B, int F, const float *dim_t, int normalize, float scale,
+                               float eps, float offset, void *const *out, void *stream);
+int rdetr_pyramid_sine_pos_bf16(const int *cum, const int *level_hw, int L, int B, int F, const float *dim_t, int normalize, float scale,
+                                float eps, float offset, void *const *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

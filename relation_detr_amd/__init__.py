@@ -17,7 +17,9 @@ from .amp_train import AddLayerNormMixedFunction, FeedForwardMixedFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
 from .criterion import RelationCriterion, SetLossFunction, assign_match, hungarian_match, match_cost, set_loss
 from .denoising import CdnQueryFunction, GenerateCDNQueries, cdn_noise, cdn_queries, denoising_mask
-from .detector import RelationDETRHead
+from .detector import RelationDETR, RelationDETRHead
+from .neck import (ChannelMapper, GroupNormLevelsFunction, PositionEmbeddingSine, PyramidBuilder, group_norm_levels, pyramid_masks,
+                   pyramid_sine_pos)
 from .optim import FusedAdamW, relation_param_groups, train_step
 
 __all__ = [
@@ -33,4 +35,6 @@ __all__ = [
     "RelationCriterion", "SetLossFunction", "match_cost", "hungarian_match", "assign_match", "set_loss",
     "GenerateCDNQueries", "CdnQueryFunction", "cdn_queries", "cdn_noise", "denoising_mask", "RelationDETRHead",
     "FusedAdamW", "relation_param_groups", "train_step",
+    "ChannelMapper", "PositionEmbeddingSine", "PyramidBuilder", "RelationDETR", "GroupNormLevelsFunction", "group_norm_levels",
+    "pyramid_masks", "pyramid_sine_pos",
 ]

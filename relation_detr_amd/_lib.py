@@ -119,6 +119,14 @@ SIGNATURES = {
     "rdetr_grad_sqnorm_f32": [_vp] * 3 + [_c_int] * 4 + [_vp, _c_ll, _vp],
     "rdetr_grad_clip_coef": [_vp, _c_ll, _c_int, _c_float, _vp],
     "rdetr_adamw_step_f32": [_vp] * 3 + [_c_int] * 4 + [_vp, _vp],
+    "rdetr_neck_workspace_bytes": [_vp] + [_c_int] * 4,
+    "rdetr_group_norm_levels_f32": [_vp] * 4 + [_c_int] * 4 + [_c_float, _vp, _c_ll] + [_vp] * 4,
+    "rdetr_group_norm_levels_bf16": [_vp] * 3 + [_c_int, _vp] + [_c_int] * 4 + [_c_float, _vp, _c_ll] + [_vp] * 4,
+    "rdetr_group_norm_levels_backward_f32": [_vp] * 6 + [_c_int] * 4 + [_vp, _c_ll] + [_vp] * 4,
+    "rdetr_group_norm_levels_backward_bf16": [_vp] * 3 + [_c_int] + [_vp] * 3 + [_c_int] * 4 + [_vp, _c_ll] + [_vp] * 4,
+    "rdetr_pyramid_masks": [_vp] + [_c_int] * 4 + [_vp, _c_int, _vp, _vp, _vp],
+    "rdetr_pyramid_sine_pos_f32": [_vp, _vp] + [_c_int] * 3 + [_vp, _c_int] + [_c_float] * 3 + [_vp, _vp],
+    "rdetr_pyramid_sine_pos_bf16": [_vp, _vp] + [_c_int] * 3 + [_vp, _c_int] + [_c_float] * 3 + [_vp, _vp],
 }
 
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3            # rdetr_status (include/relation_detr_amd.h)

@@ -2,7 +2,9 @@
 (``models/detectors/relation_detr.py:52-141``).
 
 ``RelationDETRHead(transformer, criterion, denoising_generator)`` keeps the reference detector's attribute names, so its
-state-dict keys are the reference's minus ``backbone.*`` and ``neck.*``.  One deviation: when no image of the batch has a box the
+state-dict keys are the reference's minus ``backbone.*`` and ``neck.*``; ``RelationDETR(neck, position_embedding, transformer, criterion,
+denoising_generator)`` puts the neck and the position encoding in front, so its keys are the reference's minus ``backbone.*`` and its
+``forward`` starts at the backbone's feature maps and the padding mask.  One deviation: when no image of the batch has a box the
 reference still builds (empty) denoising queries and reports ``_dn`` losses of zero; here the transformer then runs without
 denoising queries and the criterion with ``dn_meta=None``, so the dict has no ``_dn`` keys.
 """
@@ -14,6 +16,7 @@ from torch import Tensor, nn
 
 from .criterion import RelationCriterion
 from .denoising import GenerateCDNQueries, Noise
+from .neck import build_pyramid
 from .transformer import RelationTransformer
 
 
@@ -44,3 +47,32 @@ class RelationDETRHead(nn.Module):
             [t["labels"] for t in targets], [t["boxes"] for t in targets], noise=noise)
         outputs = self.transformer(multi_level_feats, multi_level_masks, multi_level_pos_embeds, label_query, box_query, attn_mask)
         return self.criterion(outputs, targets, dn_meta=(groups, group_size))
+
+
+class RelationDETR(RelationDETRHead):
+    """``forward(features, mask, targets=None, noise=None)``: ``features`` the backbone's maps (dict or sequence, contiguous NCHW),
+    ``mask`` the image-level padding mask ``[B, H, W]`` (non-zero = padded).  The pyramid is built as ``PyramidBuilder`` does
+    (``DETRDetector.get_multi_levels`` behind the backbone), the rest is ``RelationDETRHead.forward``.
+
+    The attributes are the reference detector's (``neck``, ``position_embedding``, ``transformer``, ``criterion``,
+    ``denoising_generator``), so ``state_dict()`` holds ``neck.convs.{i}.0.weight``, ``neck.convs.{i}.1.{weight,bias}`` and the head's
+    keys; ``position_embedding`` contributes none.  ``relation_param_groups`` sorts the neck by name like every other parameter,
+    as the reference does: ``neck.convs.{i}.0.weight`` and ``neck.convs.{i}.1.weight`` (no "norm" in the name) fall in the default
+    group, ``neck.convs.{i}.1.bias`` in the no-decay group of the other biases.  ``train_step(model, optimizer, features, mask, None,
+    targets)`` steps them with the rest."""
+
+    def __init__(self, neck: nn.Module, position_embedding: nn.Module, transformer: RelationTransformer, criterion: RelationCriterion,
+                 denoising_generator: GenerateCDNQueries):
+        nn.Module.__init__(self)
+        self.neck = neck
+        self.position_embedding = position_embedding
+        self.transformer = transformer
+        self.criterion = criterion
+        self.denoising_generator = denoising_generator
+
+    def get_multi_levels(self, features, mask: Tensor, dtype=None):
+        return build_pyramid(self.neck, self.position_embedding, features, mask, dtype)
+
+    def forward(self, features, mask: Tensor, targets: Optional[Sequence[Dict[str, Tensor]]] = None, noise: Optional[Noise] = None):
+        feats, masks, pos = self.get_multi_levels(features, mask)
+        return RelationDETRHead.forward(self, feats, masks, pos, targets, noise)

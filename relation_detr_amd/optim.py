@@ -403,9 +403,11 @@ class FusedAdamW(torch.optim.Optimizer):
 def train_step(head, optimizer: FusedAdamW, feats, masks, pos, targets, max_norm: float = 0.1, noise=None):
     """One pass of the reference's loop (``util/engine.py:46-61``) over a ``RelationDETRHead`` in training mode: ``zero_grad``, the
     head's forward, the sum of the loss dict, ``backward``, the clip when ``max_norm > 0``, ``step``.  Returns ``(loss_dict,
-    total_norm)``, ``total_norm`` a 0-dim tensor or None without a clip; nothing here waits for the device."""
+    total_norm)``, ``total_norm`` a 0-dim tensor or None without a clip; nothing here waits for the device.  With ``pos=None``
+    the module builds its own pyramid: ``head`` is a ``RelationDETR``, ``feats`` the backbone's feature maps and ``masks`` the image-level
+    padding mask."""
     optimizer.zero_grad()
-    loss_dict = head(feats, masks, pos, targets, noise=noise)
+    loss_dict = head(feats, masks, targets, noise=noise) if pos is None else head(feats, masks, pos, targets, noise=noise)
     sum(loss_dict.values()).backward()
     total_norm = optimizer.clip_grad_norm_(max_norm) if max_norm > 0 else None
     optimizer.step()
