@@ -52,11 +52,31 @@ __device__ __forceinline__ unsigned int positive_bf16x2(unsigned int packed)
     return __builtin_bit_cast(unsigned int, zero - b);
 }
 
+// pack_bf16x2 as a conversion of the pair: the two scalar conversions of pack_bf16x2 become two v_cvt_pk_bf16_f32 and a v_perm_b32
+// in the chunk loop, this form one v_cvt_pk_bf16_f32 with both sources (the same rounding of each half)
+__device__ __forceinline__ unsigned int ffn_pack_bf16x2(float a, float b)
+{
+    return __builtin_bit_cast(unsigned int, __builtin_convertvector(f32x2{a, b}, bf16x2_t));
+}
+
 // what the kernel body does around the two GEMMs
 constexpr int kFfnInfer = 0;               // out only (rdetr_ffn_k256_bf16, rdetr_ffn_ln_k256_bf16)
 constexpr int kFfnTrain = 1;               // ... and the hidden activations H [M, F] stored for backward
 constexpr int kFfnBwd = 2;                 // data gradient: x = dY, packed = (W2^T, W1^T), no biases; the hidden epilogue rounds
                                            // dY W2, zeroes it where the saved H is not positive, stores it as dH: out = dX
+
+// Step order of the inference kernels (ffn_k256_body.h): the activations cut into slices behind the MFMAs of the next 16 steps and
+// the weight stream of the next chunk issued piece by piece.  The development library (make dev) gives them the order of the
+// training kernels instead, each activation whole at one step and the 8 pieces back to back: its component-timing bits are
+// branches, and the spread loop has no register left for a branch (one around each piece sent 22 registers to scratch).  Without
+// a bit set that kernel runs the schedule the spread order replaced (profiles/r22/README.md).
+#ifdef RDETR_DEV
+constexpr bool kFfnSpread = false;
+#else
+constexpr bool kFfnSpread = true;
+#endif
+constexpr int kFfnDmaFirst = 3, kFfnDmaEvery = 2;          // piece i of the next chunk goes out after step First + i Every
+static_assert(kFfnDmaFirst >= 3 && kFfnDmaEvery >= 1 && kFfnDmaFirst + 7 * kFfnDmaEvery < 64, "pieces inside the chunk, behind its barrier");
 
 // H / dH are addressed through a buffer resource (SGPRs): the 16-row block's first row and the chunk's column are the scalar
 // offset, the lane's row and column inside the block a 32-bit vector offset -- no 64-bit row pointers inside the chunk loop, which

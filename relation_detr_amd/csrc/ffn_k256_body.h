@@ -6,7 +6,8 @@
 //   XF32: the rows are read from xf (float, ldx) instead of x, rounded to bf16 (RNE) and also stored as xlp [M, 256] (ldxl)
 //   DXF32: the accumulators are stored unrounded to outf (float, ldo) instead of out
 #ifdef RDETR_DEV
-    const int dbg = dbg_arg;                 // development builds: component-timing mask (1 no weight stream, 2 no barrier, 4 / 8 no GEMM 2 / 1)
+    const int dbg = dbg_arg;                 // development builds: component-timing mask (1 no weight stream, 2 no barrier, 4 / 8 no GEMM 2 / 1,
+                                             // 16 no activation arithmetic: the GEMM 1 accumulators are only packed); lumped order
 #else
     constexpr int dbg = 0;                   // product build: no branches inside the MFMA loop (they end the scheduling regions)
 #endif
@@ -28,17 +29,18 @@
     // LDS-DMA of chunk c into buffer c & 1: the chunk's 64 fragments of 1 KiB are one contiguous 64-KiB slab of the PACKED
     // weights (ffn_pack_kernel below), 8 instructions per wave, each a fully coalesced 1-KiB read
     const int nchunks = F / kFfnHC;
-    auto issue_chunk = [&](int c) {
-        const unsigned buf = (unsigned)((c & 1) * kFfnBufBytes);
+    auto issue_piece = [&](int c, int into, int i) __attribute__((always_inline)) {     // piece i of chunk c into buffer `into`
+        const unsigned buf = (unsigned)(into * kFfnBufBytes);
         const unsigned char *slab = reinterpret_cast<const unsigned char *>(packed) + (size_t)c * kFfnBufBytes;
         const unsigned lane_off = (unsigned)lane * 16u;
+        const int f = wave * 8 + i;                                           // uniform
+        const unsigned m0v = buf + (unsigned)f * 1024u;
+        const unsigned char *src = slab + f * 1024;
+        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(m0v), "v"(lane_off), "s"(src) : "memory", "m0");
+    };
+    auto issue_chunk = [&](int c) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const int f = wave * 8 + i;                                       // uniform
-            const unsigned m0v = buf + (unsigned)f * 1024u;
-            const unsigned char *src = slab + f * 1024;
-            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" : : "s"(m0v), "v"(lane_off), "s"(src) : "memory", "m0");
-        }
+        for (int i = 0; i < 8; ++i) issue_piece(c, c & 1, i);
     };
 
     __amdgpu_buffer_rsrc_t hrs, drs;                                          // H, dH: up to the end of the last row's F columns
@@ -110,16 +112,34 @@
             if (!(dbg & 2)) __syncthreads();                                  // ... everyone's; and chunk c - 1 is consumed
             const u32x4 *w1l = reinterpret_cast<const u32x4 *>(ffn_lds + (c & 1) * kFfnBufBytes);
             const u32x4 *w2l = reinterpret_cast<const u32x4 *>(ffn_lds + (c & 1) * kFfnBufBytes + kFfnW1Bytes);
-            // The chunk is ONE stream of 64 A fragments (32 of W1, 32 of W2), each feeding two MFMAs (the wave's two 16-row blocks):
-            //   t =  0..15  GEMM 1 of tile pair 0                      (k-step t >> 1, tile t & 1)          -> acc1a
-            //   t = 16..47  per k-step s: GEMM 1 of pair 1 (2 fragments -> acc1b), GEMM 2 of pair 0 (out tiles 2s, 2s + 1; B = h0)
-            //   t = 48..63  GEMM 2 of pair 1 (out tile t - 48; B = h1)
+            // The chunk is ONE stream of 64 A fragments (32 of W1, 32 of W2), each feeding two MFMAs (the wave's two 16-row blocks),
             // read through a ring of three registers, two fragments AHEAD of their use: left to itself the compiler issued every
             // ds_read_b128 right before its MFMAs and waited lgkmcnt(0) -- the LDS latency once per pair of MFMAs, the matrix pipe
             // 56 % busy.  The scheduling barriers pin the order; the counted waits follow from it.  The hidden bias is added when a
-            // pair is packed (accumulators start from the inline constant 0: no initialising moves), h0 / h1 are packed two steps
-            // after their last MFMA was issued, behind MFMAs that do not need them.
+            // pair is packed (accumulators start from the inline constant 0: no initialising moves).
+            // Inference (kFfnSpread): four blocks of 16 steps,
+            //   t =  0..15  GEMM 1 of tile pair 0   (k-step t >> 1, tile t & 1)       -> acc1a
+            //   t = 16..31  GEMM 1 of tile pair 1   (k-step (t & 15) >> 1, tile 2 + (t & 1))  -> acc1b;  behind them h0 = act(acc1a)
+            //   t = 32..47  GEMM 2 of pair 0        (out tile t & 15; B = h0);                           behind them h1 = act(acc1b)
+            //   t = 48..63  GEMM 2 of pair 1        (out tile t & 15; B = h1)
+            // so each activation has 16 steps to hide in and is cut into slices of two VALU instructions, one slice per step: an
+            // even step adds the bias to the two values of one packed register, the odd step after it rounds and clamps them
+            // (act_slice below).  The register packed last (step 31 / 47) belongs to column block 1: the SECOND MFMA of the next
+            // step is the first to read it.
+            // The 8 LDS-DMA pieces of chunk c + 1 go out one at a time, after the steps kFfnDmaFirst + i kFfnDmaEvery.
+            // Every accumulator takes the operands it took in the training order below, in the same order: the same bits.
+            // Training (and the development library): per k-step GEMM 1 of pair 1 and GEMM 2 of pair 0 alternate,
+            //   t =  0..15  GEMM 1 of tile pair 0                      (k-step t >> 1, tile t & 1)          -> acc1a
+            //   t = 16..47  per k-step s: GEMM 1 of pair 1 (2 fragments -> acc1b), GEMM 2 of pair 0 (out tiles 2s, 2s + 1; B = h0)
+            //   t = 48..63  GEMM 2 of pair 1 (out tile t - 48; B = h1)
+            // h0 / h1 are packed whole, two steps after their last MFMA was issued (the H / dH traffic of the training kernels is
+            // part of that step), and the weight stream is issued whole after step 3.
+            constexpr bool SPREAD = kFfnSpread && MODE == kFfnInfer;
             auto frag = [&](int t) -> u32x4 {
+                if constexpr (SPREAD) {
+                    if (t < 32) return w1l[(((t >> 4) * 2 + (t & 1)) * 8 + ((t & 15) >> 1)) * 64 + lane];
+                    return w2l[((t & 15) * 2 + ((t - 32) >> 4)) * 64 + lane];
+                }
                 if (t < 16) return w1l[((t & 1) * 8 + (t >> 1)) * 64 + lane];
                 if (t < 48) {
                     const int s = (t - 16) >> 2, r = (t - 16) & 3;
@@ -152,6 +172,16 @@
                     }
                     return;
                 }
+                if (dbg & 16) {
+#pragma unroll
+                    for (int cb = 0; cb < 2; ++cb) {
+                        h[cb].x = pack_bf16x2(acc1[0][cb].x, acc1[0][cb].y);
+                        h[cb].y = pack_bf16x2(acc1[0][cb].z, acc1[0][cb].w);
+                        h[cb].z = pack_bf16x2(acc1[1][cb].x, acc1[1][cb].y);
+                        h[cb].w = pack_bf16x2(acc1[1][cb].z, acc1[1][cb].w);
+                    }
+                    return;
+                }
                 const f32x4 blo = *reinterpret_cast<const f32x4 *>(b1l + c * kFfnHC + 32 * u + 8 * g);
                 const f32x4 bhi = *reinterpret_cast<const f32x4 *>(b1l + c * kFfnHC + 32 * u + 8 * g + 4);
 #pragma unroll
@@ -165,7 +195,50 @@
                 }
             };
             const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+            // SPREAD: the slices of the two activations.  Pair u has 8 packed registers; register k is h[k >> 2][k & 3], made of
+            // the values 2 (k & 1), + 1 of acc1[(k & 3) >> 1][k >> 2] and the biases 2 (k & 3), + 1 of the lane's 8.  Its three parts
+            // run at the steps 15 + 16 u + 2 k (bias pair LDS -> registers), + 1 (two adds), + 2 (one convert, one max): every odd
+            // step from 15 to 45 reads a pair, every odd step from 17 to 47 packs the register of the step before, and at a
+            // scheduling barrier two values are in flight, not the pair's 8 biases (the loop has no registers for them).  The
+            // arithmetic of activate() above, one register at a time: the same operations on the same values
+            [[maybe_unused]] f32x2 act_bias;
+            [[maybe_unused]] float act_a, act_b;
+            [[maybe_unused]] auto act_slice = [&](int t) __attribute__((always_inline)) {
+                if (t < 15 || t > 47) return;
+                const bool odd = t & 1;
+                if (odd && t < 47) {
+                    const int u = (t - 15) >> 4, k = ((t - 15) & 15) >> 1, j = k & 3;
+                    act_bias = *reinterpret_cast<const f32x2 *>(b1l + c * kFfnHC + 32 * u + 8 * g + 2 * j);
+                }
+                if (odd && t > 15) {
+                    const int u = (t - 17) >> 4, k = ((t - 17) & 15) >> 1, cb = k >> 2, j = k & 3;
+                    u32x4(&h)[2] = u ? h1 : h0;
+                    h[cb][j] = relu_bf16x2(ffn_pack_bf16x2(act_a, act_b));    // round, then relu on the packed pair
+                }
+                if (!odd) {
+                    const int u = (t - 16) >> 4, k = ((t - 16) & 15) >> 1, cb = k >> 2, j = k & 3, i = 2 * (j & 1);
+                    const f32x4(&acc1)[2][2] = u ? acc1b : acc1a;
+                    act_a = acc1[j >> 1][cb][i] + act_bias.x;
+                    asm volatile("" : "+v"(act_a));                           // two v_add_f32: left alone the pair becomes one
+                    act_b = acc1[j >> 1][cb][i + 1] + act_bias.y;             // v_pk_add_f32, 3.4 us slower per launch beside MFMAs
+                }
+            };
             auto apply = [&](int t, const u32x4 &a) {
+                if constexpr (SPREAD) {
+                    if (t < 32) {
+                        const int s = (t & 15) >> 1, e = t & 1;
+                        f32x4(&acc1)[2][2] = t < 16 ? acc1a : acc1b;
+                        acc1[e][0] = mm(a, xr[0][s], s ? acc1[e][0] : zero4);
+                        acc1[e][1] = mm(a, xr[1][s], s ? acc1[e][1] : zero4);
+                    } else {
+                        const int ot = t & 15;
+                        const u32x4(&h)[2] = t < 48 ? h0 : h1;
+                        acc2[ot][0] = mm(a, h[0], acc2[ot][0]);
+                        acc2[ot][1] = mm(a, h[1], acc2[ot][1]);
+                    }
+                    act_slice(t);
+                    return;
+                }
                 if (t < 16) {
                     const int s = t >> 1, e = t & 1;
                     acc1a[e][0] = mm(a, xr[0][s], s ? acc1a[e][0] : zero4);
@@ -201,19 +274,34 @@
                     apply(t, ring[t % 3]);
                     __builtin_amdgcn_sched_barrier(0);
                 }
-                if (c + 1 < nchunks && !(dbg & 1)) issue_chunk(c + 1);        // behind the first MFMAs: the pipe starts at once
-                if constexpr (MODE == kFfnInfer) {
+                // the weight stream of chunk c + 1, behind the first MFMAs (the pipe starts at once) and after the chunk-top barrier
+                // (its buffer is free).  SPREAD: one piece after each of the steps kFfnDmaFirst + i kFfnDmaEvery, and no branch
+                // around them (eight branches in the loop cost it its registers): behind the last chunk they fetch chunk 0 again,
+                // into the buffer that chunk does not read -- 64 KiB of L2 traffic per tile that nobody uses, landed before the
+                // vmcnt(0) below the chunk loop
+                const int cnext = c + 1 < nchunks ? c + 1 : 0;
+                auto dma_after = [&](int t) __attribute__((always_inline)) {
+                    if constexpr (SPREAD) {
+                        const int d = t - kFfnDmaFirst;
+                        if (d >= 0 && d % kFfnDmaEvery == 0 && d / kFfnDmaEvery < 8) issue_piece(cnext, (c + 1) & 1, d / kFfnDmaEvery);
+                    } else {
+                        if (t == 3 && c + 1 < nchunks && !(dbg & 1)) issue_chunk(c + 1);
+                    }
+                };
+                dma_after(3);
+                if constexpr (SPREAD) {
 #pragma unroll
                     for (int t = 4; t < 64; ++t) {
                         if (t + 2 < 64) ring[(t + 2) % 3] = frag(t + 2);
                         __builtin_amdgcn_sched_barrier(0);
                         apply(t, ring[t % 3]);
                         __builtin_amdgcn_sched_barrier(0);
+                        dma_after(t);
                     }
                 } else {
                     // the same steps written out at compile time: as a loop to be unrolled every iteration carries all of a step's
                     // cases, and with the training epilogues the body exceeds the unroller's size limit (the arrays then live in
-                    // scratch).  The inference kernels keep the loop, and with it their code, instruction for instruction.
+                    // scratch).  So does the lumped inference loop of the development library with its timing branches.
                     ffn_static_for(std::make_integer_sequence<int, 60>{}, [&](auto tc) __attribute__((always_inline)) {
                         constexpr int t = 4 + decltype(tc)::value;
                         if (t + 2 < 64) ring[(t + 2) % 3] = frag(t + 2);
@@ -225,6 +313,9 @@
             }
             __builtin_amdgcn_sched_barrier(0);
         }
+        if constexpr (kFfnSpread && MODE == kFfnInfer)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // the pieces issued behind the last chunk: nothing in flight
+                                                                              // into LDS when the next tile, or nobody, owns it
         // the epilogue's row pointers (out, pos, out2) are derived from values the compiler cannot see before this point: hoisted
         // above the chunk loop they would occupy 12 registers there and spill the loop
         unsigned col_e = (unsigned)col;
