@@ -71,3 +71,44 @@ G8_FULL_GRADS = ("level_embeds", "tgt_embed.weight", "hybrid_tgt_embed.weight",
                  "encoder.layers.0.self_attn.sampling_offsets.bias", "encoder.layers.1.self_attn.attention_weights.bias",
                  "decoder.layers.1.self_attn.in_proj_bias", "decoder.layers.2.cross_attn.sampling_offsets.bias",
                  "decoder.bbox_head.0.layers.2.bias", "hybrid_class_head.bias", "encoder_class_head.bias")
+
+
+# the optimizer checker of tests/test_gpu_optim.py and of the shadow harness (tests/shadow.py): one copy
+def snapshot(opt):
+    """The optimizer's tensors before a step, in group order: per parameter (p, m, v, step, grad), clones on the device."""
+    rows = []
+    for group in opt.param_groups:
+        for p in group["params"]:
+            s = opt.state.get(p) or {}
+            rows.append(dict(p=p.detach().clone(), m=s["exp_avg"].clone() if s else None, v=s["exp_avg_sq"].clone() if s else None,
+                             step=float(s["step"]) if s else 0.0, g=None if p.grad is None else p.grad.detach().clone(),
+                             requires_grad=p.requires_grad))
+    return rows
+
+
+def torch_route_step(opt, rows, max_norm, dtype):
+    """One clip + step of the torch route in ``dtype`` from ``rows`` under ``opt``'s current group settings ->
+    (norm, per parameter (p, m, v, scaled gradient))."""
+    from relation_detr_amd.optim import FusedAdamW
+    groups, params, i = [], [], 0
+    for group in opt.param_groups:
+        mine = []
+        for _ in group["params"]:
+            q = torch.nn.Parameter(rows[i]["p"].to(dtype, copy=True), requires_grad=rows[i]["requires_grad"])
+            q.grad = None if rows[i]["g"] is None else rows[i]["g"].to(dtype, copy=True).contiguous()
+            mine.append(q)
+            i += 1
+        params += mine
+        groups.append({"params": mine, **{k: group[k] for k in ("lr", "betas", "eps", "weight_decay")}})
+    route = FusedAdamW(groups, fused=False)
+    for q, row in zip(params, rows):
+        if row["m"] is not None:
+            route.state[q] = {"step": torch.tensor(row["step"], dtype=torch.float32), "exp_avg": row["m"].to(dtype, copy=True),
+                              "exp_avg_sq": row["v"].to(dtype, copy=True)}
+    norm = route.clip_grad_norm_(max_norm) if max_norm is not None else None
+    route.step()
+    out = []
+    for q in params:
+        s = route.state.get(q) or {}
+        out.append((q.detach(), s.get("exp_avg"), s.get("exp_avg_sq"), q.grad))
+    return norm, out

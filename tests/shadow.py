@@ -1,7 +1,9 @@
 """Shadow checks of every kernel launch on a forward (or training step) of the stack.
 
-``Shadow(monkeypatch)`` replaces the module-level functions of ``relation_detr_amd.ops`` with wrappers, and those of the four
-training modules that call the library themselves (``ffn_train``, ``ln_train``, ``attn_rel_train``, ``msda_train_hm``).  Every call
+``Shadow(monkeypatch)`` replaces the module-level functions of ``relation_detr_amd.ops`` with wrappers, and those of the nine
+modules that call the library themselves: the training routes ``ffn_train``, ``ln_train``, ``attn_rel_train``, ``msda_train_hm`` and
+``amp_train``, and the rest of a detector's training step, ``neck``, ``denoising``, ``criterion`` and ``optim`` (there also the two
+launching methods of ``FusedAdamW``, patched on the class).  Every call
 site in transformer.py, ms_deform_attn.py, self_attn.py and relation.py looks the former up as ``ops.<name>``; the autograd
 Functions in ops.py and in the training modules reach their entries through their own module's globals, so a wrapper sees every
 launch of the stack, forward or training step, whichever opt-in training route is on.  A wrapper copies the tensor
@@ -34,8 +36,10 @@ Bounds (err = |kernel - reference|; "exact" = bit equality; each from the unit t
   ffn_ln_k256                     2^-8 |ref| + 2^-5 + 1e-3; pos output exact       test_gpu_glue::test_ffn_ln_k256_is_ffn_then_add_layer_norm
   add_layer_norm                  fp32: 2e-5;  bf16: 2^-8 |ref| + 1e-3;            test_gpu_glue::test_add_layer_norm_vs_torch,
                                   pos output exact (out + pos)                     ::test_add_layer_norm_second_output_is_the_separate_add
-  relation_bias                   1e-4                                             test_gpu_parity::test_relation_bias_vs_oracle
-  bias_softmax_                   2e-6                                             test_gpu_parity::test_bias_softmax_vs_torch
+  relation_bias                   1e-4 + 4 2^-24 sum |(W_sin, W_cos)| |sine argument| test_gpu_parity::test_relation_bias_vs_oracle
+                                  (relation_bias_bound: the fp32 rounding of the arguments)
+  bias_softmax_                   2e-6 + 2^-22 max_row |logit| p  (bias_softmax_bound:   test_gpu_parity::test_bias_softmax_vs_torch
+                                  the fp32 rounding of the logits)
   relation_attention[_boxes]      2^-7 |ref| + 4e-3                                test_gpu_glue::test_relation_attention_vs_reference,
                                                                                    test_gpu_attn_rel (_close)
   _relation_attention_train       out as above; lse (natural log) 1e-3            test_gpu_attn_train::test_train_forward_is_the_inference_kernel_and_lse
@@ -82,6 +86,39 @@ to bf16 the kernel makes, plus its fp32 accumulation; tests/test_shadow_train_ho
                                   bf16 bounds on the [B,S,H,D] permutation of the value
   msda_train_hm.grad_value_from_head_major   exact (the torch expression of its docstring)       test_gpu_msda_train_hm
 No constant was raised for the training step: profiles/r14/ has every entry's worst err / bound ratio there, all below 1.
+
+The detector step (tests/test_gpu_shadow_detector.py; "floor form" = max(4 e32, 2^-20 scale), e32 the error of the module's own
+torch route run in fp32 on the same operands against the same route in float64, computed inside the checker, scale = max(1, |ref|)
+unless said otherwise; the golden fixtures g10, g11, g12 pin those routes to the reference project):
+
+  amp_train.add_layer_norm_mixed_train     out 2e-5 (add_layer_norm, fp32), mean / rstd 1e-5 max(1, |ref|)   test_gpu_amp_train::test_layernorm_kernels_against_float64
+  amp_train.add_layer_norm_mixed_backward  the fp32 bounds of ln_train.add_layer_norm_backward; the bf16 dx    (the fp32 bounds of test_gpu_ln_train)
+                                  is the rounding of the fp32 dx, exact
+  amp_train.ffn_mixed_train       ffn_train.ffn_k256_train's on the operands rounded to bf16; x's rounding exact  test_gpu_amp_train (bits of the bf16 route),
+  amp_train.ffn_mixed_backward    dH as ffn_train.ffn_k256_backward; fp32 dx (1e-6 + 4 2^-24 sqrt(F))            ::test_ffn_backward_keeps_dh_and_leaves_dx_unrounded,
+                                  max(1, max|ref|) against float64 dH_returned @ bf16(w1); bf16 dx: bf16 form    ::test_function_gradients_against_fp64
+  neck.group_norm_levels_forward  per tensor 4 max(torch's fp32 CPU GroupNorm's own error, 2^-23 max|ref|),      test_gpu_neck::test_group_norm_forward_and_backward_fp32,
+  neck.group_norm_levels_backward + 2^-8 |ref| for a bf16 result; mean 4 2^-23 max(1, max|ref|); rstd the same   ::test_group_norm_bf16
+                                  yardstick on itself; the backward's statistics recomputed in float64
+  neck._masks_and_counts          exact                                                                          test_gpu_neck::test_masks_and_counts_are_exact
+  neck._sine_pos_packed           5e-6 (+ 2^-8 |ref| in bf16) against float64 sin / cos of the fp32 argument     test_gpu_neck::test_position_encoding_at_every_pixel
+  denoising.cdn_noise, .denoising_mask   exact (the numpy Philox restatement; the torch expression)              test_gpu_denoising
+  denoising.cdn_queries_forward   labels and label queries exact; box queries floor form                         test_gpu_denoising (within)
+  denoising.cdn_embed_backward    floor form, + 2^-8 |ref| in bf16                                               test_gpu_denoising::test_embedding_gradient
+  criterion.match_cost            floor form, scale max(1, sum of the cost's term magnitudes) (match_cost_scale);  test_gpu_criterion::test_match_cost (within)
+                                  padded columns exactly 0
+  criterion.set_loss_forward      floor form: sums, dlogits per element (+ 2^-8 |ref| in bf16), the box          test_gpu_criterion::test_set_loss (within)
+                                  gradients with the tensor's max|ref| as scale
+  criterion.assign_match          device route only (the host route is scipy itself and is not recorded): per    test_gpu_assign::check_assignment
+                                  row a valid assignment, total cost = scipy's optimum on the copied costs to
+                                  1e-9 sum|chosen|, the denoising prefix the fixed pattern, status 0
+  optim.FusedAdamW._clip_fused    total norm, coefficient: floor form, scale |ref|                               test_gpu_optim (docstring)
+  optim.FusedAdamW._step_fused    floor form, gc = |g coef| with the coefficient that was armed: exp_avg scale   test_gpu_optim (docstring)
+                                  max(|m_old|, gc); exp_avg_sq max(v_old, gc^2); param |p_old| + step_size
+                                  (|m_old| + gc) / denom; tensors without a gradient keep their bits; step + 1
+profiles/r23/ has the two report tables of the detector step (mixed precision with everything on, two steps; fp32 defaults), every
+ratio below 1.  Three bounds that the composed step exceeded changed their FORM, in the unit test and here together, each for a scale the
+earlier form lacked: relation_bias (relation_bias_bound), bias_softmax_ (bias_softmax_bound) and criterion.match_cost (match_cost_scale).
 """
 from __future__ import annotations
 
@@ -306,10 +343,45 @@ def chk_add_layer_norm(a, res):
     return cmps
 
 
+def relation_bias_bound(src_boxes, tgt_boxes, proj_weight, num_pos_feats=16, temperature=10000.0, scale=100.0, eps=1e-5):
+    """1e-4 + 4 2^-24 sum_(coord, k) sqrt(W_sin^2 + W_cos^2) |a|  per (image, head, pair), a the sine argument of (coord, k).
+
+    The kernel follows the reference's fp32 operations: an argument a = RN(RN(e scale) / dim_t) of an fp32 logarithm e carries at
+    most 4 2^-24 |a| of rounding (logf to one ulp, i.e. two half-ulps, and one half-ulp for each of the two operations).  A
+    perturbation da moves W_sin sin a + W_cos cos a by da (W_sin cos a - W_cos sin a), at most |da| sqrt(W_sin^2 + W_cos^2).  A
+    constant cannot hold that: the arguments reach 100 |log(1e-5)| = 1.2e3 for a box of no width, which the noised denoising
+    queries of a real step do produce and the random boxes of the unit test (0.01 .. 0.5) do not, and the sum grows with the
+    weights.  For the two size-ratio coordinates the kernel forms the angle per box (tables of log(w_i + eps) scale / dim_t,
+    combined by the angle-difference identities), so their |a| is the sum of the two boxes'."""
+    src = _d(src_boxes)
+    tgt = src if tgt_boxes is None else _d(tgt_boxes)
+    c1, s1, c2, s2 = src[..., :2], src[..., 2:], tgt[..., :2], tgt[..., 2:]
+    dist = torch.log((c1[:, :, None, :] - c2[:, None, :, :]).abs() / (s1[:, :, None, :] + eps) + 1.0).abs()
+    ratio = (torch.log(s1 + eps).abs()[:, :, None, :] + torch.log(s2 + eps).abs()[:, None, :, :])
+    k = torch.arange(num_pos_feats // 2, dtype=torch.float64, device=src.device)
+    per_coord = torch.cat([dist, ratio], -1) * scale                                                  # [B, N1, N2, 4]
+    w = _d(proj_weight).reshape(proj_weight.shape[0], 4, num_pos_feats // 2, 2).pow(2).sum(-1).sqrt()  # per (head, coord, k)
+    w = (w / temperature ** (k * 2 / num_pos_feats)).sum(-1)                                          # [H, 4]
+    return 1e-4 + 4 * 2.0 ** -24 * torch.einsum("bnmc,hc->bhnm", per_coord, w)
+
+
 def chk_relation_bias(a, res):
     ref = torch_ref.relation_bias(_d(a["src_boxes"]), _d(a["tgt_boxes"]), _d(a["proj_weight"]), _d(a["proj_bias"]),
                                   a["num_pos_feats"], a["temperature"], a["scale"])
-    return [Cmp("out", res, ref, 1e-4)]
+    return [Cmp("out", res, ref, relation_bias_bound(a["src_boxes"], a["tgt_boxes"], a["proj_weight"], a["num_pos_feats"],
+                                                     a["temperature"], a["scale"]))]
+
+
+def bias_softmax_bound(logits, probs):
+    """2e-6 + 2^-22 max_row |logit| p  per element, from the float64 logits (scores + bias, -inf where masked) and probabilities.
+
+    The kernel rounds the sum scores + bias to fp32 and scales it to base 2 for the exponential: a logit l reaches the exponential
+    with two roundings, |dl| <= 2 2^-24 |l|.  p_i = exp(l_i) / sum_j exp(l_j) moves by p_i (dl_i - sum_j p_j dl_j), at most
+    2 p_i max |dl| = 2^-22 max |l| p_i.  The constant alone holds only while the logits stay small (the unit test's are below 20);
+    the fp32 decoder of a synthetic-weight network hands over logits in the hundreds, where one fp32 ulp of a logit is already
+    several 1e-6 of p.  The 2e-6 stays for the exponential's own error and the normalisation."""
+    size = torch.where(torch.isfinite(logits), logits.abs(), torch.zeros_like(logits)).amax(-1, keepdim=True)
+    return 2e-6 + 2.0 ** -22 * size * probs
 
 
 def chk_bias_softmax_(a, res):
@@ -319,7 +391,7 @@ def chk_bias_softmax_(a, res):
     if a["mask"] is not None:
         s = s.masked_fill(a["mask"].bool(), float("-inf"))
     ref = s.softmax(-1)
-    return [Cmp("probs", res, ref, 2e-6)]
+    return [Cmp("probs", res, ref, bias_softmax_bound(s, torch.nan_to_num(ref, nan=0.0)))]
 
 
 def _attention(q, k, v, H, bias, mask, scale):
@@ -674,7 +746,8 @@ HOST_ONLY = frozenset({
 
 
 # ------------------------------------------------------------------------------ training entries outside ops.py
-TRAIN_MODULES = ("ffn_train", "ln_train", "attn_rel_train", "msda_train_hm")
+TRAIN_MODULES = ("ffn_train", "ln_train", "attn_rel_train", "msda_train_hm", "amp_train", "neck", "denoising", "criterion", "optim")
+TRAIN_CLASSES = {"optim": ("FusedAdamW",)}       # classes whose methods are classified like module-level functions ("module.Class.method")
 LN_EPS = 1e-5                    # add_layer_norm_backward takes no eps: every norm of the network keeps nn.LayerNorm's default
 TAU = 8e-3                       # |pre-activation relation bias| below which the bf16 sine features may switch the ReLU branch
 
@@ -682,7 +755,10 @@ TAU = 8e-3                       # |pre-activation relation bias| below which th
 def train_functions(module) -> List[str]:
     """Every module-level function defined in one of the training modules, as "module.function"."""
     short = module.__name__.rsplit(".", 1)[-1]
-    return sorted(f"{short}.{n}" for n, f in vars(module).items() if inspect.isfunction(f) and f.__module__ == module.__name__)
+    names = [f"{short}.{n}" for n, f in vars(module).items() if inspect.isfunction(f) and f.__module__ == module.__name__]
+    for cls in TRAIN_CLASSES.get(short, ()):                   # and the methods of the classes named there, "module.Class.method"
+        names += [f"{short}.{cls}.{n}" for n, f in vars(getattr(module, cls)).items() if inspect.isfunction(f) and f.__module__ == module.__name__]
+    return sorted(names)
 
 
 def _bf16_form(ref):
@@ -812,6 +888,422 @@ def chk_grad_value_from_head_major(a, res):
     return [Cmp("out", res, ref)]
 
 
+# ------------------------------------------------------------------- the detector step: amp_train, neck, denoising, criterion, optim
+FLOOR = 2.0 ** -20               # 8 fp32 ulps of the scale: tests/test_gpu_criterion.py, test_gpu_denoising.py, test_gpu_optim.py
+GN_EPS = 1e-5                    # group_norm_levels_backward takes no eps: every GroupNorm of the neck keeps nn.GroupNorm's default
+F32, F64 = torch.float32, torch.float64
+
+
+def _floor_cmp(label, got, ref64, ref32, scale, rel=0.0, keep=None):
+    """|got - ref64| <= max(4 e32, 2^-20 scale) + rel |ref64|, e32 = |ref32 - ref64| the fp32 torch route's own error."""
+    ref64 = ref64.detach().double()
+    e32 = (ref32.detach().double().to(ref64.device) - ref64).abs()
+    scale = scale if torch.is_tensor(scale) else torch.full_like(ref64, float(scale))
+    return Cmp(label, got, ref64, torch.maximum(4 * e32, FLOOR * scale.double().to(ref64.device)) + rel * ref64.abs(), keep)
+
+
+def _within(label, got, ref64, ref32, floor_scale="element", rel=0.0, keep=None):
+    """tests/test_gpu_criterion.py::within: the floor's scale is max(1, |checker|), per element or of the whole tensor."""
+    r = ref64.detach().double().abs()
+    scale = r if floor_scale == "element" or not r.numel() else r.max().expand_as(r)
+    return _floor_cmp(label, got, ref64, ref32, scale.clamp(min=1.0), rel, keep)
+
+
+def _rb(t):
+    return None if t is None else t.detach().to(BF16)
+
+
+def chk_add_layer_norm_mixed_train(a, res):
+    """out (fp32) as add_layer_norm's fp32 bound, mean / rstd as ln_train.add_layer_norm_train, on the float64 sum of the stored operands."""
+    out, stats = res
+    s, mean, rstd = _ln_stats64(a["x"], a["residual"], a["eps"])
+    ref = _layer_norm(s, a["weight"], a["bias"], a["eps"])
+    mean, rstd = mean.reshape(-1), rstd.reshape(-1)
+    return [Cmp("out", out, ref, 2e-5), Cmp("mean", stats[:, 0], mean, 1e-5 * mean.abs().clamp_min(1.0)),
+            Cmp("rstd", stats[:, 1], rstd, 1e-5 * rstd.abs().clamp_min(1.0))]
+
+
+def chk_add_layer_norm_mixed_backward(a, res):
+    """The fp32 bounds of ln_train.add_layer_norm_backward on the fp32 dx; the bf16 dx is the rounding of the fp32 one (exact where
+    both are returned, else the fp32 bound + 2^-8 |ref|)."""
+    dx, dxb, dgamma, dbeta = res
+    x = a["x"]
+    s, mean, rstd = _ln_stats64(x, a["residual"], LN_EPS)
+    dy = a["dy"].float().double()
+    xhat = (s - mean) * rstd
+    g = dy * _d(a["weight"]).reshape(-1)
+    ref_dx = rstd * (g - g.mean(-1, keepdim=True) - xhat * (g * xhat).mean(-1, keepdim=True))
+    ref_dg, ref_db = (dy * xhat).reshape(-1, 256).sum(0), dy.reshape(-1, 256).sum(0)
+    top = lambda r: max(1.0, float(r.abs().max()) if r.numel() else 1.0)                               # noqa: E731
+    par = 1e-6 + 4 * 2.0 ** -24 * math.sqrt(x.numel() // 256)
+    cmps = []
+    if dx is not None:
+        cmps.append(Cmp("dx", dx, ref_dx, 1e-5 * top(ref_dx)))
+    if dxb is not None:
+        cmps.append(Cmp("dx_bf16", dxb, dx.to(BF16)) if dx is not None else
+                    Cmp("dx_bf16", dxb, ref_dx, 1e-5 * top(ref_dx) + 2.0 ** -8 * ref_dx.abs()))
+    assert cmps, "add_layer_norm_mixed_backward returned no dx"
+    if a["need_params"]:
+        cmps += [Cmp("dgamma", dgamma.reshape(-1), ref_dg, par * top(ref_dg)), Cmp("dbeta", dbeta.reshape(-1), ref_db, par * top(ref_db))]
+    else:
+        assert dgamma is None and dbeta is None
+    return cmps
+
+
+def chk_ffn_mixed_train(a, res):
+    """ffn_train.ffn_k256_train's checker on the operands rounded to bf16 (the kernel rounds them as it loads); the third result is
+    x's rounding itself, exact."""
+    out, hid, xlp = res
+    b = dict(x=_rb(a["x"]), w1=_rb(a["w1"]), b1=_rb(a["b1"]), w2=_rb(a["w2"]), b2=_rb(a["b2"]))
+    return chk_ffn_k256_train(b, (out, hid)) + [Cmp("x_bf16", xlp, b["x"])]
+
+
+def chk_ffn_mixed_backward(a, res):
+    """ffn_train.ffn_k256_backward's checker on the weights rounded to bf16.  The unrounded fp32 dx: (1e-6 + 4 2^-24 sqrt(F))
+    max(1, max |ref|) against float64 dH_returned @ bf16(w1), the running-sum form of tests/test_gpu_amp_train.py."""
+    cmps = chk_ffn_k256_backward(dict(dy=a["dy"], hid=a["hid"], w1=_rb(a["w1"]), w2=_rb(a["w2"])), res)
+    if a["fp32_dx"]:
+        ref = cmps[1].ref
+        cmps[1].bound = (1e-6 + 4 * 2.0 ** -24 * math.sqrt(a["w1"].shape[0])) * max(1.0, float(ref.abs().max()) if ref.numel() else 1.0)
+    return cmps
+
+
+# -- neck: torch's own GroupNorm on the CPU, float64 and fp32, as tests/test_gpu_neck.py::cpu_group_norm
+def _cpu_group_norm(xs, ws, bs, gos, G, eps, dtype):
+    out = []
+    for i, (x, w, b) in enumerate(zip(xs, ws, bs)):
+        with torch.enable_grad():
+            x, w, b = (t.detach().cpu().to(dtype).requires_grad_() for t in (x, w, b))
+            y = F.group_norm(x, G, w, b, eps)
+            if gos is not None:
+                y.backward(gos[i].detach().cpu().to(dtype))
+        out.append((y.detach(), x.grad, w.grad, b.grad))
+    return out
+
+
+def _yardstick(ref64, cpu32):
+    """tests/test_gpu_neck.py::yardstick_bound: 4 max(torch's fp32 CPU kernel's own error, 2^-23 max |ref|), per tensor."""
+    own = float((cpu32.double() - ref64).abs().max()) if ref64.numel() else 0.0
+    return 4.0 * max(own, 2.0 ** -23 * (float(ref64.abs().max()) if ref64.numel() else 0.0))
+
+
+def _group_stats(xs, G, eps, dtype):
+    """mean, rstd [L, B, G] of the levels as ``dtype`` arithmetic of torch on the CPU gives them."""
+    B = xs[0].shape[0]
+    flat = [x.detach().cpu().to(dtype).reshape(B, G, -1) for x in xs]
+    return torch.stack([f.mean(-1) for f in flat]), torch.stack([(f.var(-1, unbiased=False) + eps).rsqrt() for f in flat])
+
+
+def chk_group_norm_levels_forward(a, res):
+    ys, mean, rstd = res
+    G, eps, xs = a["num_groups"], a["eps"], a["xs"]
+    ref64 = _cpu_group_norm(xs, a["weights"], a["biases"], None, G, eps, F64)
+    cpu32 = _cpu_group_norm(xs, a["weights"], a["biases"], None, G, eps, F32)
+    cmps = []
+    for l, y in enumerate(ys):
+        r = ref64[l][0]
+        cmps.append(Cmp(f"y{l}", y, r, _yardstick(r, cpu32[l][0]) + (2.0 ** -8 * r.abs() if y.dtype == BF16 else 0.0)))
+    m64, r64 = _group_stats(xs, G, eps, F64)
+    _, r32 = _group_stats(xs, G, eps, F32)
+    cmps.append(Cmp("mean", mean, m64, 4 * 2.0 ** -23 * max(1.0, float(m64.abs().max()))))
+    cmps.append(Cmp("rstd", rstd, r64, _yardstick(r64, r32)))
+    return cmps
+
+
+def chk_group_norm_levels_backward(a, res):
+    """The statistics are recomputed in float64 from the levels (not the handed fp32 ones): what the forward launch handed over is
+    part of what is checked."""
+    dxs, dgamma, dbeta = res
+    G, xs = a["num_groups"], a["xs"]
+    zeros = [torch.zeros_like(w) for w in a["weights"]]
+    ref64 = _cpu_group_norm(xs, a["weights"], zeros, a["grads"], G, GN_EPS, F64)
+    cpu32 = _cpu_group_norm(xs, a["weights"], zeros, a["grads"], G, GN_EPS, F32)
+    cmps = []
+    for l, dx in enumerate(dxs):
+        r = ref64[l][1]
+        cmps.append(Cmp(f"dx{l}", dx, r, _yardstick(r, cpu32[l][1]) + (2.0 ** -8 * r.abs() if dx.dtype == BF16 else 0.0)))
+        cmps.append(Cmp(f"dgamma{l}", dgamma[l], ref64[l][2], _yardstick(ref64[l][2], cpu32[l][2])))
+        cmps.append(Cmp(f"dbeta{l}", dbeta[l], ref64[l][3], _yardstick(ref64[l][3], cpu32[l][3])))
+    return cmps
+
+
+def _cpu_masks(mask, level_hw):
+    fm = mask.detach().cpu().float()
+    masks = [F.interpolate(fm[None], size=tuple(hw))[0].to(torch.bool) for hw in level_hw]
+    return masks, [(~m).int().cumsum(1, dtype=torch.int32) for m in masks], [(~m).int().cumsum(2, dtype=torch.int32) for m in masks]
+
+
+def chk__masks_and_counts(a, res):
+    masks, cum = res
+    want, ys, xs = _cpu_masks(a["mask"], a["level_hw"])
+    packed = torch.cat([t.reshape(-1) for t in (*ys, *xs)])
+    return [Cmp(f"mask{l}", m, want[l]) for l, m in enumerate(masks)] + [Cmp("counts", cum, packed)]
+
+
+def chk__sine_pos_packed(a, res):
+    """float64 sin / cos of the fp32 argument, rebuilt on the CPU with the reference's single fp32 operations
+    (tests/test_gpu_neck.py::pos_reference): 5e-6, + 2^-8 |ref| in bf16."""
+    B, level_hw = a["B"], [tuple(int(v) for v in hw) for hw in a["level_hw"]]
+    cum = a["cum"].detach().cpu()
+    total, off, cmps = cum.numel() // 2, 0, []
+    dim_t = a["dim_t"].detach().cpu()
+    for l, (h, w) in enumerate(level_hw):
+        n = B * h * w
+        y, x = cum[off:off + n].view(B, h, w), cum[total + off:total + off + n].view(B, h, w)
+        off += n
+        if a["normalize"]:
+            ye = (y + a["offset"]) / (y[:, -1:, :] + a["eps"]) * a["scale"]
+            xe = (x + a["offset"]) / (x[:, :, -1:] + a["eps"]) * a["scale"]
+        else:
+            ye, xe = y + a["offset"], x + a["offset"]
+        assert ye.dtype == F32
+        ax, ay = (xe.unsqueeze(-1) / dim_t).double(), (ye.unsqueeze(-1) / dim_t).double()
+        px = torch.stack((ax.sin(), ax.cos()), -1).flatten(-2)
+        py = torch.stack((ay.sin(), ay.cos()), -1).flatten(-2)
+        ref = torch.cat((py, px), 3).permute(0, 3, 1, 2)
+        cmps.append(Cmp(f"pos{l}", res[l], ref, 5e-6 + (2.0 ** -8 * ref.abs() if res[l].dtype == BF16 else 0.0)))
+    return cmps
+
+
+# -- denoising
+def _denoising():
+    from relation_detr_amd import denoising
+    return denoising
+
+
+def chk_cdn_noise(a, res):
+    want = _denoising()._noise_numpy(int(a["key"]), int(a["Q"]), int(a["num_classes"]))
+    return [Cmp(n, got, torch.from_numpy(w)) for n, got, w in zip(("label_u", "label_r", "box_sign", "box_u"), res, want)]
+
+
+chk_cdn_noise.applies = lambda a: torch.device(a["device"]).type == "cuda"
+
+
+def chk_denoising_mask(a, res):
+    return [Cmp("mask", res, _denoising().denoising_mask(a["groups"], a["group_size"], a["num_queries"], "cpu", fused=False))]
+
+
+chk_denoising_mask.applies = lambda a: bool(a["fused"]) and torch.device(a["device"]).type == "cuda"
+
+
+def chk_cdn_queries_forward(a, res):
+    """Noised labels and label queries (copies of embedding rows) exact; the box queries against the module's torch route in
+    float64, max(4 e32, 2^-20 max(1, |ref|)) (tests/test_gpu_denoising.py)."""
+    dn = _denoising()
+    label_query, box_query, noised = res
+    counts, groups = [int(c) for c in a["counts"]], int(a["groups"])
+    noise, dev = a["noise"], a["embed"].device
+    if noise is None:
+        noise = tuple(torch.from_numpy(x).to(dev) for x in dn._noise_numpy(int(a["key"]), 2 * groups * sum(counts), a["embed"].shape[0]))
+    run = lambda boxes: dn._cdn_queries_torch(a["embed"].detach(), a["gt_labels"], boxes, counts, groups,       # noqa: E731
+                                              float(a["label_noise_prob"]), float(a["box_noise_scale"]), noise)
+    lq64, bq64, lab64 = run(a["gt_boxes"].double())
+    _, bq32, _ = run(a["gt_boxes"].float())
+    return [Cmp("noised_label", noised, lab64), Cmp("label_query", label_query, lq64), _within("box_query", box_query, bq64, bq32)]
+
+
+def chk_cdn_embed_backward(a, res):
+    grad, labels = a["grad_label_query"], a["noised_label"]
+    used = labels >= 0
+    index = labels[used].long()
+    d = grad.shape[-1]
+    ref64 = torch.zeros(a["num_classes"], d, dtype=F64, device=grad.device).index_add_(0, index, grad[used].double())
+    ref32 = torch.zeros(a["num_classes"], d, dtype=F32, device=grad.device).index_add_(0, index, grad[used].float())
+    return [_within("grad_embed", res, ref64, ref32, rel=0.0 if grad.dtype == F32 else 2.0 ** -8)]
+
+
+# -- criterion
+def _criterion():
+    from relation_detr_amd import criterion
+    return criterion
+
+
+def _match_cost_route(a, dtype):
+    crit = _criterion()
+    logits, boxes = a["logits"].detach().to(dtype), a["boxes"].detach().to(dtype)
+    R, N, _ = logits.shape
+    B, Gmax = a["gt_labels"].shape
+    counts = a["gt_count"].tolist()
+    cost = torch.zeros(R, N, Gmax, dtype=dtype, device=logits.device)
+    terms = torch.zeros_like(cost)
+    live = torch.zeros(R, 1, Gmax, dtype=torch.bool, device=logits.device)
+    for r in range(R):
+        g = min(max(int(counts[r % B]), 0), Gmax)
+        live[r, :, :g] = True
+        if g:
+            gt_b, gt_l = a["gt_boxes"][r % B, :g].to(dtype), a["gt_labels"][r % B, :g]
+            cost[r, :, :g] = crit._image_cost(logits[r], boxes[r], gt_b, gt_l, a["cost_class"], a["cost_bbox"], a["cost_giou"], a["alpha"],
+                                              a["gamma"])
+            # the magnitudes of what _image_cost adds up: both focal terms of the class cost, the L1 distance, the GIoU
+            prob = logits[r].sigmoid()
+            neg = (1 - a["alpha"]) * prob ** a["gamma"] * (1 - prob + 1e-6).log().abs()
+            pos = a["alpha"] * (1 - prob) ** a["gamma"] * (prob + 1e-6).log().abs()
+            valid = ((gt_l >= 0) & (gt_l < logits.shape[-1])).to(dtype)
+            lab = gt_l.clamp(0, logits.shape[-1] - 1).long()
+            giou = crit.generalized_box_iou(crit.box_cxcywh_to_xyxy(boxes[r]), crit.box_cxcywh_to_xyxy(gt_b)).abs()
+            terms[r, :, :g] = (a["cost_class"] * (pos[:, lab] + neg[:, lab]) * valid + a["cost_bbox"] * torch.cdist(boxes[r], gt_b, p=1)
+                               + a["cost_giou"] * giou)
+    return cost, live, terms
+
+
+def match_cost_scale(a):
+    """The floor's scale of a match cost: cost_class (|pos| + |neg|) + cost_bbox L1 + cost_giou |GIoU| per element, in float64.
+    The cost is the SIGNED sum of those terms and each carries the fp32 rounding of its own magnitude (the class cost alone is
+    the difference of two focal terms that reach 0.75 * 13.8 at a saturated logit), so an element where they cancel keeps the
+    rounding of the large ones: 8 fp32 ulps of the result itself, the floor's first form, held on the unit test's random stacks
+    and not on the proposals of a real step -- the reason tests/test_gpu_criterion.py already gives for the box gradients."""
+    return _match_cost_route(a, F64)[2]
+
+
+def chk_match_cost(a, res):
+    """The module's torch route in float64 (tests/test_gpu_criterion.py::test_match_cost); columns at or beyond an image's count are
+    exactly 0."""
+    ref64, live, terms = _match_cost_route(a, F64)
+    ref32 = _match_cost_route(a, F32)[0]
+    live = live.expand_as(ref64)
+    return [_floor_cmp("cost", res, ref64, ref32, terms.clamp(min=1.0), keep=live), Cmp("padded_columns", res, torch.zeros_like(ref64), keep=~live)]
+
+
+chk_match_cost.applies = lambda a: bool(a["fused"]) and a["logits"].is_cuda
+
+
+def _set_loss_route(a, dtype):
+    crit = _criterion()
+    with torch.enable_grad():
+        x = a["logits"].detach().to(dtype).requires_grad_(True)
+        b = a["boxes"].detach().to(dtype).requires_grad_(True)
+        sums = crit._set_loss_torch(x, b, a["match"], a["gt_boxes"].to(dtype), a["gt_labels"], int(a["n_split"]), a["inv_norm_a"],
+                                    a["inv_norm_b"], a["alpha"], a["gamma"])
+        dlogits, = torch.autograd.grad(sums[..., 0].sum(), x, retain_graph=True)
+        dl1, = torch.autograd.grad(sums[..., 1].sum(), b, retain_graph=True)
+        dgiou, = torch.autograd.grad(sums[..., 2].sum(), b)
+    return sums.detach(), dlogits, dl1, dgiou
+
+
+def chk_set_loss_forward(a, res):
+    """tests/test_gpu_criterion.py::test_set_loss: sums and dlogits per element (bf16 dlogits + 2^-8 |ref|), the box gradients with
+    the tensor's max |ref| in the floor."""
+    c64, c32 = _set_loss_route(a, F64), _set_loss_route(a, F32)
+    sums, dlogits, dl1, dgiou = res
+    return [_within("sums", sums, c64[0], c32[0]), _within("dlogits", dlogits, c64[1], c32[1], rel=0.0 if dlogits.dtype == F32 else 2.0 ** -8),
+            _within("dbox_l1", dl1, c64[2], c32[2], floor_scale="tensor"), _within("dbox_giou", dgiou, c64[3], c32[3], floor_scale="tensor")]
+
+
+def chk_assign_match(a, res):
+    """The device matcher as tests/test_gpu_assign.py checks it, without asking for scipy's table (ties): per row, the table is a valid
+    assignment over the image's count, its total cost on the copied costs is scipy's optimum to 1e-9 of the sum of magnitudes, the
+    denoising prefix is the fixed pattern and status is 0.  One compared element per row and property."""
+    import numpy as np
+    crit = _criterion()
+    match, status = res
+    cost = a["cost"].detach().cpu()
+    R, N, Gmax = cost.shape
+    counts, repeat, skip = [int(c) for c in a["gt_count"].tolist()], int(a["repeat"]), int(a["skip"])
+    B = len(counts)
+    used = cost.clone()
+    for r in range(R):
+        used[r, :, counts[r % B]:] = 0                                                      # scipy never sees the padding either
+    pairs = crit.hungarian_match(used, counts, repeat)
+    host, got = cost.double().numpy(), match.detach().cpu().numpy()
+    valid, total, want_total, tol = np.zeros(R), np.zeros(R), np.zeros(R), np.zeros(R)
+    for r in range(R):
+        g, m = counts[r % B], got[r, skip:]
+        ok = m.shape == (N,) and bool(((m >= -1) & (m < max(g, 1))).all()) and (g > 0 or bool((m == -1).all()))
+        if ok:
+            per_target = np.bincount(m[m >= 0], minlength=max(g, 1))[:max(g, 1)]
+            ok = bool((per_target == (repeat if g else 0)).all()) if g * repeat <= N else bool((m >= 0).all() and (per_target <= repeat).all())
+            q = np.nonzero(m >= 0)[0]
+            total[r] = host[r, q, m[q]].sum()
+        valid[r] = float(ok)
+        src, tgt = pairs[r]
+        chosen = host[r, src.numpy(), tgt.numpy()]
+        want_total[r], tol[r] = chosen.sum(), 1e-9 * np.abs(chosen).sum()
+    cmps = [Cmp("valid_assignment", torch.from_numpy(valid), torch.ones(R, dtype=F64)),
+            Cmp("total_cost", torch.from_numpy(total), torch.from_numpy(want_total), torch.from_numpy(tol)),
+            Cmp("status", status, torch.zeros(R, dtype=torch.int32))]
+    if skip:
+        groups, max_gt = int(a["dn_meta"][0]), int(a["dn_meta"][1])
+        slot = torch.arange(max_gt, dtype=torch.int32)
+        fixed = torch.stack([torch.where(slot < counts[r % B], slot, slot.new_tensor(-1)).repeat(groups) for r in range(R)])
+        same = (torch.from_numpy(got[:, :skip]) == fixed).all(1)
+        cmps.append(Cmp("denoising_prefix", same.double(), torch.ones(R, dtype=F64)))
+    return cmps
+
+
+chk_assign_match.applies = lambda a: bool(a["fused"]) and a["cost"].is_cuda          # the host matcher is scipy itself: no launch
+
+
+# -- optimizer: the torch route's single step in float64 from the kernel's own state before the step (tests/test_gpu_optim.py)
+def _optim_snapshot(a):
+    from helpers import snapshot
+    opt = a["self"]
+    return dict(a, rows=snapshot(opt), coef=None if opt._armed is None else opt._armed[-1].detach().clone())
+
+
+def chk_clip_fused(a, res):
+    """total norm and the armed coefficient: max(4 e32, 2^-20 |checker|)."""
+    from helpers import torch_route_step
+    opt, rows, max_norm = a["self"], a["rows"], float(a["max_norm"])
+    n64, _ = torch_route_step(opt, rows, max_norm, F64)
+    n32, _ = torch_route_step(opt, rows, max_norm, F32)
+    c64, c32 = (max_norm / (n64 + 1e-6)).clamp(max=1.0), (max_norm / (n32 + 1e-6)).clamp(max=1.0)
+    coef = opt.clip_coef
+    assert coef is not None, "_clip_fused armed no coefficient"
+    return [_floor_cmp("total_norm", res.reshape(1), n64.reshape(1), n32.reshape(1), n64.abs().reshape(1)),
+            _floor_cmp("coef", coef.reshape(1), c64.reshape(1), c32.reshape(1), c64.abs().reshape(1))]
+
+
+chk_clip_fused.snapshot = _optim_snapshot
+
+
+def chk_step_fused(a, res):
+    """Everything the step wrote, against the torch route stepped from the snapshot with the gradients scaled by the coefficient
+    that was armed (the value the kernel read).  Elementwise, gc = |g coef|: exp_avg max(4 e32, 2^-20 max(|m_old|, gc)); exp_avg_sq
+    max(4 e32, 2^-20 max(v_old, gc^2)); param max(4 e32, 2^-20 (|p_old| + step_size (|m_old| + gc) / denom64)); a tensor without
+    a gradient keeps its bits; every live state's step advances by one."""
+    from helpers import torch_route_step
+    from relation_detr_amd.optim import step_scalars
+    opt, rows, coef = a["self"], a["rows"], a["coef"]
+    scaled = lambda dtype: [dict(r, g=None if r["g"] is None else (r["g"].to(dtype) if coef is None else r["g"].to(dtype) * coef.to(dtype)))  # noqa: E731
+                            for r in rows]
+    _, want = torch_route_step(opt, scaled(F64), None, F64)
+    _, fp32 = torch_route_step(opt, scaled(F32), None, F32)
+    parts = {k: ([], [], [], []) for k in ("param", "exp_avg", "exp_avg_sq")}
+    steps_got, steps_want = [], []
+
+    def add(key, got, ref64, ref32, scale):
+        for lst, t in zip(parts[key], (got, ref64, ref32, scale)):
+            lst.append(t.detach().double().reshape(-1))
+    i = 0
+    for group in opt.param_groups:
+        beta1, beta2 = group["betas"]
+        for p in group["params"]:
+            row, (p64, m64, v64, g64), (p32, m32, v32, _) = rows[i], want[i], fp32[i]
+            state = opt.state.get(p) or {}
+            steps_got.append(float(state["step"]) if state else 0.0)
+            steps_want.append(row["step"] + (0.0 if row["g"] is None else 1.0))
+            if row["g"] is None:
+                add("param", p, row["p"], row["p"], torch.zeros_like(row["p"]))
+                if row["m"] is not None:
+                    add("exp_avg", state["exp_avg"], row["m"], row["m"], torch.zeros_like(row["m"]))
+                    add("exp_avg_sq", state["exp_avg_sq"], row["v"], row["v"], torch.zeros_like(row["v"]))
+            else:
+                step_size, bias2_sqrt = step_scalars(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], row["step"] + 1)[4:6]
+                m_old = torch.zeros_like(p64) if row["m"] is None else row["m"].double().abs()
+                v_old = torch.zeros_like(p64) if row["v"] is None else row["v"].double()
+                gc = g64.abs()
+                denom = v64.sqrt() / bias2_sqrt + group["eps"]
+                add("exp_avg", state["exp_avg"], m64, m32, torch.maximum(m_old, gc))
+                add("exp_avg_sq", state["exp_avg_sq"], v64, v32, torch.maximum(v_old, gc * gc))
+                add("param", p, p64, p32, row["p"].double().abs() + step_size * (m_old + gc) / denom)
+            i += 1
+    cmps = [_floor_cmp(k, *(torch.cat(lst) for lst in v)) for k, v in parts.items() if v[0]]
+    return cmps + [Cmp("step", torch.tensor(steps_got, dtype=F64), torch.tensor(steps_want, dtype=F64))]
+
+
+chk_step_fused.snapshot = _optim_snapshot
+
+# ------------------------------------------------------------------------------------------ every entry outside ops.py, one table
 TRAIN_ENTRIES: Dict[str, Callable] = {
     "ffn_train.ffn_k256_train": chk_ffn_k256_train,
     "ffn_train.ffn_k256_backward": chk_ffn_k256_backward,
@@ -821,16 +1313,63 @@ TRAIN_ENTRIES: Dict[str, Callable] = {
     "attn_rel_train._relation_attention_boxes_backward": chk__relation_attention_boxes_backward,
     "msda_train_hm.ms_deform_attn_backward_fused_hm": chk_ms_deform_attn_backward_fused_hm,
     "msda_train_hm.grad_value_from_head_major": chk_grad_value_from_head_major,
+    "amp_train.add_layer_norm_mixed_train": chk_add_layer_norm_mixed_train,
+    "amp_train.add_layer_norm_mixed_backward": chk_add_layer_norm_mixed_backward,
+    "amp_train.ffn_mixed_train": chk_ffn_mixed_train,
+    "amp_train.ffn_mixed_backward": chk_ffn_mixed_backward,
+    "neck.group_norm_levels_forward": chk_group_norm_levels_forward,
+    "neck.group_norm_levels_backward": chk_group_norm_levels_backward,
+    "neck._masks_and_counts": chk__masks_and_counts,
+    "neck._sine_pos_packed": chk__sine_pos_packed,
+    "denoising.cdn_noise": chk_cdn_noise,
+    "denoising.denoising_mask": chk_denoising_mask,
+    "denoising.cdn_queries_forward": chk_cdn_queries_forward,
+    "denoising.cdn_embed_backward": chk_cdn_embed_backward,
+    "criterion.match_cost": chk_match_cost,
+    "criterion.assign_match": chk_assign_match,
+    "criterion.set_loss_forward": chk_set_loss_forward,
+    "optim.FusedAdamW._clip_fused": chk_clip_fused,
+    "optim.FusedAdamW._step_fused": chk_step_fused,
 }
 
-# the rest of the four modules: routing predicates and argument helpers that launch nothing; ffn_train._pack, which launches a
+# the rest of the four training modules: routing predicates and argument helpers that launch nothing; ffn_train._pack, which launches a
 # re-layout only from inside a checked entry (as the ops packers); and the two public natural-log wrappers of attn_rel_train,
 # whose one launch is the checked private entry
+# and of the five modules of the detector step: routing predicates, argument checks, the torch routes (which serve as references above), the
+# differentiable wrappers whose launches are the checked entries, amp_train.ffn_pack_f32 and neck._gn_workspace (LAUNCH_INSIDE_ENTRY),
+# and every method of FusedAdamW but the two that launch
 TRAIN_HOST_ONLY = frozenset({
     "ffn_train.ffn_train_supported", "ffn_train._pack", "ffn_train._aligned_rows",
     "ln_train._aligned", "ln_train._rows", "ln_train.add_layer_norm_train_supported", "ln_train._param", "ln_train._entry",
     "attn_rel_train._f32", "attn_rel_train.relation_attention_boxes_train", "attn_rel_train.relation_attention_boxes_backward",
     "msda_train_hm._merged_slices", "msda_train_hm.split_merged_projection",
+    "amp_train.autocast_bf16_active", "amp_train.mixed_norm_operands_ok", "amp_train.add_layer_norm_mixed_supported",
+    "amp_train._ffn_dims_ok", "amp_train.ffn_mixed_supported", "amp_train.ffn_pack_f32",
+    "neck._stream", "neck._require_device", "neck._pointers", "neck._level_hw", "neck._gn_check", "neck._gn_workspace",
+    "neck.group_norm_levels", "neck._split_counts", "neck.pyramid_masks", "neck.sine_dim_t", "neck.pyramid_sine_pos", "neck._conv_norm",
+    "neck.build_pyramid",
+    "denoising.denoising_groups", "denoising.philox4x32_10", "denoising._noise_numpy", "denoising._layout", "denoising._suffix",
+    "denoising._cdn_queries_torch", "denoising._check_noise", "denoising.cdn_queries",
+    "criterion.box_cxcywh_to_xyxy", "criterion._inter_union", "criterion.box_iou", "criterion.generalized_box_iou", "criterion._image_cost",
+    "criterion._varifocal", "criterion._set_losses", "criterion._set_loss_torch", "criterion._rows", "criterion._suffix",
+    "criterion._check_stack", "criterion.hungarian_match", "criterion._dn_groups", "criterion.set_loss", "criterion._layer_keys",
+    "optim.build_chunk_map", "optim.step_scalars", "optim.fused_refusal", "optim.relation_param_groups", "optim.train_step",
+    "optim.FusedAdamW.__init__", "optim.FusedAdamW.add_param_group", "optim.FusedAdamW._params", "optim.FusedAdamW._on_fused_route",
+    "optim.FusedAdamW._first_param", "optim.FusedAdamW._check_flags", "optim.FusedAdamW._check_groups", "optim.FusedAdamW._init_state",
+    "optim.FusedAdamW._clip_torch", "optim.FusedAdamW._step_torch", "optim.FusedAdamW._gather", "optim.FusedAdamW._group_keys",
+    "optim.FusedAdamW._build_tables", "optim.FusedAdamW._prepare", "optim.FusedAdamW._prepared_still_holds",
+    "optim.FusedAdamW.clip_grad_norm_", "optim.FusedAdamW.step", "optim.FusedAdamW.load_state_dict",
+})
+
+
+# functions ("module.function") that name a launching rdetr_* symbol, or a *_workspace_bytes size, without being a checked entry:
+# each launches only from inside one.  tests/test_shadow_complete.py holds this from the source: every function of the package that
+# names such a symbol is an entry or listed here, and every caller of a listed function is an entry or listed.
+LAUNCH_INSIDE_ENTRY = frozenset({
+    "ops._packed_k256", "ops._packed_k_halves", "ops._packed_query_proj", "ops.ffn_k256_packed_weights", "ffn_train._pack",
+    "rowtail.linear_ln_rows", "amp_train.ffn_pack_f32",
+    "ln_train._entry",                                        # picks the symbol its two callers, both entries, launch
+    "ops._msda_backward_buffers", "neck._gn_workspace",      # callers of a *_workspace_bytes size
 })
 
 
@@ -863,7 +1402,12 @@ class Shadow:
         targets = [(ops, name, name, KERNEL_ENTRIES, HOST_ONLY) for name in ops_functions(ops)]
         for short in TRAIN_MODULES:
             module = importlib.import_module(f"relation_detr_amd.{short}")
-            targets += [(module, key.split(".", 1)[1], key, TRAIN_ENTRIES, TRAIN_HOST_ONLY) for key in train_functions(module)]
+            for key in train_functions(module):
+                *owners, attr = key.split(".")[1:]
+                owner = module
+                for name in owners:                                # "module.Class.method": patched on the class
+                    owner = getattr(owner, name)
+                targets.append((owner, attr, key, TRAIN_ENTRIES, TRAIN_HOST_ONLY))
         for module, attr, key, entries, host_only in targets if check else ():
             if key in host_only:
                 continue
@@ -889,13 +1433,19 @@ class Shadow:
 
     def _checked(self, name, fn, checker):
         sig = inspect.signature(fn)
+        # a checker may carry `applies(arguments) -> bool` (False: this call takes the function's host route, which launches
+        # nothing and is not recorded; the tripwire still stands behind it) and `snapshot(arguments) -> copies` (its own
+        # pre-call copy, for operands that are not tensor arguments: an optimizer's parameters, state and armed coefficient)
+        applies, snapshot = getattr(checker, "applies", None), getattr(checker, "snapshot", None)
 
         def wrapper(*args, **kwargs):
-            call = self.calls[name]
-            self.calls[name] += 1
             bound = sig.bind(*args, **kwargs)
             bound.apply_defaults()
-            copies = {k: _copy(v) for k, v in bound.arguments.items()}
+            if applies is not None and not applies(bound.arguments):
+                return fn(*args, **kwargs)
+            call = self.calls[name]
+            self.calls[name] += 1
+            copies = snapshot(bound.arguments) if snapshot is not None else {k: _copy(v) for k, v in bound.arguments.items()}
             self.depth += 1
             try:
                 result = fn(*args, **kwargs)
@@ -908,7 +1458,8 @@ class Shadow:
             strict, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
             torch.use_deterministic_algorithms(False)
             try:
-                with torch.no_grad():
+                # autocast off: the fp32 torch routes that give e32 must run in fp32 (float64 is never autocast)
+                with torch.no_grad(), torch.autocast("cuda", enabled=False):
                     self._record(name, call, checker(copies, result))
             finally:
                 torch.use_deterministic_algorithms(strict, warn_only=warn)

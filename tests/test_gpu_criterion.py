@@ -5,7 +5,8 @@ route run in fp32 on the same values against the checker, computed here, element
     |kernel - checker| <= max(4 * e32, 2^-20 * max(1, |checker|))
 elementwise: the kernels compute in fp32 like the fp32 route, in another operation order (the factor 4), and 2^-20 = 8 fp32 ulps
 covers the elements where the fp32 route happens to round to the checker.  Box gradients use max |checker| of the tensor in the
-floor (their terms cancel, so a small element carries the rounding of the large ones); bf16 ``dlogits`` are rounded once to bf16:
+floor (their terms cancel, so a small element carries the rounding of the large ones), the match cost for the same reason the
+summed magnitude of its own terms (tests/shadow.py, match_cost_scale); bf16 ``dlogits`` are rounded once to bf16:
 2^-8 |checker| + 4 * e32, and the bf16 gradient that autograd returns twice (the saved ``dlogits``, then its product with the
 upstream gradient): ((1 + 2^-8)^2 - 1) |checker| + 4 * e32.  With ``RDETR_CRITERION_ERRORS=<file>`` the worst error of each
 quantity, as a fraction of its bound, is written there (profiles/r16/criterion_errors.txt)."""
@@ -45,7 +46,7 @@ def within(what, got, checker, fp32, floor_scale="element", rel=0.0):
         return
     assert torch.isfinite(got).all(), what
     e32 = (fp32 - checker).abs()
-    scale = checker.abs() if floor_scale == "element" else checker.abs().max()
+    scale = floor_scale.to(F64) if torch.is_tensor(floor_scale) else checker.abs() if floor_scale == "element" else checker.abs().max()
     bound = torch.maximum(4 * e32, FLOOR * scale.clamp(min=1.0)) + rel * checker.abs()
     err = (got - checker).abs()
     frac = (err / bound).max().item()
@@ -89,7 +90,11 @@ def test_match_cost(R, N, C, counts, dtype):
     assert got.dtype == F32 and tuple(got.shape) == (R, N, gt_boxes.shape[1])
     checker = crit.match_cost(logits.to(F64), boxes.to(F64), gt_boxes.to(F64), gt_labels, gt_count, fused=False)
     fp32 = crit.match_cost(logits.to(F32), boxes, gt_boxes, gt_labels, gt_count, fused=False)
-    within(f"match_cost {'f32' if dtype == F32 else 'bf16'}", got, checker, fp32)
+    # the floor's scale is the magnitude of the terms the cost adds up, not of their signed sum (tests/shadow.py, match_cost_scale)
+    import shadow
+    scale = shadow.match_cost_scale(dict(logits=logits, boxes=boxes, gt_boxes=gt_boxes, gt_labels=gt_labels, gt_count=gt_count, cost_class=2.0,
+                                         cost_bbox=5.0, cost_giou=2.0, alpha=0.25, gamma=2.0))
+    within(f"match_cost {'f32' if dtype == F32 else 'bf16'}", got, checker, fp32, floor_scale=scale)
     for r in range(R):
         assert (got[r, :, counts[r % len(counts)]:] == 0).all()                             # padded columns: exactly 0
     assert counts[0] == 0 or (got[0, :, :counts[0]] != 0).all()

@@ -14,6 +14,7 @@ import copy
 import pytest
 import torch
 
+from helpers import snapshot, torch_route_step
 from relation_detr_amd.optim import CHUNK, FusedAdamW, relation_param_groups, step_scalars, train_step
 
 pytestmark = pytest.mark.gpu
@@ -25,45 +26,6 @@ SIZES = (1, 3, 4, 5, 91, 256, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 3)
 
 
 # ------------------------------------------------------------------------------------------------------------------------ checker
-def snapshot(opt):
-    """The optimizer's tensors before a step, in group order: per parameter (p, m, v, step, grad), clones on the device."""
-    rows = []
-    for group in opt.param_groups:
-        for p in group["params"]:
-            s = opt.state.get(p) or {}
-            rows.append(dict(p=p.detach().clone(), m=s["exp_avg"].clone() if s else None, v=s["exp_avg_sq"].clone() if s else None,
-                             step=float(s["step"]) if s else 0.0, g=None if p.grad is None else p.grad.detach().clone(),
-                             requires_grad=p.requires_grad))
-    return rows
-
-
-def torch_route_step(opt, rows, max_norm, dtype):
-    """One clip + step of the torch route in ``dtype`` from ``rows`` under ``opt``'s current group settings ->
-    (norm, per parameter (p, m, v, scaled gradient))."""
-    groups, params, i = [], [], 0
-    for group in opt.param_groups:
-        mine = []
-        for _ in group["params"]:
-            q = torch.nn.Parameter(rows[i]["p"].to(dtype, copy=True), requires_grad=rows[i]["requires_grad"])
-            q.grad = None if rows[i]["g"] is None else rows[i]["g"].to(dtype, copy=True).contiguous()
-            mine.append(q)
-            i += 1
-        params += mine
-        groups.append({"params": mine, **{k: group[k] for k in ("lr", "betas", "eps", "weight_decay")}})
-    route = FusedAdamW(groups, fused=False)
-    for q, row in zip(params, rows):
-        if row["m"] is not None:
-            route.state[q] = {"step": torch.tensor(row["step"], dtype=F32), "exp_avg": row["m"].to(dtype, copy=True),
-                              "exp_avg_sq": row["v"].to(dtype, copy=True)}
-    norm = route.clip_grad_norm_(max_norm) if max_norm is not None else None
-    route.step()
-    out = []
-    for q in params:
-        s = route.state.get(q) or {}
-        out.append((q.detach(), s.get("exp_avg"), s.get("exp_avg_sq"), q.grad))
-    return norm, out
-
-
 class Worst:
     """The worst fraction of its bound per compared quantity; 0 / 0 counts as 0, anything / 0 as inf."""
 

@@ -273,6 +273,11 @@ def test_relation_bias_vs_oracle(rd, B, N1, N2):
     ref32 = torch_ref.relation_bias(src, tgt, w, b)
     np.testing.assert_allclose(out.cpu().numpy(), ref32.numpy(), rtol=0, atol=1e-4)
     np.testing.assert_allclose(out.cpu().numpy(), ref64.numpy(), rtol=0, atol=1e-4)
+    # and against float64 in the form the shadow harness holds every relation_bias launch to (tests/shadow.py,
+    # relation_bias_bound: 1e-4 + the fp32 rounding of the sine arguments, scaled by the weights), which at these boxes and weights is the wider of the two
+    import shadow
+    err = (out.cpu().double() - torch_ref.relation_bias(src.double(), tgt.double(), w.double(), b.double())).abs()
+    assert bool((err <= shadow.relation_bias_bound(src, tgt, w)).all()), float(err.max())
 
 
 def test_relation_bias_generic_heads(rd):
@@ -391,6 +396,14 @@ def test_bias_softmax_vs_torch(rd, BH, N1, N2):
         out = rd.bias_softmax_(s.clone().to(DEV), None if bias is None else bias.to(DEV),
                                None if mask is None else mask.to(DEV))
         np.testing.assert_allclose(out.cpu().numpy(), ref.numpy(), rtol=0, atol=2e-6)
+        # and against float64 in the form the shadow harness holds every launch to (tests/shadow.py, bias_softmax_bound: the
+        # constant plus the fp32 rounding of the logits, which at these magnitudes adds at most 2^-22 * 20 = 5e-6 p)
+        import shadow
+        l64 = s.double() if bias is None else s.double() + bias.double()
+        if mask is not None:
+            l64 = l64.masked_fill(mask, float("-inf"))
+        p64 = torch.softmax(l64, -1)
+        assert bool(((out.cpu().double() - p64).abs() <= shadow.bias_softmax_bound(l64, p64)).all())
 
 
 def test_bias_softmax_inf_bias_rows(rd):

@@ -3,6 +3,9 @@ nor the built library: each entry's result is formed by the unfused torch sequen
 fp32 arithmetic, rounded where the kernel stores.  Every Cmp of the checker must pass on that -- the float64 reference alone
 stays inside its own bounds at these shapes -- and each corruption below must fail it.
 
+The second half does the same for the checkers of a detector step (amp_train, neck, denoising, criterion, optim): the module's own
+fp32 torch route as the "kernel", then one planted defect each.
+
 Shapes: FFN 37 rows x F = 64; LayerNorm 5 and 300 rows; attention B = 2, N = M = 37 with a block mask and one fully masked row;
 MSDA levels [(9, 7), (5, 4)], B = 2, one padded image.
 """
@@ -259,3 +262,512 @@ def test_msda_checkers(msda):
     low = want.masked_fill(mask[..., None], 0).clone()
     low.view(torch.int16)[0, 0, 0] ^= 1                                     # one bit of one element
     _fails(relayout, a, low, "one ulp in one element")
+
+
+# ====================================================================================== the detector step's checkers
+# amp_train, neck, denoising, criterion, optim: the "kernel result" is the module's own fp32 torch route on the same operands (the
+# checker's e32 yardstick is that route's error, so it passes by construction and by no wider margin than the bound's factor 4); then
+# one planted defect each, of the kind a kernel can have.
+F32, F64 = torch.float32, torch.float64
+
+
+def _cmp(key, args, res, label):
+    with torch.no_grad():
+        return next(c for c in shadow.TRAIN_ENTRIES[key](args, res) if c.label == label)
+
+
+def _bump(key, args, res, label, tensor, idx, factor=4.0):
+    """`tensor` (the part of `res` that Cmp `label` compares) with element `idx` moved `factor` times its bound off the reference."""
+    c = _cmp(key, args, res, label)
+    bound = c.bound[idx] if torch.is_tensor(c.bound) else c.bound
+    out = tensor.clone()
+    out[idx] = (c.ref[idx].double() + factor * float(bound)).to(out.dtype)
+    return out
+
+
+def _labels(bad):
+    return " ".join(w for w, _, _ in bad)
+
+
+def test_new_entries_are_all_exercised_here():
+    new = {k for k in shadow.TRAIN_ENTRIES if k.split(".")[0] in ("amp_train", "neck", "denoising", "criterion", "optim")}
+    assert new == set(DETECTOR_CASES), (sorted(new - set(DETECTOR_CASES)), sorted(set(DETECTOR_CASES) - new))
+
+
+DETECTOR_CASES = {}
+
+
+def _case(key):
+    def register(fn):
+        DETECTOR_CASES[key] = fn
+        return fn
+    return register
+
+
+# ------------------------------------------------------------------------------------------------- mixed LayerNorm / FFN
+@_case("amp_train.add_layer_norm_mixed_train")
+def test_mixed_layer_norm_forward():
+    key = "amp_train.add_layer_norm_mixed_train"
+    x, r, w, b, _ = _ln_case(BF, 37, True)
+    r, w, b = r.float() * 1.01, w.float(), b.float()                         # bf16 x, fp32 residual and parameters
+    s = x.float() + r
+    out = torch.nn.functional.layer_norm(s, (256,), w, b, 1e-5)
+    stats = torch.stack([s.mean(-1), (s.var(-1, unbiased=False) + 1e-5).rsqrt()], -1)
+    a = dict(x=x, residual=r, weight=w, bias=b, eps=1e-5)
+    _passes(key, a, (out, stats))
+    assert "out[11, 5]" in _labels(_fails(key, a, (_bump(key, a, (out, stats), "out", out, (11, 5)), stats), "one element 4 x its bound off"))
+    alone = torch.nn.functional.layer_norm(x.float(), (256,), w, b, 1e-5)
+    assert "out" in _labels(_fails(key, a, (alone, stats), "the residual not added"))
+    bumped = stats.clone()
+    bumped[20, 1] *= 1 + 2.0 ** -14
+    assert "rstd[20]" in _labels(_fails(key, a, (out, bumped), "one rstd off by 2^-14"))
+
+
+@_case("amp_train.add_layer_norm_mixed_backward")
+def test_mixed_layer_norm_backward():
+    key = "amp_train.add_layer_norm_mixed_backward"
+    x, r, w, b, dy = _ln_case(BF, 300, True)
+    r, w, dy = r.float() * 1.01, w.float(), dy.float()
+    s = (x.float() + r).requires_grad_(True)
+    wf = w.clone().requires_grad_(True)
+    bfl = b.float().requires_grad_(True)
+    torch.nn.functional.layer_norm(s, (256,), wf, bfl, 1e-5).backward(dy)
+    dx, dg, db = s.grad, wf.grad, bfl.grad
+    stats = torch.zeros(300, 2)
+    a = dict(dy=dy, x=x, residual=r, stats=stats, weight=w, need_params=True)
+    res = (dx, dx.to(BF), dg, db)
+    _passes(key, a, res)
+    _passes(key, dict(a, need_params=False), (dx, dx.to(BF), None, None))
+    _passes(key, dict(a, residual=None, x=(x.float() + r).to(BF)), (None,) + _mixed_ln_bf16_only(x, r, w, dy))
+    assert "dx[7, 9]" in _labels(_fails(key, a, (_bump(key, a, res, "dx", dx, (7, 9)), dx.to(BF), dg, db), "dx element 4 x its bound off"))
+    low = dx.to(BF)
+    low.view(torch.int16)[3, 3] ^= 1
+    assert "dx_bf16[3, 3]" in _labels(_fails(key, a, (dx, low, dg, db), "the bf16 dx one ulp from the rounding of the fp32 dx"))
+    big = int(dg.abs().argmax())
+    assert f"dgamma[{big}]" in _labels(_fails(key, a, (dx, dx.to(BF), _bump(key, a, res, "dgamma", dg, (big,)), db), "dgamma 4 x its bound off"))
+
+
+def _mixed_ln_bf16_only(x, r, w, dy):
+    xb = (x.float() + r).to(BF)
+    s = xb.float().requires_grad_(True)
+    wf = w.clone().requires_grad_(True)
+    bfl = torch.zeros(256, requires_grad=True)
+    torch.nn.functional.layer_norm(s, (256,), wf, bfl, 1e-5).backward(dy)
+    return s.grad.to(BF), wf.grad, bfl.grad
+
+
+@pytest.fixture(scope="module")
+def ffn32(ffn):
+    """The bf16 fixture's operands as fp32 tensors that are NOT bf16 values (the kernel rounds them), results from the rounded ones."""
+    g = torch.Generator().manual_seed(8)
+    jitter = lambda t: t.float() * (1 + 2.0 ** -8 * torch.rand(t.shape, generator=g))                  # noqa: E731
+    x, w1, b1, w2, b2 = (jitter(ffn["fwd"][k]) for k in ("x", "w1", "b1", "w2", "b2"))
+    rb = lambda t: t.to(BF).float()                                                                      # noqa: E731
+    hid = torch.relu(rb(x) @ rb(w1).t() + rb(b1)).to(BF)
+    out = (hid.float() @ rb(w2).t() + rb(b2)).to(BF)
+    dy = ffn["bwd"]["dy"].float()
+    dh = (dy.to(BF).float() @ rb(w2)).to(BF) * (hid > 0)
+    dx = dh.float() @ rb(w1)
+    return dict(fwd=dict(x=x, w1=w1, b1=b1, w2=w2, b2=b2), bwd=dict(dy=dy, hid=hid, w1=w1, w2=w2, fp32_dx=True), out=out, hid=hid, dh=dh, dx=dx)
+
+
+@_case("amp_train.ffn_mixed_train")
+def test_mixed_ffn_forward(ffn32):
+    key, c = "amp_train.ffn_mixed_train", ffn32
+    xlp = c["fwd"]["x"].to(BF)
+    assert not torch.equal(xlp.float(), c["fwd"]["x"])
+    _passes(key, c["fwd"], (c["out"], c["hid"], xlp))
+    assert "out" in _labels(_fails(key, c["fwd"], (_scale_column(c["out"]), c["hid"], xlp), "out column scaled"))
+    assert "hid" in _labels(_fails(key, c["fwd"], (c["out"], _swap_blocks(c["hid"]), xlp), "hid blocks swapped"))
+    trunc = (c["fwd"]["x"].view(torch.int32) & -65536).view(F32).to(BF)                                # truncated, not rounded to nearest
+    assert not torch.equal(trunc, xlp)
+    assert "x_bf16" in _labels(_fails(key, c["fwd"], (c["out"], c["hid"], trunc), "x truncated instead of rounded"))
+
+
+@_case("amp_train.ffn_mixed_backward")
+def test_mixed_ffn_backward(ffn32):
+    key, c = "amp_train.ffn_mixed_backward", ffn32
+    res = (c["dx"], c["dh"])
+    _passes(key, c["bwd"], res)
+    _passes(key, dict(c["bwd"], fp32_dx=False), (c["dx"].to(BF), c["dh"]))
+    assert "dx[5, 17]" in _labels(_fails(key, c["bwd"], (_bump(key, c["bwd"], res, "dx", c["dx"], (5, 17)), c["dh"]), "dx 4 x its bound off"))
+    assert "dx" in _labels(_fails(key, c["bwd"], (c["dx"].to(BF).float(), c["dh"]), "the fp32 dx rounded to bf16 on the way"))
+    unrounded = c["dh"].float() @ c["bwd"]["w1"]                            # dx from the fp32 w1 instead of its bf16 rounding
+    assert "dx" in _labels(_fails(key, c["bwd"], (unrounded, c["dh"]), "w1 not rounded"))
+
+
+# ------------------------------------------------------------------------------------------------------------------ neck
+GN_LEVELS = ((9, 7), (5, 4), (1, 2))
+
+
+@pytest.fixture(scope="module")
+def gn():
+    g = torch.Generator().manual_seed(12)
+    B, C, G = 2, 32, 8
+    xs = [torch.randn(B, C, h, w, generator=g) + 0.3 for h, w in GN_LEVELS]
+    ws = [1.0 + 0.3 * torch.randn(C, generator=g) for _ in GN_LEVELS]
+    bs = [0.3 * torch.randn(C, generator=g) for _ in GN_LEVELS]
+    gos = [torch.randn(B, C, h, w, generator=g) for h, w in GN_LEVELS]
+
+    def run(groups):
+        out = []
+        for x, w, b, go in zip(xs, ws, bs, gos):
+            x, w, b = (t.clone().requires_grad_() for t in (x, w, b))
+            y = torch.nn.functional.group_norm(x, groups, w, b, 1e-5)
+            y.backward(go)
+            out.append((y.detach(), x.grad, w.grad, b.grad))
+        return out
+
+    def stats(groups):
+        flat = [x.reshape(B, groups, -1) for x in xs]
+        return torch.stack([f.mean(-1) for f in flat]), torch.stack([(f.var(-1, unbiased=False) + 1e-5).rsqrt() for f in flat])
+    return dict(G=G, xs=xs, ws=ws, bs=bs, gos=gos, run=run, stats=stats)
+
+
+@_case("neck.group_norm_levels_forward")
+def test_group_norm_forward_checker(gn):
+    key = "neck.group_norm_levels_forward"
+    a = dict(xs=gn["xs"], weights=gn["ws"], biases=gn["bs"], num_groups=gn["G"], eps=1e-5)
+    ys = [r[0] for r in gn["run"](gn["G"])]
+    mean, rstd = gn["stats"](gn["G"])
+    _passes(key, a, (ys, mean, rstd))
+    y1 = _bump(key, a, (ys, mean, rstd), "y1", ys[1], (1, 17, 2, 3))
+    assert "y1[1, 17, 2, 3]" in _labels(_fails(key, a, ([ys[0], y1, ys[2]], mean, rstd), "one element 4 x its bound off"))
+    wrong = torch.stack([(x.reshape(2, 4, -1).var(-1, unbiased=False) + 1e-5).rsqrt().repeat_interleave(2, 1) for x in gn["xs"]])
+    assert wrong.shape == rstd.shape
+    assert "rstd" in _labels(_fails(key, a, (ys, mean, wrong), "rstd taken with the wrong group size"))
+    assert "y0" in _labels(_fails(key, a, ([r[0] for r in gn["run"](4)], mean, rstd), "normalised over the wrong group size"))
+    swapped = [torch.nn.functional.group_norm(x, gn["G"], gn["ws"][(l + 1) % 3], gn["bs"][l], 1e-5) for l, x in enumerate(gn["xs"])]
+    assert "y0" in _labels(_fails(key, a, (swapped, mean, rstd), "another level's weight"))
+
+
+@_case("neck.group_norm_levels_backward")
+def test_group_norm_backward_checker(gn):
+    key = "neck.group_norm_levels_backward"
+    mean, rstd = gn["stats"](gn["G"])
+    a = dict(grads=gn["gos"], xs=gn["xs"], weights=gn["ws"], mean=mean, rstd=rstd, num_groups=gn["G"])
+    pack = lambda rows: ([r[1] for r in rows], torch.stack([r[2] for r in rows]), torch.stack([r[3] for r in rows]))    # noqa: E731
+    res = pack(gn["run"](gn["G"]))
+    _passes(key, a, res)
+    wrong = pack(gn["run"](4))                                              # the backward of statistics over groups twice the size
+    assert "dx0" in _labels(_fails(key, a, (wrong[0], res[1], res[2]), "rstd taken with the wrong group size"))
+    dg = _bump(key, a, res, "dgamma1", res[1][1], (13,))
+    dgamma = res[1].clone()
+    dgamma[1] = dg
+    assert "dgamma1[13]" in _labels(_fails(key, a, (res[0], dgamma, res[2]), "dgamma element 4 x its bound off"))
+    assert "dbeta" in _labels(_fails(key, a, (res[0], res[1], res[2].flip(0)), "dbeta levels reversed"))
+
+
+def _pyramid_mask():
+    m = torch.ones(2, 37, 53, dtype=torch.bool)
+    m[0, :, :] = False
+    m[1, :20, :31] = False
+    return m, [(10, 14), (5, 7), (3, 4)]
+
+
+@_case("neck._masks_and_counts")
+def test_masks_and_counts_checker():
+    key = "neck._masks_and_counts"
+    mask, level_hw = _pyramid_mask()
+    masks, ys, xs = shadow._cpu_masks(mask, level_hw)
+    cum = torch.cat([t.reshape(-1) for t in (*ys, *xs)])
+    a = dict(mask=mask, level_hw=level_hw)
+    _passes(key, a, (masks, cum))
+    _passes(key, dict(a, mask=mask.float() * 3.0), (masks, cum))
+    off = cum.clone()
+    off[200] += 1
+    assert "counts[200]" in _labels(_fails(key, a, (masks, off), "one running count off by one"))
+    flipped = [m.clone() for m in masks]
+    flipped[1][1, 2, 4] ^= True
+    assert "mask1[1, 2, 4]" in _labels(_fails(key, a, (flipped, cum), "one mask pixel flipped"))
+    assert "counts" in _labels(_fails(key, a, (masks, torch.cat([t.reshape(-1) for t in (*xs, *ys)])), "the two count halves exchanged"))
+
+
+@_case("neck._sine_pos_packed")
+@pytest.mark.parametrize("normalize,offset", [(True, -0.5), (False, 0.0)])
+def test_sine_pos_checker(normalize, offset):
+    from relation_detr_amd.neck import PositionEmbeddingSine, sine_dim_t
+    key = "neck._sine_pos_packed"
+    mask, level_hw = _pyramid_mask()
+    masks, ys, xs = shadow._cpu_masks(mask, level_hw)
+    cum = torch.cat([t.reshape(-1) for t in (*ys, *xs)])
+    pe = PositionEmbeddingSine(16, 10000, normalize, offset=offset, fused=False)
+    pos = [pe.forward_torch(m) for m in masks]
+    a = dict(cum=cum, B=2, level_hw=level_hw, dim_t=sine_dim_t(16, 10000), num_pos_feats=16, normalize=normalize, scale=pe.scale, eps=pe.eps,
+             offset=offset, dtype=F32)
+    _passes(key, a, pos)
+    _passes(key, dict(a, dtype=BF), [p.to(BF) for p in pos])
+    p1 = _bump(key, a, pos, "pos1", pos[1], (1, 20, 2, 3))
+    assert "pos1[1, 20, 2, 3]" in _labels(_fails(key, a, [pos[0], p1, pos[2]], "one element 4 x its bound off"))
+    assert "pos0" in _labels(_fails(key, a, [torch.cat((p[:, 16:], p[:, :16]), 1) for p in pos], "the y and x halves exchanged"))
+
+
+# ------------------------------------------------------------------------------------------------------------- denoising
+DN_C = 7
+
+
+@pytest.fixture(scope="module")
+def cdn():
+    from relation_detr_amd import denoising as dn
+    g = torch.Generator().manual_seed(21)
+    counts, groups = [3, 0, 5], 2
+    G = sum(counts)
+    labels = torch.randint(0, DN_C, (G,), generator=g)
+    boxes = torch.cat((0.05 + 0.9 * torch.rand(G, 2, generator=g), 0.02 + 0.5 * torch.rand(G, 2, generator=g)), -1)
+    embed = torch.randn(DN_C, 64, generator=g)
+    key = 0xC0FFEE
+    noise = dn.cdn_noise(key, 2 * groups * G, DN_C, "cpu")
+    args = dict(embed=embed, gt_labels=labels, gt_boxes=boxes, counts=counts, groups=groups, label_noise_prob=0.6, box_noise_scale=1.0,
+                noise=noise, key=None)
+    res = dn._cdn_queries_torch(embed, labels, boxes, counts, groups, 0.6, 1.0, noise)
+    return dict(dn=dn, args=args, res=res, key=key, Q=2 * groups * G)
+
+
+@_case("denoising.cdn_noise")
+def test_cdn_noise_checker(cdn):
+    key, dn = "denoising.cdn_noise", cdn["dn"]
+    a = dict(key=cdn["key"], Q=cdn["Q"], num_classes=DN_C, device="cuda:0")
+    assert shadow.TRAIN_ENTRIES[key].applies(a) and not shadow.TRAIN_ENTRIES[key].applies(dict(a, device="cpu"))
+    draws = dn.cdn_noise(cdn["key"], cdn["Q"], DN_C, "cpu")
+    _passes(key, a, draws)
+    shifted = dn.cdn_noise(cdn["key"], cdn["Q"] + 1, DN_C, "cpu")            # row r holds the draw of counter r + 1
+    assert "box_u" in _labels(_fails(key, a, (draws[0], draws[1], draws[2], shifted[3][1:]), "one draw shifted by one counter"))
+    assert "label_r" in _labels(_fails(key, a, dn.cdn_noise(cdn["key"] + 1, cdn["Q"], DN_C, "cpu"), "another key"))
+
+
+@_case("denoising.denoising_mask")
+def test_denoising_mask_checker(cdn):
+    key, dn = "denoising.denoising_mask", cdn["dn"]
+    a = dict(groups=2, group_size=10, num_queries=9, device="cuda:0", fused=True)
+    entry = shadow.TRAIN_ENTRIES[key]
+    assert entry.applies(a) and not entry.applies(dict(a, fused=False)) and not entry.applies(dict(a, device="cpu"))
+    mask = dn.denoising_mask(2, 10, 9, "cpu", fused=False)
+    _passes(key, a, mask)
+    seen = mask.clone()
+    seen[3, 14] = False                                                       # a denoising query sees another group
+    assert "mask[3, 14]" in _labels(_fails(key, a, seen, "one pair visible across groups"))
+
+
+@_case("denoising.cdn_queries_forward")
+def test_cdn_queries_checker(cdn):
+    key, dn, a, res = "denoising.cdn_queries_forward", cdn["dn"], cdn["args"], cdn["res"]
+    _passes(key, a, res)
+    _passes(key, dict(a, noise=None, key=cdn["key"]), res)                   # the keyed call: the checker rebuilds the draws
+    box = _bump(key, a, res, "box_query", res[1], (2, 13, 1))
+    assert "box_query[2, 13, 1]" in _labels(_fails(key, a, (res[0], box, res[2]), "one box element 4 x its bound off"))
+    shifted = dn.cdn_noise(cdn["key"], cdn["Q"] + 1, DN_C, "cpu")
+    other = dn._cdn_queries_torch(a["embed"], a["gt_labels"], a["gt_boxes"], a["counts"], a["groups"], 0.6, 1.0,
+                                  (a["noise"][0], a["noise"][1], a["noise"][2], shifted[3][1:]))
+    assert "box_query" in _labels(_fails(key, a, other, "one noise draw shifted by one counter"))
+    pad = res[0].clone()
+    assert (res[2][1] < 0).all()
+    pad[1, 0, 0] = 1.0                                                        # image 1 has no box: its slots are padding, exactly 0
+    assert "label_query[1, 0, 0]" in _labels(_fails(key, a, (pad, res[1], res[2]), "a padded slot not zero"))
+
+
+@_case("denoising.cdn_embed_backward")
+def test_cdn_embed_backward_checker(cdn):
+    key = "denoising.cdn_embed_backward"
+    noised = cdn["res"][2]
+    grad = torch.randn(*noised.shape, 64, generator=torch.Generator().manual_seed(2))
+    used = noised >= 0
+    want = torch.zeros(DN_C, 64).index_add_(0, noised[used].long(), grad[used])
+    a = dict(grad_label_query=grad, noised_label=noised, num_classes=DN_C)
+    _passes(key, a, want)
+    _passes(key, dict(a, grad_label_query=grad.to(BF)), torch.zeros(DN_C, 64).index_add_(0, noised[used].long(), grad.to(BF)[used].float()).to(BF))
+    assert "grad_embed[3, 5]" in _labels(_fails(key, a, _bump(key, a, want, "grad_embed", want, (3, 5)), "one element 4 x its bound off"))
+    padded = torch.zeros(DN_C, 64).index_add_(0, noised.clamp(min=0).flatten().long(), grad.reshape(-1, 64))
+    assert "grad_embed[0" in _labels(_fails(key, a, padded, "the padded slots summed into class 0"))
+
+
+# ------------------------------------------------------------------------------------------------------------- criterion
+@pytest.fixture(scope="module")
+def crit_case():
+    from relation_detr_amd import criterion as crit
+    g = torch.Generator().manual_seed(31)
+    R, N, C, counts = 4, 23, 7, [3, 5]
+    B, Gmax = 2, 5
+    logits = (2 * torch.randn(R, N, C, generator=g)).clamp(-6, 6)
+    boxes = torch.cat((torch.rand(R, N, 2, generator=g), 0.02 + 0.4 * torch.rand(R, N, 2, generator=g)), -1)
+    gt_boxes = torch.cat((torch.rand(B, Gmax, 2, generator=g), 0.02 + 0.4 * torch.rand(B, Gmax, 2, generator=g)), -1)
+    gt_labels = torch.randint(0, C, (B, Gmax), generator=g, dtype=torch.int32)
+    gt_count = torch.tensor(counts, dtype=torch.int32)
+    cost_args = dict(logits=logits, boxes=boxes, gt_boxes=gt_boxes, gt_labels=gt_labels, gt_count=gt_count, cost_class=2.0, cost_bbox=5.0,
+                     cost_giou=2.0, alpha=0.25, gamma=2.0, fused=True, out=None)
+    cost = crit.match_cost(logits, boxes, gt_boxes, gt_labels, gt_count, fused=False)
+    return dict(crit=crit, cost_args=cost_args, cost=cost, counts=counts, R=R, N=N, C=C)
+
+
+@_case("criterion.match_cost")
+def test_match_cost_checker(crit_case):
+    key, c = "criterion.match_cost", crit_case
+    a, cost = c["cost_args"], c["cost"]
+    assert not shadow.TRAIN_ENTRIES[key].applies(a) and not shadow.TRAIN_ENTRIES[key].applies(dict(a, fused=False))      # CPU tensors
+    _passes(key, a, cost)
+    _passes(key, dict(a, logits=a["logits"].to(BF)), c["crit"].match_cost(a["logits"].to(BF), a["boxes"], a["gt_boxes"], a["gt_labels"],
+                                                                           a["gt_count"], fused=False))
+    assert "cost[2, 9, 1]" in _labels(_fails(key, a, _bump(key, a, cost, "cost", cost, (2, 9, 1)), "one element 4 x its bound off"))
+    dirty = cost.clone()
+    dirty[0, 4, 3] = 2.0 ** -30                                               # image 0 has 3 boxes: column 3 is padding
+    bad = _fails(key, a, dirty, "a padded cost column not zero")
+    assert len(bad) == 1 and "padded_columns[0, 4, 3]" in bad[0][0]
+    wrong_image = cost.clone()
+    wrong_image[1], wrong_image[3] = cost[3], cost[1]
+    assert "cost" in _labels(_fails(key, a, wrong_image.roll(1, 0), "rows against the other image's targets"))
+
+
+@_case("criterion.set_loss_forward")
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["f32", "bf16"])
+def test_set_loss_checker(crit_case, dtype):
+    key, c = "criterion.set_loss_forward", crit_case
+    g = torch.Generator().manual_seed(41)
+    ca = c["cost_args"]
+    match = torch.full((c["R"], c["N"]), -1, dtype=torch.int32)
+    for r in range(c["R"]):
+        match[r] = torch.randint(-1, c["counts"][r % 2], (c["N"],), generator=g, dtype=torch.int32)
+    a = dict(logits=ca["logits"].to(dtype), boxes=ca["boxes"], match=match, gt_boxes=ca["gt_boxes"], gt_labels=ca["gt_labels"], n_split=6,
+             inv_norm_a=1.0 / 12.0, inv_norm_b=1.0 / 5.0, alpha=0.25, gamma=2.0)
+    sums, dlogits, dl1, dgiou = shadow._set_loss_route(a, F32)
+    res = (sums, dlogits.to(dtype), dl1, dgiou)
+    _passes(key, a, res)
+    dl = _bump(key, a, res, "dlogits", res[1], (1, 8, 2), factor=4.0 if dtype == F32 else 8.0)
+    assert "dlogits[1, 8, 2]" in _labels(_fails(key, a, (sums, dl, dl1, dgiou), "one dlogits element off"))
+    other = shadow._set_loss_route(dict(a, n_split=7), F32)
+    assert not torch.equal(other[0], sums)
+    bad = _labels(_fails(key, a, (other[0], other[1].to(dtype), other[2], other[3]), "n_split off by one"))
+    assert "sums" in bad or "dlogits" in bad
+    assert "dbox_giou" in _labels(_fails(key, a, (sums, res[1], dl1, dl1), "the L1 gradient in the GIoU gradient's place"))
+    unscaled = shadow._set_loss_route(dict(a, inv_norm_a=1.0), F32)
+    assert "sums" in _labels(_fails(key, a, (unscaled[0], res[1], dl1, dgiou), "the denoising segment not normalised"))
+
+
+@_case("criterion.assign_match")
+def test_assign_match_checker(crit_case):
+    key, c = "criterion.assign_match", crit_case
+    crit, cost, counts = c["crit"], c["cost"], c["counts"]
+    entry = shadow.TRAIN_ENTRIES[key]
+    for repeat, skip, dn_meta in ((1, 0, None), (6, 0, None), (1, 10, (1, 10)), (1, 10, (2, 5))):
+        a = dict(cost=cost, gt_count=torch.tensor(counts, dtype=torch.int32), repeat=repeat, skip=skip, dn_meta=dn_meta, out=None, fused=True)
+        assert not entry.applies(a)                                           # a CPU cost goes to scipy: not a launch, not recorded
+        table, status = crit.assign_match(cost, counts, repeat, skip, dn_meta, fused=False)
+        _passes(key, a, (table, status))
+        m = table.clone()
+        row = m[2, skip:]
+        q = int((row >= 0).nonzero()[0])
+        free = (row < 0).nonzero().flatten() if repeat == 1 else (row != row[q]).nonzero().flatten()
+        worse = max(free.tolist(), key=lambda j: float(cost[2, j, row[q]]))
+        assert cost[2, worse, row[q]] > cost[2, q, row[q]]
+        if repeat == 1:
+            row[worse], row[q] = row[q], -1                                   # the target handed to a costlier query: still valid
+        else:
+            row[worse], row[q] = row[q].clone(), row[worse].clone()           # two queries exchange their targets
+        bad = _fails(key, a, (m, status), "one matched pair swapped to a costlier one")
+        assert len(bad) == 1 and "total_cost[2]" in bad[0][0], bad
+        twice = table.clone()
+        t = twice[1, skip:]
+        pair = (t >= 0).nonzero().flatten()[:2]
+        if repeat == 1:
+            t[pair[1]] = t[pair[0]]                                           # one gt matched twice, another never
+            assert "valid_assignment[1]" in _labels(_fails(key, a, (twice, status), "a gt matched twice"))
+        beyond = table.clone()
+        beyond[0, skip + 1] = 4                                               # image 0 has 3 boxes
+        assert "valid_assignment[0]" in _labels(_fails(key, a, (beyond, status), "an index at or beyond the image's count"))
+        flagged = status.clone()
+        flagged[3] = 1
+        assert "status[3]" in _labels(_fails(key, a, (table, flagged), "status not 0"))
+        if skip:
+            prefix = table.clone()
+            prefix[1, 4] = -1 if int(prefix[1, 4]) >= 0 else 0
+            bad = _fails(key, a, (prefix, status), "a denoising match outside the fixed pattern")
+            assert len(bad) == 1 and "denoising_prefix[1]" in bad[0][0], bad
+
+
+# ------------------------------------------------------------------------------------------------------------- optimizer
+def _optimizer(step2):
+    """A CPU FusedAdamW over five tensors in two groups -- one without a gradient -- before its first or second step."""
+    from relation_detr_amd.optim import FusedAdamW
+    g = torch.Generator().manual_seed(51)
+    params = [torch.nn.Parameter(torch.randn(n, generator=g)) for n in (5, 91, 256, 8193, 7)]
+    opt = FusedAdamW([{"params": params[:3]}, {"params": params[3:], "lr": 3e-4, "weight_decay": 0.0}], lr=1e-3, weight_decay=1e-2, fused=False)
+    for round_ in range(2 if step2 else 1):
+        for i, p in enumerate(params):
+            p.grad = None if i == 4 else torch.randn(p.shape, generator=g) * (1.0 if i != 1 else 1e-3)
+        if round_ == 0 and step2:
+            opt.step()
+    return opt, params
+
+
+def _apply_fp32_route(opt, rows, coef, unclipped_v=False, keep_step=False):
+    """Write what the fp32 torch route makes of `rows` into `opt` (the "kernel"), with the planted defects on request."""
+    from helpers import torch_route_step
+    scaled = [dict(r, g=None if r["g"] is None else r["g"] * coef) for r in rows]
+    _, out = torch_route_step(opt, scaled, None, F32)
+    _, raw = torch_route_step(opt, rows, None, F32)
+    i = 0
+    with torch.no_grad():
+        for group in opt.param_groups:
+            for p in group["params"]:
+                if rows[i]["g"] is not None:
+                    state = opt._init_state(p)
+                    p.copy_(out[i][0])
+                    state["exp_avg"].copy_(out[i][1])
+                    state["exp_avg_sq"].copy_(raw[i][2] if unclipped_v else out[i][2])
+                    state["step"] = torch.tensor(rows[i]["step"] + (0.0 if keep_step else 1.0))
+                i += 1
+
+
+@_case("optim.FusedAdamW._clip_fused")
+def test_clip_checker():
+    from helpers import snapshot, torch_route_step
+    key = "optim.FusedAdamW._clip_fused"
+    opt, _ = _optimizer(step2=True)
+    rows = snapshot(opt)
+    norm, _ = torch_route_step(opt, rows, 0.1, F32)
+    coef = (0.1 / (norm + 1e-6)).clamp(max=1.0)
+    assert coef < 1
+    a = dict(self=opt, max_norm=0.1, rows=rows, coef=None)
+    opt._armed = torch.stack([norm, coef])
+    _passes(key, a, norm)
+    assert "total_norm" in _labels(_fails(key, a, norm * (1 + 2.0 ** -18), "the norm 2^-18 off"))
+    partial = torch.cat([r["g"].flatten() for r in rows[:3] if r["g"] is not None]).norm()
+    assert "total_norm" in _labels(_fails(key, a, partial, "the norm of the first group alone"))
+    opt._armed = torch.stack([norm, torch.ones(())])
+    assert "coef" in _labels(_fails(key, a, norm, "the coefficient left at 1"))
+    opt._armed = None
+
+
+@_case("optim.FusedAdamW._step_fused")
+@pytest.mark.parametrize("step2", [False, True], ids=["first_step", "second_step"])
+def test_step_checker(step2):
+    from helpers import snapshot
+    key = "optim.FusedAdamW._step_fused"
+    coef = torch.tensor(0.0371)
+
+    def run(**defect):
+        opt, params = _optimizer(step2)
+        rows = snapshot(opt)
+        assert [r["step"] for r in rows] == ([1.0] * 4 + [0.0] if step2 else [0.0] * 5)
+        _apply_fp32_route(opt, rows, coef, **defect)
+        return dict(self=opt, rows=rows, coef=coef), params
+    a, params = run()
+    _passes(key, a, None)
+    a, params = run()
+    c = _cmp(key, a, None, "param")
+    at = 5 + 91 + 100                                                         # flat: the third tensor, element 100
+    with torch.no_grad():
+        params[2][100] = (c.ref[at] + 4 * c.bound[at]).float()
+    bad = _fails(key, a, None, "one parameter element 4 x its bound off")
+    assert len(bad) == 1 and f"param[{at}]" in bad[0][0], bad
+    a, params = run()
+    with torch.no_grad():
+        params[4][3] += 2.0 ** -20                                            # the tensor without a gradient keeps its bits
+    assert f"param[{5 + 91 + 256 + 8193 + 3}]" in _labels(_fails(key, a, None, "a tensor without a gradient written"))
+    a, _ = run(unclipped_v=True)
+    bad = _fails(key, a, None, "exp_avg_sq updated with the unclipped gradient")
+    assert len(bad) == 1 and "exp_avg_sq" in bad[0][0], bad
+    a, _ = run(keep_step=True)
+    bad = _fails(key, a, None, "step not advanced")
+    assert len(bad) == 1 and "step[0]" in bad[0][0], bad
+    a, _ = run()
+    a["coef"] = None                                                          # the reference then steps with the unclipped gradients
+    assert "exp_avg" in _labels(_fails(key, a, None, "the clip coefficient applied where none was armed"))
