@@ -156,8 +156,8 @@ int rdetr_msda_forward_sweep_bf16(const uint16_t *value, int value_layout, const
  * (ms_deform_attn_cuda_forward, ms_deform_attn_cuda.cu:12-72; kernel ms_deform_im2col_cuda.cuh:226-288), same per-query
  * arithmetic as the query-run kernel; the points of a query are accumulated in another order (coarse and fine levels
  * alternate), so results agree with rdetr_msda_forward_opt_bf16(..., RDETR_MSDA_DIRECT) to fp32 re-association: the last bit
- * of a bf16 output differs now and then (4e-5 of the outputs at the R50 shape).  One persistent 1024-thread workgroup per CU serves one (image, head) plane and keeps the
- * plane's COARSE levels -- as many trailing levels as fit beside the staging area in the CU's 160 KB of LDS (levels 2 and 3
+ * of a bf16 output differs now and then (4e-5 of the outputs at the R50 shape).  One persistent 12-wave (768-thread)
+ * workgroup per CU serves one (image, head) plane and keeps the plane's COARSE levels -- as many trailing levels as fit beside the staging area in the CU's 160 KB of LDS (levels 2 and 3
  * at the R50 800 x 1333 shape: half of all samples) -- resident in LDS: samples on those levels read their corner rows with
  * ds_read_b128 instead of through the texture path, whose instruction rate bounds the query-run kernel.
  * The LEVEL TABLE is passed as HOST pointers (the resident set is sized on the host; the reference reads spatial_shapes on

@@ -4,7 +4,7 @@
 // The shortest-augmenting-path method scipy runs (Crouse, "On implementing 2D rectangular assignment algorithms", 2016), in its
 // arithmetic: fp64 duals and path costs over the fp32 costs, so the optimum is scipy's wherever it is unique.  Row r of a stack
 // belongs to image r % B.
-#include "common.h"
+#include "launch.h"
 
 #include <math.h>
 
@@ -240,14 +240,11 @@ int assign_match(const float *cost, const int *gt_count, int R, int B, int N, in
     if (!cost || !gt_count || !match || !status) return RDETR_ERR_INVALID_ARG;
     if (R % B || (long long)dn_groups * dn_max_gt != skip || ld_match < (long long)skip + N) return RDETR_ERR_INVALID_ARG;
     if (N > kAssignMaxSide || (long long)Gmax * repeat > kAssignMaxSide) return RDETR_ERR_UNSUPPORTED;
-    if (!aligned_to(cost, 4) || !aligned_to(gt_count, 4) || !aligned_to(match, 4) || !aligned_to(status, 4)) return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(4, cost, gt_count, match, status)) return RDETR_ERR_UNSUPPORTED;
     const int copies = Gmax * repeat;                                      // a row's count is on the device: size for the largest
     const int n_long = N > copies ? N : copies, n_short = N > copies ? copies : N;
     const size_t lds = assign_lds_bytes(n_long, n_short);
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(assign_match_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                       (int)assign_lds_bytes(kAssignMaxSide, kAssignMaxSide));
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
+    if (const int s = ensure_dynamic_lds<assign_match_kernel>((int)assign_lds_bytes(kAssignMaxSide, kAssignMaxSide))) return s;
     hipLaunchKernelGGL(assign_match_kernel, dim3((unsigned)R), dim3(kAssignThreads), lds, static_cast<hipStream_t>(stream), cost,
                        gt_count, B, N, Gmax, repeat, skip, dn_max_gt > 0 ? dn_max_gt : 1, n_long, n_short, match, ld_match, status);
     return launch_status();

@@ -3,7 +3,7 @@
 // view of the row log-sum-exp, the host-side alignment test and the Di = rowsum(dO o O) launch.  Only what is identical in all
 // its users lives here; the soft-max and dS bodies differ per kernel on purpose and stay in their files.
 #pragma once
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 

@@ -268,10 +268,7 @@ static int launch_relation_attention_boxes(const uint16_t *q, const uint16_t *k,
     if (B > 65535 || (long long)M * (ldk > ldv ? ldk : ldv) * 2 >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const RelFreq fr = rel_freq(F, rel_scale, temperature);
-    // a function-local static of a function template: one per instantiation, so each kernel gets its own attribute call
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(relation_attention_boxes_kernel<kLse>),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kArLdsBytes);
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
+    if (const int s = ensure_dynamic_lds<relation_attention_boxes_kernel<kLse>>(kArLdsBytes)) return s;
     hipLaunchKernelGGL(relation_attention_boxes_kernel<kLse>, dim3((unsigned)((N + kRelTileQ - 1) / kRelTileQ), (unsigned)B),
                        dim3(kRelWaves * kWave), kArLdsBytes, st, q, k, v, ldq, ldk, ldv, src_boxes, tgt_boxes,
                        proj_weight, proj_bias, bool_mask, N, M, attn_scale * kLog2e, eps, fr, out, ldo, RDETR_AR_DBG, lse);

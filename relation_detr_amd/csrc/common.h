@@ -1,4 +1,4 @@
-// Shared device/host helpers for librelation_detr_amd (gfx950 only).
+// What the kernels of librelation_detr_amd share (gfx950 only).  The host wrappers' helpers are in launch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -14,6 +14,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kWave = 64;        // CDNA wavefront
 constexpr int kXcds = 8;         // MI355X: 8 XCDs, each with a private 4 MiB L2
+constexpr int kCus = 256;        // MI355X: 256 CUs (32 per XCD) -- host grid arithmetic; the runtime's count is device_cu_count()
 
 // Workgroups are dealt round-robin over the XCDs (block b and b+8 share an L2).  Map the hardware
 // block id to a logical id so that every XCD owns one contiguous chunk of the logical range:
@@ -48,13 +49,6 @@ __device__ __forceinline__ unsigned int pack_bf16x2(float a, float b)
 __device__ __forceinline__ unsigned int relu_bf16x2(unsigned int packed)
 {
     return __builtin_bit_cast(unsigned int, __builtin_elementwise_max(__builtin_bit_cast(s16x2_t, packed), s16x2_t{0, 0}));
-}
-
-inline bool aligned_to(const void *p, unsigned a) { return reinterpret_cast<uintptr_t>(p) % a == 0; }
-
-inline int launch_status()
-{
-    return hipGetLastError() == hipSuccess ? RDETR_OK : RDETR_ERR_LAUNCH;
 }
 
 }  // namespace rdetr

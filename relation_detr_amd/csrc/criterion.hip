@@ -3,7 +3,7 @@
 //   rdetr_set_loss_*    varifocal class loss, L1 and GIoU of a stack of matched sets, forward and gradient in one pass
 //                       (one launch + one launch that adds the per-workgroup partial sums in a fixed order).
 // fp32 math throughout; logits fp32 or bf16, boxes fp32.  Row r of a stack belongs to image r % B.
-#include "common.h"
+#include "launch.h"
 
 #include <math.h>
 
@@ -147,7 +147,7 @@ int match_cost(const T *logits, long long ld_logits, const float *boxes, long lo
         return RDETR_ERR_UNSUPPORTED;
     const long long pairs = (long long)N * Gmax, per_block = kCostThreads * kCostPerThread;
     const long long blocks = (pairs + per_block - 1) / per_block;
-    if (blocks > 0x7fffffffLL) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(blocks)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(match_cost_kernel<T>, dim3((unsigned)blocks, (unsigned)R), dim3(kCostThreads), (size_t)Gmax * 5 * sizeof(float),
                        static_cast<hipStream_t>(stream), logits, ld_logits, boxes, ld_boxes, gt_boxes, gt_labels, gt_count, B, N, C,
                        Gmax, alpha, gamma, w_class, w_bbox, w_giou, cost);

@@ -8,7 +8,7 @@
 // repeated ground truth, gt off[b] + t, copy i positive when even and negative when odd.  fp32 math in the reference's operation
 // order (the build has -ffp-contract=off).
 #include "cdn_noise.h"
-#include "common.h"
+#include "launch.h"
 
 #include <math.h>
 
@@ -122,7 +122,7 @@ int cdn_queries(const long long *gt_labels, const float *gt_boxes, const int *gt
         return RDETR_ERR_UNSUPPORTED;
     const long long work = (long long)B * n_dn * (d / per_vec);
     const long long blocks = (work + kCdnThreads - 1) / kCdnThreads;
-    if (blocks > 0x7fffffffLL) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(blocks)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(cdn_queries_kernel<T>, dim3((unsigned)blocks), dim3(kCdnThreads), 0, static_cast<hipStream_t>(stream), gt_labels,
                        gt_boxes, gt_offset, B, G, max_gt, groups, C, d, label_noise_prob, box_noise_scale, embed, label_u, label_r, box_sign,
                        box_u, keyed, key, label_query, box_query, noised_label);

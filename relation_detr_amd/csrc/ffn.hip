@@ -19,7 +19,7 @@
 #include <cstdlib>
 #include <utility>
 
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -33,6 +33,7 @@ constexpr int kFfnHC = 64;                 // hidden units per chunk
 constexpr int kFfnW1Bytes = kFfnHC * kFfnK * 2;          // 32 KiB: [4 tiles][8 k-steps][64 lanes] x 16 B
 constexpr int kFfnW2Bytes = kFfnK * kFfnHC * 2;          // 32 KiB: [16 out tiles][2 k-steps][64 lanes] x 16 B
 constexpr int kFfnBufBytes = kFfnW1Bytes + kFfnW2Bytes;
+constexpr int kFfnMaxLdsBytes = 2 * kFfnBufBytes + (4096 + 3 * kFfnK) * 4;      // dynamic LDS at the largest F served
 
 // fn(integral_constant<0>) ... fn(integral_constant<N - 1>)
 template <int... I, class Fn>
@@ -231,7 +232,7 @@ extern "C" int rdetr_ffn_k256_pack_bf16(const uint16_t *w1, const uint16_t *w2, 
     if (F <= 0) return RDETR_ERR_INVALID_ARG;
     if ((F % kFfnHC) || F > 4096) return RDETR_ERR_UNSUPPORTED;
     if (!w1 || !w2 || !packed) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(packed)) & 15) return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, w1, w2, packed)) return RDETR_ERR_UNSUPPORTED;
     const int total = (F / kFfnHC) * 64 * 64;
     hipLaunchKernelGGL(ffn_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), w1, w2, F,
                        reinterpret_cast<u32x4 *>(packed));
@@ -249,12 +250,10 @@ extern "C" int rdetr_ffn_k256_pack_f32(const float *w1, long long w1_row_stride,
     if ((F % kFfnHC) || F > 4096) return RDETR_ERR_UNSUPPORTED;
     if (!w1 || !w2 || !packed) return RDETR_ERR_INVALID_ARG;
     if ((b1 != nullptr) != (b2 != nullptr) || (b1 != nullptr) != (biases_bf16 != nullptr)) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(packed) & 15) || ((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2)) & 3) ||
-        (b1 && ((reinterpret_cast<uintptr_t>(b1) | reinterpret_cast<uintptr_t>(b2)) & 3)) || (reinterpret_cast<uintptr_t>(biases_bf16) & 1))
-        return RDETR_ERR_UNSUPPORTED;
+    if (!aligned_to(packed, 16) || !all_aligned(4, w1, w2, b1, b2) || !aligned_to(biases_bf16, 2)) return RDETR_ERR_UNSUPPORTED;
     // how a tile is walked: 2 = rows of contiguous 16-byte aligned floats, 1 = down the columns (a transposed view), 0 = along the rows
     auto mode = [](const float *w, long long rs, long long cs) {
-        if (cs == 1 && reinterpret_cast<uintptr_t>(w) % 16 == 0 && rs % 4 == 0) return 2;
+        if (cs == 1 && aligned_to(w, 16) && rs % 4 == 0) return 2;
         return rs < cs ? 1 : 0;
     };
     const int blocks = 2 * (F / kFfnHC) + (biases_bf16 ? (F + kFfnK + 255) / 256 : 0);
@@ -276,20 +275,17 @@ static int ffn_launch(const uint16_t *x, long long ldx, const uint16_t *packed, 
                       int F, uint16_t *out, long long ldo, const uint16_t *gamma, const uint16_t *beta, float eps, const uint16_t *pos,
                       long long ldp, uint16_t *out2, long long ldo2, void *stream)
 {
-    if (M < 0 || F <= 0 || ldx < kFfnK || ldo < kFfnK) return RDETR_ERR_INVALID_ARG;
-    if ((F % kFfnHC) || F > 4096 || (ldx & 7) || (ldo & 7)) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0 || F <= 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = rows_status({{x, ldx, kFfnK, 2}, {out, ldo, kFfnK, 2}})) return s;
+    if ((F % kFfnHC) || F > 4096) return RDETR_ERR_UNSUPPORTED;
     if (M == 0) return RDETR_OK;
     if (!x || !packed || !b1 || !b2 || !out) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(out)) & 15)
-        return RDETR_ERR_UNSUPPORTED;
+    if (!aligned_to(packed, 16)) return RDETR_ERR_UNSUPPORTED;
     const int lds = 2 * kFfnBufBytes + (F + 3 * kFfnK) * 4;
-    static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_kernel<false>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kFfnBufBytes + (4096 + 3 * kFfnK) * 4);
-    static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_kernel<true>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kFfnBufBytes + (4096 + 3 * kFfnK) * 4);
-    if (attr0 != hipSuccess || attr1 != hipSuccess) return RDETR_ERR_LAUNCH;
+    if (ensure_dynamic_lds<ffn_k256_kernel<false>>(kFfnMaxLdsBytes) || ensure_dynamic_lds<ffn_k256_kernel<true>>(kFfnMaxLdsBytes))
+        return RDETR_ERR_LAUNCH;
     const long long ntiles = (M + kFfnWaves * kFfnRows - 1) / (kFfnWaves * kFfnRows);
-    const long long gx = ntiles < 256 ? ntiles : 256;
+    const long long gx = ntiles < kCus ? ntiles : kCus;
 #ifdef RDETR_DEV
     const int dbg = g_ffn_dbg;
 #else
@@ -318,9 +314,8 @@ extern "C" int rdetr_ffn_ln_k256_bf16(const uint16_t *x, long long ldx, const ui
                                       uint16_t *out2, long long ldo2, void *stream)
 {
     if (!gamma || !beta || (pos != nullptr) != (out2 != nullptr)) return RDETR_ERR_INVALID_ARG;
-    if (pos && (ldp < kFfnK || ldo2 < kFfnK)) return RDETR_ERR_INVALID_ARG;
-    if (pos && ((ldp & 7) || (ldo2 & 7) || ((reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(out2)) & 15)))
-        return RDETR_ERR_UNSUPPORTED;
+    if (pos)
+        if (const int s = rows_status({{pos, ldp, kFfnK, 2}, {out2, ldo2, kFfnK, 2}})) return s;
     return ffn_launch(x, ldx, packed, b1, b2, M, F, out, ldo, gamma, beta, eps, pos, ldp, out2, ldo2, stream);
 }
 
@@ -331,29 +326,24 @@ static int ffn_train_launch(bool bwd, bool f32, const void *x, long long ldx, co
                             long long ldd, uint16_t *xlp, long long ldxl, void *stream)
 {
     const bool xf32 = f32 && !bwd, of32 = f32 && bwd;
-    if (M < 0 || F <= 0 || ldx < kFfnK || ldo < kFfnK || ldh < F || (bwd && ldd < F) || (xf32 && ldxl < kFfnK)) return RDETR_ERR_INVALID_ARG;
-    if ((F % kFfnHC) || F > 4096 || (ldx & (xf32 ? 3 : 7)) || (ldo & (of32 ? 3 : 7)) || (ldh & 7) || (bwd && (ldd & 7)) || (xf32 && (ldxl & 7)))
-        return RDETR_ERR_UNSUPPORTED;
+    if (M < 0 || F <= 0) return RDETR_ERR_INVALID_ARG;
+    // dH and xlp are absent (NULL, stride 0) outside the backward / the fp32-x forward: rows of no elements there
+    if (const int s = rows_status({{x, ldx, kFfnK, xf32 ? 4 : 2}, {out, ldo, kFfnK, of32 ? 4 : 2}, {hid, ldh, F, 2}, {dhid, ldd, bwd ? F : 0, 2},
+                                   {xlp, ldxl, xf32 ? kFfnK : 0, 2}}))
+        return s;
+    if ((F % kFfnHC) || F > 4096) return RDETR_ERR_UNSUPPORTED;
     if (M == 0) return RDETR_OK;
     if (!x || !packed || !out || !hid || (bwd ? !dhid : (!b1 || !b2)) || (xf32 && !xlp)) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(out) |
-         reinterpret_cast<uintptr_t>(hid) | reinterpret_cast<uintptr_t>(dhid) | reinterpret_cast<uintptr_t>(xlp)) & 15)
-        return RDETR_ERR_UNSUPPORTED;
+    if (!aligned_to(packed, 16)) return RDETR_ERR_UNSUPPORTED;
     // H / dH are addressed with 32-bit byte offsets whose top bit marks "no such row" (kFfnNoRow)
     if (M * ldh * 2 > 0x7fffffffLL || (bwd && M * ldd * 2 > 0x7fffffffLL)) return RDETR_ERR_UNSUPPORTED;
     const int lds = 2 * kFfnBufBytes + (F + 3 * kFfnK) * 4;
-    constexpr int max_lds = 2 * kFfnBufBytes + (4096 + 3 * kFfnK) * 4;
-    static const hipError_t attr0 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_kernel<kFfnTrain>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    static const hipError_t attr1 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_kernel<kFfnBwd>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    static const hipError_t attr2 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_f32_kernel<kFfnTrain>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    static const hipError_t attr3 = hipFuncSetAttribute(reinterpret_cast<const void *>(ffn_k256_train_f32_kernel<kFfnBwd>),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    if (attr0 != hipSuccess || attr1 != hipSuccess || attr2 != hipSuccess || attr3 != hipSuccess) return RDETR_ERR_LAUNCH;
+    if (ensure_dynamic_lds<ffn_k256_train_kernel<kFfnTrain>>(kFfnMaxLdsBytes) || ensure_dynamic_lds<ffn_k256_train_kernel<kFfnBwd>>(kFfnMaxLdsBytes) ||
+        ensure_dynamic_lds<ffn_k256_train_f32_kernel<kFfnTrain>>(kFfnMaxLdsBytes) ||
+        ensure_dynamic_lds<ffn_k256_train_f32_kernel<kFfnBwd>>(kFfnMaxLdsBytes))
+        return RDETR_ERR_LAUNCH;
     const long long ntiles = (M + kFfnWaves * kFfnRows - 1) / (kFfnWaves * kFfnRows);
-    const long long gx = ntiles < 256 ? ntiles : 256;
+    const long long gx = ntiles < kCus ? ntiles : kCus;
     const dim3 grid((unsigned)gx), block(kFfnThreads);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint16_t *xb = static_cast<const uint16_t *>(x);

@@ -17,7 +17,7 @@
 //                      models/bricks/relation_transformer.py:87-89) written into its row range of the level-packed
 //                      [B, S, C] token tensor (models/bricks/base_transformer.py:17-23): LDS-tiled transpose, 64 x 64
 //   nchw_levels_to_tokens   the same for up to 8 levels of a pyramid in one launch
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -443,7 +443,7 @@ extern "C" int rdetr_box_refine_f32(const void *delta, int delta_is_bf16, const 
     if (n == 0) return RDETR_OK;
     if (!delta || !ref || !out) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (n + 255) / 256;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (delta_is_bf16)
         hipLaunchKernelGGL((box_refine_kernel<uint16_t>), dim3((unsigned)nblk), dim3(256), 0, st, static_cast<const uint16_t *>(delta),
@@ -466,7 +466,7 @@ extern "C" int rdetr_sine_pos_embed(const float *pos, long long rows, int n, int
     // get_dim_t: temperature ** (2 * (arange(F) // 2) / F), fp32 (position_encoding.py:101-105)
     for (int k = 0; k < F / 2; ++k) dt.v[k] = powf(temperature, 2.0f * (float)k / (float)F);
     const long long total = rows * n * (F / 2), nblk = (total + 255) / 256;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (out_is_bf16)
         hipLaunchKernelGGL((sine_pos_embed_kernel<uint16_t>), dim3((unsigned)nblk), dim3(256), 0, st, pos, rows, n, F, scale, dt,
@@ -483,9 +483,9 @@ extern "C" int rdetr_detections_from_topk(const float *score, const long long *i
     if (B < 0 || N <= 0 || C <= 0 || K < 0) return RDETR_ERR_INVALID_ARG;
     if (B == 0 || K == 0) return RDETR_OK;
     if (!score || !index || !boxes || !image_sizes || !out) return RDETR_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(boxes) % 16) return RDETR_ERR_UNSUPPORTED;
+    if (!aligned_to(boxes, 16)) return RDETR_ERR_UNSUPPORTED;
     const long long total = (long long)B * K, nblk = (total + 255) / 256;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(detections_kernel, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), score, index, boxes,
                        image_sizes, N, C, K, total, out);
     return launch_status();
@@ -498,7 +498,7 @@ extern "C" int rdetr_scaled_pos(const void *a, const void *scale, const void *qu
     if (n == 0) return RDETR_OK;
     if (!a || !scale || !query || !pos || !qp) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (n + 255) / 256;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (is_bf16)
         hipLaunchKernelGGL((scaled_pos_kernel<uint16_t>), dim3((unsigned)nblk), dim3(256), 0, st, static_cast<const uint16_t *>(a),
@@ -521,7 +521,7 @@ extern "C" int rdetr_decoder_reference(const float *reference, const float *vali
     GlueDimT dt;
     for (int k = 0; k < F / 2; ++k) dt.v[k] = powf(temperature, 2.0f * (float)k / (float)F);
     const long long total = (long long)B * N * 4 * (F / 2), nblk = (total + 255) / 256;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (emb_is_bf16)
         hipLaunchKernelGGL((decoder_reference_kernel<uint16_t>), dim3((unsigned)nblk), dim3(256), 0, st, reference, valid_ratios, N, L, F,
@@ -538,9 +538,9 @@ extern "C" int rdetr_zero_masked_rows(void *x, const unsigned char *mask, long l
     if (rows < 0 || row_bytes <= 0 || ld_bytes < row_bytes) return RDETR_ERR_INVALID_ARG;
     if ((row_bytes & 15) || (ld_bytes & 15)) return RDETR_ERR_UNSUPPORTED;
     if (rows == 0) return RDETR_OK;
-    if (!x || !mask || (reinterpret_cast<uintptr_t>(x) & 15)) return RDETR_ERR_INVALID_ARG;
+    if (!x || !mask || !aligned_to(x, 16)) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (rows + 255) / 256;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(zero_masked_rows_kernel, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<unsigned char *>(x), mask, rows, row_bytes, ld_bytes);
     return launch_status();
@@ -551,9 +551,9 @@ extern "C" int rdetr_grad_value_from_head_major_bf16(const float *grad_hm, const
 {
     if (B < 0 || S < 0 || H != 8 || D != 32 || ld < H * D || ld % 8) return RDETR_ERR_INVALID_ARG;
     if (B == 0 || S == 0) return RDETR_OK;
-    if (!grad_hm || !dst || (reinterpret_cast<uintptr_t>(grad_hm) & 15) || (reinterpret_cast<uintptr_t>(dst) & 15)) return RDETR_ERR_INVALID_ARG;
+    if (!grad_hm || !dst || !aligned_to(grad_hm, 16) || !aligned_to(dst, 16)) return RDETR_ERR_INVALID_ARG;
     const long long rows = (long long)B * S, nblk = (rows + 31) / 32;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(grad_value_from_head_major_kernel, dim3((unsigned)nblk), dim3(256), 0, static_cast<hipStream_t>(stream), grad_hm,
                        key_padding_mask, rows, S, ld, dst);
     return launch_status();
@@ -565,7 +565,7 @@ extern "C" int rdetr_row_max(const void *x, int is_bf16, long long rows, int C, 
     if (rows == 0) return RDETR_OK;
     if (!x || !out) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (rows + 15) / 16;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (is_bf16)
         hipLaunchKernelGGL((row_max_kernel<uint16_t>), dim3((unsigned)nblk), dim3(256), 0, st, static_cast<const uint16_t *>(x), rows, C,
@@ -585,9 +585,7 @@ extern "C" int rdetr_nchw_to_tokens(const void *src, const void *add_vec, int is
     if (B > 65535 || (C + 63) / 64 > 65535) return RDETR_ERR_UNSUPPORTED;
     const dim3 grid((unsigned)((P + 63) / 64), (unsigned)((C + 63) / 64), (unsigned)B);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (is_bf16 && P % 8 == 0 && C % 8 == 0 && ld_out % 8 == 0 && out_image_stride % 8 == 0 && al16(src) && al16(out) &&
-        (!add_vec || al16(add_vec)))
+    if (is_bf16 && P % 8 == 0 && C % 8 == 0 && rows_ok(out, ld_out, C, 2) && out_image_stride % 8 == 0 && all_aligned(16, src, add_vec))
         hipLaunchKernelGGL(nchw_to_tokens_bf16_vec_kernel, grid, dim3(256), 0, st, static_cast<const uint16_t *>(src),
                            static_cast<const uint16_t *>(add_vec), C, P, out_image_stride, ld_out, static_cast<uint16_t *>(out));
     else if (is_bf16)
@@ -605,10 +603,9 @@ extern "C" int rdetr_nchw_levels_to_tokens(const void *const *level_src, const v
 {
     if (L <= 0 || B < 0 || C <= 0 || !level_src || !level_pixels || ld_out < C || out_image_stride < 0) return RDETR_ERR_INVALID_ARG;
     if (L > 8 || B > 65535 || (C + 63) / 64 > 65535 || (is_bf16 != 0 && is_bf16 != 1)) return RDETR_ERR_UNSUPPORTED;
-    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
     TokLevels lv = {};
     long long rows = 0, tiles = 0;
-    bool wide = C % 8 == 0 && ld_out % 8 == 0 && out_image_stride % 8 == 0 && al16(out);
+    bool wide = C % 8 == 0 && rows_ok(out, ld_out, C, 2) && out_image_stride % 8 == 0;
     for (int l = 0; l < L; ++l) {
         if (level_pixels[l] < 0 || (level_pixels[l] > 0 && !level_src[l])) return RDETR_ERR_INVALID_ARG;
         lv.src[l] = level_src[l];
@@ -619,7 +616,7 @@ extern "C" int rdetr_nchw_levels_to_tokens(const void *const *level_src, const v
         rows += level_pixels[l];
         tiles += (level_pixels[l] + 63) / 64;
         if (rows >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
-        wide = wide && al16(lv.vec[l]);
+        wide = wide && aligned_to(lv.vec[l], 16);
     }
     lv.tile0[L] = (int)tiles;
     if (B == 0 || tiles == 0) return RDETR_OK;

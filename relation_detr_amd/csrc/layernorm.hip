@@ -12,7 +12,8 @@
 //
 // Training (C = 256 only, further down): the same forward body that also stores {mean, rstd} per row, and the backward from them --
 // dx for both operands in one pass over dy, x and r, dgamma / dbeta through per-workgroup partials summed in a fixed order.
-#include "common.h"
+#include "launch.h"
+#include "rows256.h"
 
 namespace rdetr {
 
@@ -62,14 +63,6 @@ template <> __device__ __forceinline__ float ln_round<uint16_t>(float v) { retur
 constexpr int kLnWaves = 4;
 constexpr int kLnRowsPerWave = 4;          // C = 256 kernel: half a wave per row (32 lanes x 8 channels), 2 rows per half
 
-// sum over the 32 lanes of a half wave
-__device__ __forceinline__ float ln_half_sum(float v)
-{
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <typename T> struct LnIO8;
 template <> struct LnIO8<float> {
     static __device__ __forceinline__ void load(const float *p, float (&v)[8])
@@ -86,14 +79,11 @@ template <> struct LnIO8<float> {
 template <> struct LnIO8<uint16_t> {
     static __device__ __forceinline__ void load(const uint16_t *p, float (&v)[8])
     {
-        const u32x4 r = *reinterpret_cast<const u32x4 *>(p);
-        v[0] = __builtin_bit_cast(float, r.x << 16); v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-        v[2] = __builtin_bit_cast(float, r.y << 16); v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
-        v[4] = __builtin_bit_cast(float, r.z << 16); v[5] = __builtin_bit_cast(float, r.z & 0xffff0000u);
-        v[6] = __builtin_bit_cast(float, r.w << 16); v[7] = __builtin_bit_cast(float, r.w & 0xffff0000u);
+        row256_widen8(*reinterpret_cast<const u32x4 *>(p), v);
     }
     static __device__ __forceinline__ void store(uint16_t *p, const float (&v)[8])
     {
+        // two converts and an OR per pair, not pack_bf16x2's one packed convert (same bits): that spelling is the kernels' measured code
         u32x4 o;
         o.x = f32_to_bf16_bits(v[0]) | (f32_to_bf16_bits(v[1]) << 16);
         o.y = f32_to_bf16_bits(v[2]) | (f32_to_bf16_bits(v[3]) << 16);
@@ -147,18 +137,19 @@ __device__ __forceinline__ void add_layernorm256_body(const T *__restrict__ x, c
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const long long row = row0 + 2 * i;
-        // same summation tree per lane as the 4-channel version would not be required: statistics are fp32 either way
+        // same summation tree per lane as the 4-channel version would not be required: statistics are fp32 either way.
+        // rt_normalise (csrc/rowtail.hip) repeats this block operation for operation: change the two together (rows256.h)
         float s = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) s += v[i][k];
-        const float mean = ln_half_sum(s) * (1.0f / 256.0f);
+        const float mean = row256_half_sum(s) * (1.0f / 256.0f);
         float sq = 0.f;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             v[i][k] -= mean;
             sq += v[i][k] * v[i][k];
         }
-        const float rstd = 1.0f / sqrtf(ln_half_sum(sq) * (1.0f / 256.0f) + eps);
+        const float rstd = 1.0f / sqrtf(row256_half_sum(sq) * (1.0f / 256.0f) + eps);
         float y[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) y[k] = v[i][k] * rstd * g[k] + b[k];
@@ -253,12 +244,11 @@ static int add_layernorm(const T *x, const T *r, const T *gamma, const T *beta, 
     if (rows == 0) return RDETR_OK;
     if (!x || !gamma || !beta || !out) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (rows + kLnWaves - 1) / kLnWaves;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     const long long nblk256 = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave);
-    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const long long a16 = 16 / (long long)sizeof(T);
-    if (C == 256 && al16(x) && al16(out) && al16(gamma) && al16(beta) && (!r || al16(r)) && ldx % a16 == 0 && ldo % a16 == 0 &&
-        (!r || ldr % a16 == 0) && (!out2 || (al16(pos) && al16(out2) && ldp % a16 == 0 && ldo2 % a16 == 0)))
+    constexpr int eb = (int)sizeof(T);
+    if (C == 256 && rows_ok(x, ldx, C, eb) && rows_ok(out, ldo, C, eb) && all_aligned(16, gamma, beta) && (!r || rows_ok(r, ldr, C, eb)) &&
+        (!out2 || (rows_ok(pos, ldp, C, eb) && rows_ok(out2, ldo2, C, eb))))
         hipLaunchKernelGGL((add_layernorm256_kernel<T>), dim3((unsigned)nblk256), dim3(kLnWaves * kWave), 0, stream, x, r, gamma,
                            beta, rows, ldx, ldr, ldo, eps, out, pos, ldp, out2, ldo2);
     else
@@ -278,11 +268,10 @@ static int add_layernorm_train(const T *x, const T *r, const T *gamma, const T *
     if (rows == 0) return RDETR_OK;
     if (!x || !gamma || !beta || !out || !stats) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave);
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
-    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const long long a16 = 16 / (long long)sizeof(T);
-    if (!(al16(x) && al16(out) && al16(gamma) && al16(beta) && (!r || al16(r)) && ldx % a16 == 0 && ldo % a16 == 0 &&
-          (!r || ldr % a16 == 0) && reinterpret_cast<uintptr_t>(stats) % 8 == 0))
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
+    constexpr int eb = (int)sizeof(T);
+    if (!(rows_ok(x, ldx, C, eb) && rows_ok(out, ldo, C, eb) && all_aligned(16, gamma, beta) && (!r || rows_ok(r, ldr, C, eb)) &&
+          aligned_to(stats, 8)))
         return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL((add_layernorm256_train_kernel<T>), dim3((unsigned)nblk), dim3(kLnWaves * kWave), 0, stream, x, r, gamma, beta,
                        rows, ldx, ldr, ldo, eps, out, stats);
@@ -298,7 +287,7 @@ static int add_layernorm_train(const T *x, const T *r, const T *gamma, const T *
 // dbeta in registers across trips, the workgroup adds its 8 half-waves through LDS in index order and writes ONE [2, 256] partial;
 // ln_param_grad_kernel then adds the partials in index order.  No atomics: the same bits every run.
 // Bound: HBM (4 x rows x C x sizeof(T) bytes; the partials are at most 2 MiB).
-constexpr int kLnBwdMaxBlocks = 1024;      // 4 workgroups (16 waves) on each of the MI355X's 256 CUs: 24 KB of bf16 loads per CU and trip
+constexpr int kLnBwdMaxBlocks = 4 * kCus;  // 4 workgroups (16 waves) on each CU: 24 KB of bf16 loads per CU and trip
 
 // T is the type of dy, gamma and dx; TX / TR those of x and the residual (all T in the same-dtype kernels).  kTwin (the
 // mixed-precision backward, T = float): dx may be null, and dxb, where it is not null, receives the same values rounded to bf16 (RNE)
@@ -357,7 +346,7 @@ __device__ __forceinline__ void add_layernorm256_bwd_body(const T *__restrict__ 
                 s1 += gg[k];
                 s2 += gg[k] * v[i][k];
             }
-            const float m1 = ln_half_sum(s1) * (1.0f / 256.0f), m2 = ln_half_sum(s2) * (1.0f / 256.0f);
+            const float m1 = row256_half_sum(s1) * (1.0f / 256.0f), m2 = row256_half_sum(s2) * (1.0f / 256.0f);
             float o[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) o[k] = rstd[i] * (gg[k] - m1 - v[i][k] * m2);
@@ -466,10 +455,9 @@ static int add_layernorm_backward(const T *dy, long long lddy, const T *x, long 
     if (!dy || !x || !gamma || !stats || !dx) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave), grid = ln_backward_blocks(rows);
     if (dgamma && (!workspace || workspace_bytes < grid * 512 * (long long)sizeof(float))) return RDETR_ERR_INVALID_ARG;
-    auto al16 = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const long long a16 = 16 / (long long)sizeof(T);
-    if (!(al16(dy) && al16(x) && al16(dx) && al16(gamma) && (!r || al16(r)) && lddy % a16 == 0 && ldx % a16 == 0 &&
-          (!r || ldr % a16 == 0) && reinterpret_cast<uintptr_t>(stats) % 8 == 0 && (!dgamma || al16(workspace))))
+    constexpr int eb = (int)sizeof(T);
+    if (!(rows_ok(dy, lddy, C, eb) && rows_ok(x, ldx, C, eb) && all_aligned(16, dx, gamma) && (!r || rows_ok(r, ldr, C, eb)) &&
+          aligned_to(stats, 8) && (!dgamma || aligned_to(workspace, 16))))
         return RDETR_ERR_UNSUPPORTED;
     if (dgamma) {
         float *partial = static_cast<float *>(workspace);
@@ -488,10 +476,6 @@ static int add_layernorm_backward(const T *dy, long long lddy, const T *x, long 
 // The routes above under bf16 autocast over fp32 parameters: x and the residual are each fp32 or bf16 (the residual stream is
 // fp32, a sublayer's linear output bf16), gamma / beta / out / dy fp32.  One launcher per direction, instantiated for the four
 // operand-type pairs; the argument checks are those of the same-dtype routes with each operand on its own 16-byte grid.
-static bool ln_rows_ok(const void *p, bool is_bf16, long long ld)
-{
-    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % (is_bf16 ? 8 : 4) == 0;
-}
 
 template <typename TX, typename TR>
 static void ln_train_mixed_launch(const void *x, const void *r, const float *gamma, const float *beta, long long rows, long long ldx,
@@ -510,9 +494,9 @@ static int add_layernorm_train_mixed(const void *x, bool xb, long long ldx, cons
     if (rows == 0) return RDETR_OK;
     if (!x || !gamma || !beta || !out || !stats) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave);
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
-    if (!(ln_rows_ok(x, xb, ldx) && ln_rows_ok(out, false, ldo) && (!r || ln_rows_ok(r, rb, ldr)) && aligned_to(gamma, 16) &&
-          aligned_to(beta, 16) && aligned_to(stats, 8)))
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
+    if (!(rows_ok(x, ldx, C, xb ? 2 : 4) && rows_ok(out, ldo, C, 4) && (!r || rows_ok(r, ldr, C, rb ? 2 : 4)) && all_aligned(16, gamma, beta) &&
+          aligned_to(stats, 8)))
         return RDETR_ERR_UNSUPPORTED;
     auto *launch = xb ? (rb ? ln_train_mixed_launch<uint16_t, uint16_t> : ln_train_mixed_launch<uint16_t, float>)
                       : (rb ? ln_train_mixed_launch<float, uint16_t> : ln_train_mixed_launch<float, float>);
@@ -548,8 +532,8 @@ static int add_layernorm_backward_mixed(const float *dy, long long lddy, const v
     if ((any_bf16 && !dxb) || (any_f32 && !dx)) return RDETR_ERR_INVALID_ARG;
     const long long nblk = (rows + kLnWaves * kLnRowsPerWave - 1) / (kLnWaves * kLnRowsPerWave), grid = ln_backward_blocks(rows);
     if (dgamma && (!workspace || workspace_bytes < grid * 512 * (long long)sizeof(float))) return RDETR_ERR_INVALID_ARG;
-    if (!(ln_rows_ok(dy, false, lddy) && ln_rows_ok(x, xb, ldx) && (!r || ln_rows_ok(r, rb, ldr)) && aligned_to(gamma, 16) &&
-          (!dx || aligned_to(dx, 16)) && (!dxb || aligned_to(dxb, 16)) && aligned_to(stats, 8) && (!dgamma || aligned_to(workspace, 16))))
+    if (!(rows_ok(dy, lddy, C, 4) && rows_ok(x, ldx, C, xb ? 2 : 4) && (!r || rows_ok(r, ldr, C, rb ? 2 : 4)) && all_aligned(16, gamma, dx, dxb) &&
+          aligned_to(stats, 8) && (!dgamma || aligned_to(workspace, 16))))
         return RDETR_ERR_UNSUPPORTED;
     float *partial = dgamma ? static_cast<float *>(workspace) : nullptr;
     auto *launch = xb ? (rb ? ln_bwd_mixed_launch<uint16_t, uint16_t> : ln_bwd_mixed_launch<uint16_t, float>)

@@ -17,7 +17,7 @@
 // Bound: HBM (X in + out; the weights come from L2 once per workgroup).
 #include <cstdlib>
 
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -148,16 +148,13 @@ template <int NT, bool RELU>
 static int linear_launch(const uint16_t *x, long long ldx, const uint16_t *w, const uint16_t *bias, long long M, int N,
                          uint16_t *out, long long ldo, int chunks, hipStream_t st, const unsigned char *row_mask = nullptr, int hm_S = 0)
 {
-    auto kern = linear_k256_kernel<NT, RELU>;
     constexpr int lds = NT * 8 * 64 * 16 + NT * 16 * 4;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
+    if (const int s = ensure_dynamic_lds<linear_k256_kernel<NT, RELU>>(lds)) return s;
     const long long steps = (M + kLinRows - 1) / kLinRows;
     long long gx = (steps + kLinThreads / 64 - 1) / (kLinThreads / 64);
-    const long long cap = 256 / chunks > 0 ? 256 / chunks : 1;                // about one resident workgroup per CU
+    const long long cap = kCus / chunks > 0 ? kCus / chunks : 1;              // about one resident workgroup per CU
     if (gx > cap) gx = cap;
-    hipLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)chunks), dim3(kLinThreads), (size_t)lds, st, x, ldx, w, bias, M, N, out,
+    hipLaunchKernelGGL((linear_k256_kernel<NT, RELU>), dim3((unsigned)gx, (unsigned)chunks), dim3(kLinThreads), (size_t)lds, st, x, ldx, w, bias, M, N, out,
                        ldo, 0, row_mask, hm_S);
     return launch_status();
 }
@@ -305,11 +302,12 @@ using namespace rdetr;
 extern "C" int rdetr_linear_k256_bf16(const uint16_t *x, long long ldx, const uint16_t *w, const uint16_t *bias, long long M,
                                       int N, int relu, uint16_t *out, long long ldo, void *stream)
 {
-    if (M < 0 || N <= 0 || ldx < kLinK || ldo < N) return RDETR_ERR_INVALID_ARG;
-    if ((N & 31) || (ldx & 7) || (ldo & 7)) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0 || N <= 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = rows_status({{x, ldx, kLinK, 2}, {out, ldo, N, 2}})) return s;
+    if (N & 31) return RDETR_ERR_UNSUPPORTED;
     if (M == 0) return RDETR_OK;
     if (!x || !w || !out) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(out)) & 15) return RDETR_ERR_UNSUPPORTED;
+    if (!aligned_to(w, 16)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // slices of 256 columns (16 tiles), or of 192 when that divides N and 256 does not (N = 384)
     if (N % 256 == 0 || N < 192 || (N % 192 != 0)) {
@@ -328,12 +326,12 @@ extern "C" int rdetr_linear_k256_bf16(const uint16_t *x, long long ldx, const ui
 extern "C" int rdetr_linear_k256_hm_bf16(const uint16_t *x, long long ldx, const uint16_t *w, const uint16_t *bias,
                                          const uint8_t *row_mask, int B, int S, uint16_t *out_hm, void *stream)
 {
-    if (B < 0 || S < 0 || ldx < kLinK) return RDETR_ERR_INVALID_ARG;
-    if (ldx & 7) return RDETR_ERR_UNSUPPORTED;
+    if (B < 0 || S < 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = rows_status({{x, ldx, kLinK, 2}})) return s;
     if (B == 0 || S == 0) return RDETR_OK;
     if ((long long)B * S >= (1ll << 31)) return RDETR_ERR_UNSUPPORTED;
     if (!x || !w || !out_hm) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(out_hm)) & 15) return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, w, out_hm)) return RDETR_ERR_UNSUPPORTED;
     return linear_launch<16, false>(x, ldx, w, bias, (long long)B * S, 256, out_hm, 256, 1, static_cast<hipStream_t>(stream), row_mask, S);
 }
 
@@ -341,7 +339,7 @@ extern "C" int rdetr_linear_k256_hm_bf16(const uint16_t *x, long long ldx, const
 extern "C" int rdetr_linear_pack_k256_bf16(const uint16_t *w, uint16_t *packed, void *stream)
 {
     if (!w || !packed) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(packed)) & 15) return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, w, packed)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(linear_pack_kernel, dim3(32), dim3(256), 0, static_cast<hipStream_t>(stream), w, reinterpret_cast<u32x4 *>(packed));
     return launch_status();
 }
@@ -352,20 +350,16 @@ extern "C" int rdetr_linear_ln_k256_bf16(const uint16_t *x, long long ldx, const
                                          const uint16_t *residual, long long ldr, const uint16_t *gamma, const uint16_t *beta,
                                          float eps, long long M, uint16_t *out, long long ldo, void *stream)
 {
-    if (M < 0 || ldx < kLinK || ldr < kLinK || ldo < kLinK) return RDETR_ERR_INVALID_ARG;
-    if ((ldx & 7) || (ldr & 7) || (ldo & 7)) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = rows_status({{x, ldx, kLinK, 2}, {residual, ldr, kLinK, 2}, {out, ldo, kLinK, 2}})) return s;
     if (M == 0) return RDETR_OK;
     if (!x || !packed || !residual || !gamma || !beta || !out) return RDETR_ERR_INVALID_ARG;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(packed) | reinterpret_cast<uintptr_t>(residual) |
-         reinterpret_cast<uintptr_t>(out)) & 15)
-        return RDETR_ERR_UNSUPPORTED;
+    if (!aligned_to(packed, 16)) return RDETR_ERR_UNSUPPORTED;
     constexpr int lds = 16 * 8 * 64 * 16 + 3 * 256 * 4;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(linear_ln_k256_kernel),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
+    if (const int s = ensure_dynamic_lds<linear_ln_k256_kernel>(lds)) return s;
     const long long steps = (M + kLinRows - 1) / kLinRows;
     long long gx = (steps + kLnlWaves - 1) / kLnlWaves;
-    if (gx > 256) gx = 256;
+    if (gx > kCus) gx = kCus;
     hipLaunchKernelGGL(linear_ln_k256_kernel, dim3((unsigned)gx), dim3(kLnlThreads), (size_t)lds, static_cast<hipStream_t>(stream), x,
                        ldx, packed, bias, residual, ldr, gamma, beta, eps, M, out, ldo);
     return launch_status();

@@ -44,7 +44,7 @@
 //              isolated -- faster while one launch has the chip to itself, slower than 32 rows once the workgroups outnumber
 //              the CUs, which is the stack's situation (both image groups' launches coincide) -- and the step does not tell them
 //              apart (1036-1063 vs 1055-1063 images/s, ab_candidates.txt); 32 rows moves half the weight bytes from L2.
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -269,15 +269,13 @@ extern "C" int rdetr_box_head_k256_bf16(const uint16_t *xa, long long lda, const
                                         const float *reference, int reference_is_logit, float eps, long long M, float *out_a, float *out_b,
                                         void *stream)
 {
-    if (M < 0 || lda < 256 || (xb && ldb < 256)) return RDETR_ERR_INVALID_ARG;
-    if ((lda & 7) || (xb && (ldb & 7))) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = xb ? rows_status({{xa, lda, 256, 2}, {xb, ldb, 256, 2}}) : rows_status({{xa, lda, 256, 2}})) return s;
     if (M == 0) return RDETR_OK;
     if (!xa || !pw1 || !b1 || !pw2 || !b2 || !w3 || !b3 || !reference || !out_a || (xb && !out_b)) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (!al(xa) || (xb && !al(xb)) || !al(pw1) || !al(pw2) || !al(w3) || !al(reference) || !al(out_a) || (xb && !al(out_b)))
-        return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, pw1, pw2, w3, reference, out_a) || (xb && !aligned_to(out_b, 16))) return RDETR_ERR_UNSUPPORTED;
     const long long total = xb ? 2 * M : M, nblk = (total + kMlpRows - 1) / kMlpRows;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(box_head_k256_kernel, dim3((unsigned)nblk), dim3(kMlpThreads), 0, static_cast<hipStream_t>(stream), xa,
                        lda, xb, ldb, pw1, b1, pw2, b2, w3, b3, reference, reference_is_logit, eps, M, out_a, out_b);
     return launch_status();
@@ -292,17 +290,16 @@ extern "C" int rdetr_box_head_cls_k256_bf16(const uint16_t *xa, long long lda, c
                                             const float *reference, int reference_is_logit, float eps, const uint16_t *pwc, const uint16_t *bc,
                                             int C, long long M, float *out_a, float *out_b, uint16_t *out_cls, long long ldc, void *stream)
 {
-    if (M < 0 || lda < 256 || (xb && ldb < 256) || C < 1 || ldc < C) return RDETR_ERR_INVALID_ARG;
-    if ((lda & 7) || (xb && (ldb & 7)) || C > 256) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0 || C < 1 || ldc < C) return RDETR_ERR_INVALID_ARG;
+    if (const int s = xb ? rows_status({{xa, lda, 256, 2}, {xb, ldb, 256, 2}}) : rows_status({{xa, lda, 256, 2}})) return s;
+    if (C > 256) return RDETR_ERR_UNSUPPORTED;
     if (M == 0) return RDETR_OK;
     if (!xa || !pw1 || !b1 || !pw2 || !b2 || !w3 || !b3 || !reference || !out_a || (xb && !out_b) || !pwc || !bc || !out_cls)
         return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (!al(xa) || (xb && !al(xb)) || !al(pw1) || !al(pw2) || !al(w3) || !al(reference) || !al(out_a) || (xb && !al(out_b)) || !al(pwc)
-        || reinterpret_cast<uintptr_t>(out_cls) % 2 || reinterpret_cast<uintptr_t>(bc) % 2)
+    if (!all_aligned(16, pw1, pw2, w3, reference, out_a, pwc) || (xb && !aligned_to(out_b, 16)) || !all_aligned(2, out_cls, bc))
         return RDETR_ERR_UNSUPPORTED;
     const long long total = xb ? 2 * M : M, nblk = (total + kMlpRows - 1) / kMlpRows;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     const MlpCls cl = {pwc, bc, out_cls, ldc, C};
     hipLaunchKernelGGL(box_head_cls_k256_kernel, dim3((unsigned)nblk), dim3(kMlpThreads), 0, static_cast<hipStream_t>(stream), xa,
                        lda, xb, ldb, pw1, b1, pw2, b2, w3, b3, reference, reference_is_logit, eps, M, out_a, out_b, cl);

@@ -29,7 +29,7 @@
 // to run.  Every other gradient is a shuffle-tree sum inside a wave: the same bits in both modes.
 #include <hipcub/hipcub.hpp>
 
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 

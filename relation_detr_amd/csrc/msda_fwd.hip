@@ -31,7 +31,7 @@
 // Any other (H, D, P) runs msda_fwd_generic_kernel (one thread per output, 64-bit indexing).
 #include <cstdlib>
 
-#include "common.h"
+#include "launch.h"
 #include "msda_qrun.h"
 
 namespace rdetr {
@@ -487,13 +487,13 @@ static void launch_qrun(dim3 grid, dim3 block, hipStream_t stream, const T *valu
     const int hg = MsdaOrder::head_group_log2 >= 0 ? MsdaOrder::head_group_log2 : 1;
     const int order = interleave | (hg << 1);
     // the 4-level kernel reads a lane's share of the query-side inputs as 16-byte vectors
-    const bool vec_ok = reinterpret_cast<uintptr_t>(src_a) % 16 == 0 && reinterpret_cast<uintptr_t>(src_b) % 16 == 0 &&
-                        (!FUSED || (reinterpret_cast<uintptr_t>(ref) % 16 == 0 && (ld_a * (int)sizeof(T)) % 16 == 0 &&
+    const bool vec_ok = aligned_to(src_a, 16) && aligned_to(src_b, 16) &&
+                        (!FUSED || (aligned_to(ref, 16) && (ld_a * (int)sizeof(T)) % 16 == 0 &&
                                     (ld_b * (int)sizeof(T)) % 16 == 0));
     // the 5-level bf16 kernel reads runs of 5 / 10 values at their natural alignment and two reference points at once
     const bool vec5_ok = sizeof(T) == 4 ||
-                         (reinterpret_cast<uintptr_t>(src_a) % 8 == 0 && reinterpret_cast<uintptr_t>(src_b) % 4 == 0 &&
-                          (!FUSED || (reinterpret_cast<uintptr_t>(ref) % 16 == 0 && (ld_a * (int)sizeof(T)) % 4 == 0)));
+                         (aligned_to(src_a, 8) && aligned_to(src_b, 4) &&
+                          (!FUSED || (aligned_to(ref, 16) && (ld_a * (int)sizeof(T)) % 4 == 0)));
     if (L == 4 && vec_ok)
         hipLaunchKernelGGL((msda_fwd_qrun_kernel<T, 4, FUSED>), grid, block, 0, stream, value, shapes, level_start, src_a,
                            src_b, ref, ref_dim, S, L, Nq, tiles, nblk, out, pad_mask, ld_a, ld_b, head_major, value_pix_bytes, order);
@@ -528,8 +528,7 @@ static int msda_forward(const T *value, int layout, const int64_t *shapes, const
     // value_ld (elements, [B,S,H,D] only): row stride of a value tensor whose pixels are column slices of a wider buffer; 0 = dense
     if (value_ld && (hm || value_ld < (long long)H * D || (value_ld * (long long)sizeof(T)) % 16 != 0)) return RDETR_ERR_INVALID_ARG;
     const long long pixel_bytes = (value_ld ? value_ld : (long long)H * D) * (long long)sizeof(T);
-    const bool aligned = (reinterpret_cast<uintptr_t>(value) % 16 == 0) && (reinterpret_cast<uintptr_t>(out) % 16 == 0) &&
-                         (reinterpret_cast<uintptr_t>(src_a) % 8 == 0) && (reinterpret_cast<uintptr_t>(src_b) % 4 == 0);
+    const bool aligned = all_aligned(16, value, out) && aligned_to(src_a, 8) && aligned_to(src_b, 4);
     if (fast_path(H, D, L, P) && aligned && (long long)S * pixel_bytes < (1ll << 31)) {
         if constexpr (sizeof(T) == 2) {
             // encoder shape (queries = the pyramid's own pixels): the LDS-window MFMA kernel.  It enumerates its queries as the
@@ -550,7 +549,7 @@ static int msda_forward(const T *value, int layout, const int64_t *shapes, const
         const int qpb = kWavesPerBlock * slots;
         const long long tiles = (Nq + qpb - 1) / qpb;
         const long long nblk = (long long)B * H * tiles;
-        if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+        if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
         launch_qrun<T, FUSED>(dim3((unsigned)nblk), dim3(kWavesPerBlock * kWave), stream, value, shapes, level_start,
                               src_a, src_b, ref, ref_dim, S, L, Nq, (int)tiles, (int)nblk, out, pad_mask, ld_a, ld_b, hm ? 1 : 0,
                               (int)pixel_bytes);
@@ -734,7 +733,7 @@ extern "C" int rdetr_value_to_head_major_bf16(const uint16_t *src, long long ld,
 {
     if (B < 0 || S < 0 || H != rdetr::kHeads || D != rdetr::kHeadDim || ld < H * D || ld % 8) return RDETR_ERR_INVALID_ARG;
     if (B == 0 || S == 0) return RDETR_OK;
-    if (!src || !dst || reinterpret_cast<uintptr_t>(src) % 16 || reinterpret_cast<uintptr_t>(dst) % 16) return RDETR_ERR_INVALID_ARG;
+    if (!src || !dst || !rdetr::all_aligned(16, src, dst)) return RDETR_ERR_INVALID_ARG;
     if (B > 65535) return RDETR_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(rdetr::value_to_head_major_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)B), dim3(256), 0,
                        static_cast<hipStream_t>(stream), src, ld, key_padding_mask, S, dst);

@@ -35,7 +35,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 #include "msda_qrun.h"
 
 namespace rdetr {
@@ -505,6 +505,15 @@ struct ResVariant {
 #endif
 };
 
+// One launch of one variant: the kernel is named by its template arguments, so each variant sets its own LDS attribute
+template <int LT, bool FUSED, int RW, int LR, int DBG = 0>
+static int res_launch(const ResArgs &a, dim3 grid, int lds, hipStream_t stream)
+{
+    if (const int s = ensure_dynamic_lds<msda_fwd_res_kernel<LT, FUSED, RW, LR, DBG>>(kLdsBytes)) return s;
+    hipLaunchKernelGGL((msda_fwd_res_kernel<LT, FUSED, RW, LR, DBG>), grid, dim3(RW * kWave), (size_t)lds, stream, a);
+    return launch_status();
+}
+
 // Host side.  Returns RDETR_ERR_UNSUPPORTED for everything the kernel does not cover (the caller then runs the query-run kernel).
 template <bool FUSED>
 static int msda_res_forward(const uint16_t *value, const int64_t *shapes, const int64_t *level_start, const void *src_a,
@@ -524,14 +533,13 @@ static int msda_res_forward(const uint16_t *value, const int64_t *shapes, const 
     }
     if (at != S) return RDETR_ERR_UNSUPPORTED;
     // alignment of the vector loads (msda_fwd.hip: vec_ok / vec5_ok)
-    const auto al = [](const void *p, uintptr_t n) { return reinterpret_cast<uintptr_t>(p) % n == 0; };
-    if (!al(value, 16) || !al(out, 16)) return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, value, out)) return RDETR_ERR_UNSUPPORTED;
     if (L == 4) {
-        if (!al(src_a, 16) || !al(src_b, 16)) return RDETR_ERR_UNSUPPORTED;
-        if (FUSED && (!al(ref, 16) || (ld_a * 2) % 16 != 0 || (ld_b * 2) % 16 != 0)) return RDETR_ERR_UNSUPPORTED;
+        if (!all_aligned(16, src_a, src_b)) return RDETR_ERR_UNSUPPORTED;
+        if (FUSED && (!aligned_to(ref, 16) || (ld_a * 2) % 16 != 0 || (ld_b * 2) % 16 != 0)) return RDETR_ERR_UNSUPPORTED;
     } else {
-        if (!al(src_a, 8) || !al(src_b, 4)) return RDETR_ERR_UNSUPPORTED;
-        if (FUSED && (!al(ref, 16) || (ld_a * 2) % 4 != 0)) return RDETR_ERR_UNSUPPORTED;
+        if (!aligned_to(src_a, 8) || !aligned_to(src_b, 4)) return RDETR_ERR_UNSUPPORTED;
+        if (FUSED && (!aligned_to(ref, 16) || (ld_a * 2) % 4 != 0)) return RDETR_ERR_UNSUPPORTED;
     }
     const int RW = ResVariant::waves;
     const int stage = L * kPoints * kRQ * 16 * RW;                               // weights of all points, per wave
@@ -562,57 +570,45 @@ static int msda_res_forward(const uint16_t *value, const int64_t *shapes, const 
         a.runs = (int)t;
     }
     const int lds = a.stage_base + stage;
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return RDETR_ERR_LAUNCH;
-        cus = prop.multiProcessorCount >= 8 ? prop.multiProcessorCount / 8 * 8 : 256;
-    }
+    const int cus = device_cu_count() >= kXcds ? device_cu_count() / kXcds * kXcds : kCus;      // the same number of workgroups on every XCD
     const dim3 grid((unsigned)cus);
-    auto launch = [&](auto kern, int waves) -> int {
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
-        hipLaunchKernelGGL(kern, grid, dim3(waves * kWave), (size_t)lds, stream, a);
-        return launch_status();
-    };
     const bool two = lr == L - 2;
 #ifdef RDETR_DEV
     if (ResVariant::dbg && L == 4 && !FUSED && two) {
         if constexpr (!FUSED) {
             switch (ResVariant::dbg) {
-            case 512: return launch(msda_fwd_res_kernel<4, false, 8, 2, 512>, 8);
-            case 128: return launch(msda_fwd_res_kernel<4, false, 12, 2, 128>, 12);
-            case 256: return launch(msda_fwd_res_kernel<4, false, 12, 2, 256>, 12);
-            case 16: return launch(msda_fwd_res_kernel<4, false, 8, 2, 16>, 8);
-            case 32: return launch(msda_fwd_res_kernel<4, false, 8, 2, 32>, 8);
-            case 64: return launch(msda_fwd_res_kernel<4, false, 8, 2, 64>, 8);
-            case 1: return launch(msda_fwd_res_kernel<4, false, 12, 2, 1>, 12);
-            case 2: return launch(msda_fwd_res_kernel<4, false, 12, 2, 2>, 12);
-            case 3: return launch(msda_fwd_res_kernel<4, false, 12, 2, 3>, 12);
-            case 4: return launch(msda_fwd_res_kernel<4, false, 12, 2, 4>, 12);
-            case 7: return launch(msda_fwd_res_kernel<4, false, 12, 2, 7>, 12);
-            case 8: return launch(msda_fwd_res_kernel<4, false, 12, 2, 8>, 12);
-            case 9: return launch(msda_fwd_res_kernel<4, false, 12, 2, 9>, 12);
-            case 11: return launch(msda_fwd_res_kernel<4, false, 12, 2, 11>, 12);
-            case 12: return launch(msda_fwd_res_kernel<4, false, 12, 2, 12>, 12);
-            case 15: return launch(msda_fwd_res_kernel<4, false, 12, 2, 15>, 12);
+            case 512: return res_launch<4, false, 8, 2, 512>(a, grid, lds, stream);
+            case 128: return res_launch<4, false, 12, 2, 128>(a, grid, lds, stream);
+            case 256: return res_launch<4, false, 12, 2, 256>(a, grid, lds, stream);
+            case 16: return res_launch<4, false, 8, 2, 16>(a, grid, lds, stream);
+            case 32: return res_launch<4, false, 8, 2, 32>(a, grid, lds, stream);
+            case 64: return res_launch<4, false, 8, 2, 64>(a, grid, lds, stream);
+            case 1: return res_launch<4, false, 12, 2, 1>(a, grid, lds, stream);
+            case 2: return res_launch<4, false, 12, 2, 2>(a, grid, lds, stream);
+            case 3: return res_launch<4, false, 12, 2, 3>(a, grid, lds, stream);
+            case 4: return res_launch<4, false, 12, 2, 4>(a, grid, lds, stream);
+            case 7: return res_launch<4, false, 12, 2, 7>(a, grid, lds, stream);
+            case 8: return res_launch<4, false, 12, 2, 8>(a, grid, lds, stream);
+            case 9: return res_launch<4, false, 12, 2, 9>(a, grid, lds, stream);
+            case 11: return res_launch<4, false, 12, 2, 11>(a, grid, lds, stream);
+            case 12: return res_launch<4, false, 12, 2, 12>(a, grid, lds, stream);
+            case 15: return res_launch<4, false, 12, 2, 15>(a, grid, lds, stream);
             default: break;
             }
         }
     }
     if (RW == 16) {
-        if (L == 4) return two ? launch(msda_fwd_res_kernel<4, FUSED, 16, 2>, 16) : launch(msda_fwd_res_kernel<4, FUSED, 16, 3>, 16);
-        return two ? launch(msda_fwd_res_kernel<5, FUSED, 16, 3>, 16) : launch(msda_fwd_res_kernel<5, FUSED, 16, 4>, 16);
+        if (L == 4) return two ? res_launch<4, FUSED, 16, 2>(a, grid, lds, stream) : res_launch<4, FUSED, 16, 3>(a, grid, lds, stream);
+        return two ? res_launch<5, FUSED, 16, 3>(a, grid, lds, stream) : res_launch<5, FUSED, 16, 4>(a, grid, lds, stream);
     }
     if (RW == 8) {
-        if (L == 4) return two ? launch(msda_fwd_res_kernel<4, FUSED, 8, 2>, 8) : launch(msda_fwd_res_kernel<4, FUSED, 8, 3>, 8);
-        return two ? launch(msda_fwd_res_kernel<5, FUSED, 8, 3>, 8) : launch(msda_fwd_res_kernel<5, FUSED, 8, 4>, 8);
+        if (L == 4) return two ? res_launch<4, FUSED, 8, 2>(a, grid, lds, stream) : res_launch<4, FUSED, 8, 3>(a, grid, lds, stream);
+        return two ? res_launch<5, FUSED, 8, 3>(a, grid, lds, stream) : res_launch<5, FUSED, 8, 4>(a, grid, lds, stream);
     }
 #endif
     // 12 waves = 3 per SIMD = 168 registers each: the rounds need ~160 (16 waves: spills, 170 us; 8 waves: the same time as 12)
-    if (L == 4) return two ? launch(msda_fwd_res_kernel<4, FUSED, 12, 2>, 12) : launch(msda_fwd_res_kernel<4, FUSED, 12, 3>, 12);
-    return two ? launch(msda_fwd_res_kernel<5, FUSED, 12, 3>, 12) : launch(msda_fwd_res_kernel<5, FUSED, 12, 4>, 12);
+    if (L == 4) return two ? res_launch<4, FUSED, 12, 2>(a, grid, lds, stream) : res_launch<4, FUSED, 12, 3>(a, grid, lds, stream);
+    return two ? res_launch<5, FUSED, 12, 3>(a, grid, lds, stream) : res_launch<5, FUSED, 12, 4>(a, grid, lds, stream);
 }
 
 }  // namespace rdetr

@@ -30,7 +30,7 @@
 // relative representation error (the bf16 output rounds at 2^-9).
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -651,19 +651,9 @@ int msda_sweep_forward(const uint16_t *value, const int64_t *shapes, const int64
     if (th == 0) return RDETR_ERR_UNSUPPORTED;
     const long long total = (long long)B * kSwHeads * nb * steps_x;
     if (total >= (1ll << 24)) return RDETR_ERR_UNSUPPORTED;                  // sw_div on the step id
-    static int cus = 0;
-    if (cus == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return RDETR_ERR_LAUNCH;
-        cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    auto kern = msda_fwd_sweep_kernel<HM>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kSwLdsBytes);
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
-    const long long nblk = total < cus ? total : cus;                        // one persistent workgroup per CU
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kSwThreads), (size_t)kSwLdsBytes, stream, value, loc, attn, lv, S, nb,
+    if (const int s = ensure_dynamic_lds<msda_fwd_sweep_kernel<HM>>(kSwLdsBytes)) return s;
+    const long long cus = device_cu_count(), nblk = total < cus ? total : cus;       // one persistent workgroup per CU
+    hipLaunchKernelGGL((msda_fwd_sweep_kernel<HM>), dim3((unsigned)nblk), dim3(kSwThreads), (size_t)kSwLdsBytes, stream, value, loc, attn, lv, S, nb,
                        steps_x, (int)total, (int)nblk, dbg, out);
     return launch_status();
 }
@@ -689,9 +679,7 @@ extern "C" int rdetr_msda_forward_sweep_bf16(const uint16_t *value, int value_la
     if (!value || !host_spatial_shapes || !host_level_start_index || !sampling_loc || !attn_weight || !out) return RDETR_ERR_INVALID_ARG;
     if (S == 0) return RDETR_ERR_INVALID_ARG;
     if (H != rdetr::kSwHeads || D != rdetr::kSwHeadDim || P != rdetr::kSwPoints) return RDETR_ERR_UNSUPPORTED;
-    if (reinterpret_cast<uintptr_t>(value) % 16 || reinterpret_cast<uintptr_t>(out) % 16 ||
-        reinterpret_cast<uintptr_t>(sampling_loc) % 16 || reinterpret_cast<uintptr_t>(attn_weight) % 8)
-        return RDETR_ERR_UNSUPPORTED;
+    if (!rdetr::all_aligned(16, value, out, sampling_loc) || !rdetr::aligned_to(attn_weight, 8)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t s = static_cast<hipStream_t>(stream);
     return value_layout == RDETR_VALUE_BHSD
                ? rdetr::msda_sweep_forward<true>(value, host_spatial_shapes, host_level_start_index, sampling_loc, attn_weight, B,

@@ -47,7 +47,7 @@
 // 2^-17 relative representation error (the bf16 output rounds at 2^-9).
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -815,17 +815,14 @@ int msda_win_forward(const uint16_t *value, const int64_t *shapes, const int64_t
     if (L != kWnLevels || Nq != S || S < 4096) return RDETR_ERR_UNSUPPORTED;
     const long long gpix = HM ? 64 : 512;
     if ((long long)S * gpix >= (1ll << 31) || S > (1 << 21)) return RDETR_ERR_UNSUPPORTED;     // tile geometry: 2 * 16 * w * regions < 2^24
-    auto kern = msda_fwd_win_kernel<FUSED, HM>;
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                                       hipFuncAttributeMaxDynamicSharedMemorySize, kWnLdsBytes);
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
+    if (const int s = ensure_dynamic_lds<msda_fwd_win_kernel<FUSED, HM>>(kWnLdsBytes)) return s;
     const long long pairs = (long long)B * kWnHeads;
-    long long splits = 256 / pairs;                 // one resident workgroup per CU
+    long long splits = kCus / pairs;                // one resident workgroup per CU
     if (splits < 1) splits = 1;
     if (splits > 64) splits = 64;
     const long long nblk = pairs * splits;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kWnThreads), (size_t)kWnLdsBytes, stream, value, shapes,
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((msda_fwd_win_kernel<FUSED, HM>), dim3((unsigned)nblk), dim3(kWnThreads), (size_t)kWnLdsBytes, stream, value, shapes,
                        level_start, src_a, src_b, ref, ref_dim, S, (int)splits, (int)nblk, RDETR_WIN_DBG, ld_a, ld_b, out);
     return launch_status();
 }

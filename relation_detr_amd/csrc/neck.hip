@@ -17,7 +17,7 @@
 // Position encoding: one lane per (pixel, frequency) writes the sin and the cos channel; every step is one fp32 IEEE operation in
 // the reference's order and dim_t comes from the caller, because a padded column's argument is about -3e6 rad and one ulp of dim_t
 // moves it by 0.2 rad.
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 namespace {

@@ -9,14 +9,14 @@
 // No atomics: a chunk belongs to one workgroup whatever the grid, every sum has a fixed order, so the bits repeat from run to run.
 // The arithmetic is torch's single-tensor AdamW (torch/optim/adam.py, _single_tensor_adam) element by element in fp32, under the
 // makefile's -ffp-contract=off and HIP's correctly rounded division and square root.
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 namespace {
 
 constexpr int kOptThreads = 256;
 constexpr int kOptWaves = kOptThreads / kWave;
-constexpr int kOptGridCap = 2048;            // 256 CUs x 8 workgroups: the grid walks the chunks with this stride beyond it
+constexpr int kOptGridCap = 8 * kCus;        // 8 workgroups per CU: the grid walks the chunks with this stride beyond it
 constexpr int kCoefThreads = 256;
 
 static_assert(sizeof(rdetr_optim_tensor) == 40 && sizeof(rdetr_optim_step) == 40 && sizeof(rdetr_optim_chunk) == 16, "table layout");

@@ -18,7 +18,7 @@
 //              = one 16-byte store; for the value: column block u = head u of the head-major plane).
 #include <type_traits>
 
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -172,29 +172,15 @@ extern "C" int rdetr_encoder_proj_k256_bf16(const uint16_t *x, long long ldx, co
                                             const uint16_t *bv, const uint16_t *pwq, const uint16_t *bq, const uint8_t *row_mask, int B, int S,
                                             int q_cols, uint16_t *out_hm, uint16_t *out_q, void *stream)
 {
-    if (B < 0 || S < 0 || ldx < 256 || ldq < 256) return RDETR_ERR_INVALID_ARG;
+    if (B < 0 || S < 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = rows_status({{x, ldx, 256, 2}, {xq, ldq, 256, 2}})) return s;
     if (q_cols != 384 && q_cols != 480) return RDETR_ERR_UNSUPPORTED;
-    if ((ldx & 7) || (ldq & 7)) return RDETR_ERR_UNSUPPORTED;
     if (B == 0 || S == 0) return RDETR_OK;
     if (!x || !xq || !pwv || !pwq || !out_hm || !out_q) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (!al(x) || !al(xq) || !al(pwv) || !al(pwq) || !al(out_hm) || !al(out_q)) return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, pwv, pwq, out_hm, out_q)) return RDETR_ERR_UNSUPPORTED;
     const long long M = (long long)B * S;
-    static const hipError_t attr = [] {
-        hipError_t e = hipSuccess;
-        const void *fns[4] = {reinterpret_cast<const void *>(encoder_proj_k256_kernel<2, 512, 384>),
-                              reinterpret_cast<const void *>(encoder_proj_k256_kernel<1, 768, 384>),
-                              reinterpret_cast<const void *>(encoder_proj_k256_kernel<2, 512, 480>),
-                              reinterpret_cast<const void *>(encoder_proj_k256_kernel<1, 768, 480>)};
-        for (const void *fn : fns) {
-            const hipError_t r = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kPjLdsBytes);
-            if (r != hipSuccess) e = r;
-        }
-        return e;
-    }();
-    if (attr != hipSuccess) return RDETR_ERR_LAUNCH;
-    // tile shape as for the thin feed-forward experiment: rounds of tiles over 256 CUs x (waves per SIMD x blocks per wave)
-    const auto rounds = [&](long long rows) { return ((M + rows - 1) / rows + 255) / 256; };
+    // tile shape as for the thin feed-forward experiment: rounds of tiles over kCus CUs x (waves per SIMD x blocks per wave)
+    const auto rounds = [&](long long rows) { return ((M + rows - 1) / rows + kCus - 1) / kCus; };
     long long best = 4 * rounds(256);
     int thin = 0;
 #ifndef RDETR_PROJ_THIN
@@ -210,8 +196,11 @@ extern "C" int rdetr_encoder_proj_k256_bf16(const uint16_t *x, long long ldx, co
         }
     const long long tile_rows = thin ? 16 * thin : 256;
     const long long ntiles = (M + tile_rows - 1) / tile_rows;
-    if (ntiles > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(ntiles)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    if (ensure_dynamic_lds<encoder_proj_k256_kernel<2, 512, 384>>(kPjLdsBytes) || ensure_dynamic_lds<encoder_proj_k256_kernel<1, 768, 384>>(kPjLdsBytes) ||
+        ensure_dynamic_lds<encoder_proj_k256_kernel<2, 512, 480>>(kPjLdsBytes) || ensure_dynamic_lds<encoder_proj_k256_kernel<1, 768, 480>>(kPjLdsBytes))
+        return RDETR_ERR_LAUNCH;
     auto launch = [&](auto kernel, unsigned threads) {
         hipLaunchKernelGGL(kernel, dim3((unsigned)ntiles), dim3(threads), kPjLdsBytes, st, x, ldx, xq, ldq, pwv, bv, pwq, bq, row_mask, S, M,
                            out_hm, out_q);

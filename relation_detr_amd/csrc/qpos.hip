@@ -54,7 +54,7 @@
 //              inputs (96 VGPRs) do not fit beside two fragment sets at 8 waves, and with one set the loads no longer overlap
 //              the MFMAs of the previous block.  Loads under a lane mask for the rows >= M (`rok ? load : 0`): hipcc branches
 //              around every one and put a vmcnt(0) between them.
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -313,17 +313,15 @@ extern "C" int rdetr_query_pos_k256_bf16(const uint16_t *emb, long long lde, con
                                          const uint16_t *c1, const uint16_t *pv2, const uint16_t *c2, long long M, uint16_t *out_pos,
                                          uint16_t *out_qpp, void *stream)
 {
-    if (M < 0 || lde < 512 || ldq < 256) return RDETR_ERR_INVALID_ARG;
-    if ((lde & 7) || (ldq & 7)) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = rows_status({{emb, lde, 512, 2}, {query, ldq, 256, 2}})) return s;
     if (M == 0) return RDETR_OK;
     if (!emb || !query || !pw1a || !pw1b || !b1 || !pw2 || !b2 || !out_pos || !out_qpp) return RDETR_ERR_INVALID_ARG;
     const bool any = pv1 || c1 || pv2 || c2, all = pv1 && c1 && pv2 && c2;
     if (any && !all) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (!al(emb) || !al(query) || !al(pw1a) || !al(pw1b) || !al(pw2) || (all && (!al(pv1) || !al(pv2))) || !al(out_pos) || !al(out_qpp))
-        return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, pw1a, pw1b, pw2, pv1, pv2, out_pos, out_qpp)) return RDETR_ERR_UNSUPPORTED;
     const long long nblk = (M + kQpRows - 1) / kQpRows;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     if (all)
         hipLaunchKernelGGL(query_pos_k256_kernel<true>, dim3((unsigned)nblk), dim3(kQpThreads), 0, static_cast<hipStream_t>(stream), emb, lde,
                            query, ldq, pw1a, pw1b, b1, pw2, b2, pv1, c1, pv2, c2, M, out_pos, out_qpp);
@@ -344,19 +342,16 @@ extern "C" int rdetr_query_pos_inproj_k256_bf16(const uint16_t *emb, long long l
                                                 uint16_t *out_pos, uint16_t *out_qpp, uint16_t *out_qk, long long ldqk, uint16_t *out_v,
                                                 long long ldv, void *stream)
 {
-    if (M < 0 || lde < 512 || ldq < 256 || ldqk < 512 || ldv < 256) return RDETR_ERR_INVALID_ARG;
-    if ((lde & 7) || (ldq & 7) || (ldqk & 7) || (ldv & 7)) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = rows_status({{emb, lde, 512, 2}, {query, ldq, 256, 2}, {out_qk, ldqk, 512, 2}, {out_v, ldv, 256, 2}})) return s;
     if (M == 0) return RDETR_OK;
     if (!emb || !query || !pw1a || !pw1b || !b1 || !pw2 || !b2 || !out_pos || !out_qpp || !pwq || !pwk || !pwv || !bias || !out_qk || !out_v)
         return RDETR_ERR_INVALID_ARG;
     const bool any = pv1 || c1 || pv2 || c2, all = pv1 && c1 && pv2 && c2;
     if (any && !all) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (!al(emb) || !al(query) || !al(pw1a) || !al(pw1b) || !al(pw2) || (all && (!al(pv1) || !al(pv2))) || !al(out_pos) || !al(out_qpp)
-        || !al(pwq) || !al(pwk) || !al(pwv) || !al(out_qk) || !al(out_v))
-        return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, pw1a, pw1b, pw2, pv1, pv2, out_pos, out_qpp, pwq, pwk, pwv)) return RDETR_ERR_UNSUPPORTED;
     const long long nblk = (M + kQpRows - 1) / kQpRows;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     const QpInProj ip = {pwq, pwk, pwv, bias, out_qk, out_v, ldqk, ldv};
     if (all)
         hipLaunchKernelGGL(query_pos_inproj_k256_kernel<true>, dim3((unsigned)nblk), dim3(kQpThreads), 0, static_cast<hipStream_t>(stream),

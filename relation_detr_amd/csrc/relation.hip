@@ -16,7 +16,7 @@
 // (nn.MultiheadAttention with a float attn_mask, relation_transformer.py:452-459), one wavefront
 // per row, row kept in registers between the max / sum / normalise passes (one HBM read of scores
 // and bias, one write), wave reductions by cross-lane shuffles.
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -382,7 +382,7 @@ extern "C" int rdetr_relation_bias_f32(const float *src, const float *tgt, const
         dt.v[k] = powf(temperature, (float)k * 2.0f / (float)F);
         dt.inv[k] = (float)(1.0 / (double)dt.v[k]);
     }
-    const bool aligned = reinterpret_cast<uintptr_t>(tgt) % 16 == 0;
+    const bool aligned = aligned_to(tgt, 16);
     if (F == 16 && Hh == 8 && aligned) {
         const int rows_per_block = kRelWaves * kRelRows;
         dim3 grid((N2 + kWave - 1) / kWave, (N1 + rows_per_block - 1) / rows_per_block, B), block(kRelWaves * kWave);
@@ -419,7 +419,7 @@ extern "C" int rdetr_relation_bias_ws_f32(const float *src, const float *tgt, co
                                           float *workspace, float *out, void *stream)
 {
     // the table route serves the model's configuration only; anything else is the plain entry point's business
-    const bool aligned = reinterpret_cast<uintptr_t>(tgt) % 16 == 0 && reinterpret_cast<uintptr_t>(workspace) % 8 == 0;
+    const bool aligned = aligned_to(tgt, 16) && aligned_to(workspace, 8);
     if (!(F == 16 && Hh == 8 && aligned && workspace) || B <= 0 || N1 <= 0 || N2 <= 0 || B > 65535)
         return rdetr_relation_bias_f32(src, tgt, proj_weight, proj_bias, B, N1, N2, Hh, F, scale, temperature, eps, out, stream);
     if (!src || !tgt || !proj_weight || !out) return RDETR_ERR_INVALID_ARG;
@@ -450,11 +450,9 @@ extern "C" int rdetr_bias_softmax_f32(float *scores, const float *bias, const ui
     hipStream_t st = static_cast<hipStream_t>(stream);
     const long long rows = (long long)BH * N1;
     const long long nblk = (rows + kSmWaves - 1) / kSmWaves;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     dim3 grid((unsigned)nblk), block(kSmWaves * kWave);
-    const bool vec = (N2 % 4 == 0) && reinterpret_cast<uintptr_t>(scores) % 16 == 0 &&
-                     (!bias || reinterpret_cast<uintptr_t>(bias) % 16 == 0) &&
-                     (!mask || reinterpret_cast<uintptr_t>(mask) % 4 == 0);
+    const bool vec = (N2 % 4 == 0) && all_aligned(16, scores, bias) && aligned_to(mask, 4);
     if (vec && N2 <= 16 * kWave * 4)
         launch_softmax<4>((N2 + kWave * 4 - 1) / (kWave * 4), grid, block, st, scores, bias, mask, rows, N1, N2);
     else if (N2 <= 16 * kWave)

@@ -13,7 +13,7 @@
 //   reduction    DETERMINISTIC: wave shuffles -> LDS across the 4 waves -> one 72-float record per block in a workspace ->
 //                a second kernel adds the records in a fixed order.  No float atomics, no zero-initialised output
 //                (SURVEY section 8 f4 asks for a deterministic alternative to atomics on the training path).
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -193,7 +193,7 @@ extern "C" int rdetr_relation_bias_backward_f32(const float *src, const float *t
         return launch_status();
     }
     if (!src || !tgt || !grad_out || !active || !workspace) return RDETR_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(tgt) % 16 != 0) return RDETR_ERR_INVALID_ARG;
+    if (!aligned_to(tgt, 16)) return RDETR_ERR_INVALID_ARG;
     const long long bxy = rb_blocks_xy(N1, N2);
     const int gx = (N2 + kRbThreads - 1) / kRbThreads, gy = (N1 + kRbRows - 1) / kRbRows;
     if ((long long)B * 8 > 65535 || gy > 65535 || bxy > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;

@@ -43,7 +43,8 @@
 //                add_layernorm256 passes (profiles/r19/time_rowtail_with_ffn_tail.txt).  A 32-row workgroup pulls all of W2
 //                (1 MiB) through its own L1: 7-8 us at 64 bytes per clock before any latency, on 57 of 256 CUs; the library
 //                kernel splits K over the idle CUs.  Taken out again, with its instantiations.
-#include "common.h"
+#include "launch.h"
+#include "rows256.h"
 
 namespace rdetr {
 
@@ -57,21 +58,7 @@ constexpr int kRtXImg = 2 * 8 * 64;                        // x in u32x4: [row b
 // this wave's 16 fragments of the packed weight (tiles 2 w, 2 w + 1), in the order the MFMAs take them
 struct RtFrags { u32x4 f[16]; };                           // f[2 s + e]: k-step s, tile e
 
-__device__ __forceinline__ float rt_half_sum(float v)
-{
-#pragma unroll
-    for (int o = 16; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ void rt_widen8(const u32x4 &r, float (&v)[8])
-{
-    v[0] = __builtin_bit_cast(float, r.x << 16); v[1] = __builtin_bit_cast(float, r.x & 0xffff0000u);
-    v[2] = __builtin_bit_cast(float, r.y << 16); v[3] = __builtin_bit_cast(float, r.y & 0xffff0000u);
-    v[4] = __builtin_bit_cast(float, r.z << 16); v[5] = __builtin_bit_cast(float, r.z & 0xffff0000u);
-    v[6] = __builtin_bit_cast(float, r.w << 16); v[7] = __builtin_bit_cast(float, r.w & 0xffff0000u);
-}
-
+// the loads are issued at the top of the kernel and widened (row256_widen8) where they are used
 __device__ __forceinline__ u32x4 rt_load8(const uint16_t *p) { return *reinterpret_cast<const u32x4 *>(p); }
 
 __device__ __forceinline__ void rt_store8(uint16_t *p, const float (&v)[8])
@@ -79,20 +66,21 @@ __device__ __forceinline__ void rt_store8(uint16_t *p, const float (&v)[8])
     *reinterpret_cast<u32x4 *>(p) = u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
 }
 
-// y = LayerNorm(v) * g + b over the 256 channels a half wave holds (8 per lane); the statistics of add_layernorm256_body
+// y = LayerNorm(v) * g + b over the 256 channels a half wave holds (8 per lane): the statistics block of add_layernorm256_body
+// (csrc/layernorm.hip) operation for operation -- a COPY, see rows256.h; change the two together
 __device__ __forceinline__ void rt_normalise(float (&v)[8], const float (&g)[8], const float (&b)[8], float eps, float (&y)[8])
 {
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) s += v[k];
-    const float mean = rt_half_sum(s) * (1.0f / 256.0f);
+    const float mean = row256_half_sum(s) * (1.0f / 256.0f);
     float sq = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         v[k] -= mean;
         sq += v[k] * v[k];
     }
-    const float rstd = 1.0f / sqrtf(rt_half_sum(sq) * (1.0f / 256.0f) + eps);
+    const float rstd = 1.0f / sqrtf(row256_half_sum(sq) * (1.0f / 256.0f) + eps);
 #pragma unroll
     for (int k = 0; k < 8; ++k) y[k] = v[k] * rstd * g[k] + b[k];
 }
@@ -180,11 +168,11 @@ __global__ __launch_bounds__(kRtThreads) void linear_ln_rows_kernel(RtArgs a)
     // bias, one rounding to bf16, + residual in fp32 -> the LDS image.  Lane (row, g): tile e holds columns c0 + 4 e .. + 3
     {
         float bb[8];
-        rt_widen8(bq, bb);
+        row256_widen8(bq, bb);
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
             float rf[8];
-            rt_widen8(rv[cb], rf);
+            row256_widen8(rv[cb], rf);
             const f32x4 lo = acc[0][cb], hi = acc[1][cb];
             const float o[8] = {lo.x + bb[0], lo.y + bb[1], lo.z + bb[2], lo.w + bb[3], hi.x + bb[4], hi.y + bb[5], hi.z + bb[6], hi.w + bb[7]};
             float s[8];
@@ -199,8 +187,8 @@ __global__ __launch_bounds__(kRtThreads) void linear_ln_rows_kernel(RtArgs a)
 
     // a half wave per row, two rows per half: rows 2 wave + half and 16 + 2 wave + half of the block
     float gm[8], bt[8];
-    rt_widen8(gq, gm);
-    rt_widen8(tq, bt);
+    row256_widen8(gq, gm);
+    row256_widen8(tq, bt);
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int lr = 16 * i + 2 * wave + half;
@@ -213,7 +201,7 @@ __global__ __launch_bounds__(kRtThreads) void linear_ln_rows_kernel(RtArgs a)
         if (ok) rt_store8(a.out + row * a.ldo + c, y);
         if (kPos && ok) {
             float pv[8];
-            rt_widen8(pr[i], pv);
+            row256_widen8(pr[i], pv);
 #pragma unroll
             for (int k = 0; k < 8; ++k) pv[k] += bf16_bits_to_f32(f32_to_bf16_bits(y[k]));        // out as stored
             rt_store8(a.out_pos + row * a.ldop + c, pv);
@@ -235,15 +223,15 @@ extern "C" int rdetr_linear_ln_rows_bf16(const uint16_t *x, long long ldx, const
                                          long long ldop, void *stream)
 {
     const bool has_pos = pos != nullptr;
-    if (M < 0 || ldx < 256 || ldr < 256 || ldo < 256 || (has_pos && (ldp < 256 || ldop < 256))) return RDETR_ERR_INVALID_ARG;
-    if ((ldx & 7) || (ldr & 7) || (ldo & 7) || (has_pos && ((ldp & 7) || (ldop & 7)))) return RDETR_ERR_UNSUPPORTED;
+    if (M < 0) return RDETR_ERR_INVALID_ARG;
+    if (const int s = has_pos ? rows_status({{x, ldx, 256, 2}, {residual, ldr, 256, 2}, {out, ldo, 256, 2}, {pos, ldp, 256, 2}, {out_pos, ldop, 256, 2}})
+                              : rows_status({{x, ldx, 256, 2}, {residual, ldr, 256, 2}, {out, ldo, 256, 2}}))
+        return s;
     if (M == 0) return RDETR_OK;
     if (!x || !packed || !residual || !gamma || !beta || !out || (has_pos && !out_pos)) return RDETR_ERR_INVALID_ARG;
-    auto al = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    if (!al(x) || !al(packed) || !al(bias) || !al(residual) || !al(gamma) || !al(beta) || !al(out) || (has_pos && (!al(pos) || !al(out_pos))))
-        return RDETR_ERR_UNSUPPORTED;
+    if (!all_aligned(16, packed, bias, gamma, beta)) return RDETR_ERR_UNSUPPORTED;
     const long long nblk = (M + kRtRows - 1) / kRtRows;
-    if (nblk > 0x7fffffffll) return RDETR_ERR_UNSUPPORTED;
+    if (!grid_fits(nblk)) return RDETR_ERR_UNSUPPORTED;
     const RtArgs a = {x, packed, bias, residual, gamma, beta, pos, out, out_pos, ldx, ldr, ldp, ldo, ldop, M, eps};
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (has_pos)

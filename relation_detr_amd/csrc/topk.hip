@@ -11,7 +11,7 @@
 // order among equal values is unspecified; its NaN rule is the same).  Every comparison is made on a 64-bit composite
 //     (ordered 32-bit key of the float) << 20  |  (0xfffff - index)            n < 2^20
 // whose values are pairwise distinct, so the k-th largest composite is a sharp threshold and no tie ever needs a rule of its own.
-#include "common.h"
+#include "launch.h"
 
 namespace rdetr {
 
@@ -415,7 +415,7 @@ extern "C" int rdetr_topk(const void *x, int is_bf16, int rows, int n, int k, vo
     if (k > n || k > 1024 || n >= (1 << 20) || rows > 65535) return RDETR_ERR_UNSUPPORTED;
     if (rows == 0) return RDETR_OK;
     if (!x || !workspace || !values || !indices) return RDETR_ERR_INVALID_ARG;
-    if (reinterpret_cast<uintptr_t>(workspace) % 16) return RDETR_ERR_UNSUPPORTED;
+    if (!aligned_to(workspace, 16)) return RDETR_ERR_UNSUPPORTED;
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned char *ws = static_cast<unsigned char *>(workspace);
     const int chunks = (n + kTkChunk - 1) / kTkChunk;

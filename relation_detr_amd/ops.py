@@ -116,7 +116,8 @@ _host_array_cache: dict = {}
 
 
 def _host_level_arrays(spatial_shapes: torch.Tensor, level_start_index: torch.Tensor):
-    """ctypes int64 arrays of the cached host copy of the level table (the tile kernel's entry points take HOST pointers)."""
+    """ctypes int64 arrays of the cached host copy of the level table (the resident-levels and sweep kernels' entry points take
+    HOST pointers)."""
     import ctypes
     key = host_levels(spatial_shapes, level_start_index)
     hit = _host_array_cache.get(key)
