@@ -948,6 +948,36 @@ int rdetr_pyramid_sine_pos_f32(const int *cum, const int *level_hw, int L, int B
 int rdetr_pyramid_sine_pos_bf16(const int *cum, const int *level_hw, int L, int B, int F, const float *dim_t, int normalize, float scale,
                                 float eps, float offset, void *const *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The image front end (csrc/images.hip; models/detectors/base_detector.py: EvalResize -> ConvertImageDtype -> Normalize ->
+ * image_list_from_tensors -> construct_mask): a list of device images -> the padded batch and its padding mask, one launch.
+ *
+ * images: a HOST array of B <= RDETR_IMAGE_MAX_IMAGES descriptors, copied into the kernel's argument block.  src: a DEVICE image
+ * [3, h, w], uint8 (src_is_u8 = 1) or fp32, unit stride along a row, row_stride and channel_stride in elements (>= 0); (oh, ow): the
+ * size it is resized to, (oh, ow) == (h, w) for none.  out: [B, 3, Hp, Wp] fp32 or bf16 (out_bf16), contiguous, or with
+ * channels_last = 1 the same tensor stored [B, Hp, Wp, 3]; 16-byte aligned, Wp % 8 == 0.  mask: [B, Hp, Wp] bool bytes, 1 = padded.
+ * mean, std: HOST float[3], read when normalize = 1.
+ *
+ * Per output (b, c, y, x): y >= oh_b or x >= ow_b gives +0 and mask 1.  Otherwise mask 0 and v = sum_j sum_i Wy[y, j] Wx[x, i]
+ * src[c, j, i] with torch's antialiased bilinear taps for n_in -> n_out per axis: scale = n_in / n_out, support = max(scale, 1),
+ * center = scale (o + 0.5), lo = max(int(center - support + 0.5), 0), hi = min(int(center + support + 0.5), n_in), w_j = max(0, 1 -
+ * |(j - center + 0.5) / support|) over [lo, hi) divided by their sum; the taps in fp64, the two passes (rows first, as torch's CPU
+ * kernel) in fp32.  uint8: q = rint(v) (half to even), out = (float(q) / 255 - mean_c) / std_c, three IEEE fp32 operations.  fp32:
+ * out = (v - mean_c) / std_c, or v with normalize = 0 (fp32 sources only).  bf16 output rounds the fp32 value to nearest even.
+ *
+ * RDETR_ERR_INVALID_ARG: a NULL pointer, a size <= 0, a negative stride, B < 0, a flag outside {0, 1}, (oh, ow) beyond (Hp, Wp),
+ * a std of 0.  RDETR_ERR_UNSUPPORTED: B > RDETR_IMAGE_MAX_IMAGES, h > RDETR_IMAGE_MAX_DOWNSCALE * oh (or w, ow: the LDS rows of one
+ * tile), Wp % 8 != 0, a misaligned out / mask / fp32 src, a uint8 source with normalize = 0.  B == 0 launches nothing. */
+#define RDETR_IMAGE_MAX_IMAGES 16
+#define RDETR_IMAGE_MAX_DOWNSCALE 8
+typedef struct rdetr_image_desc {
+    const void *src;
+    long long row_stride, channel_stride;
+    int h, w, oh, ow;
+} rdetr_image_desc;
+int rdetr_image_batch(const rdetr_image_desc *images, int B, int src_is_u8, int Hp, int Wp, const float *mean, const float *std,
+                      int normalize, int out_bf16, int channels_last, void *out, void *mask, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

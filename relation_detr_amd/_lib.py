@@ -127,6 +127,7 @@ SIGNATURES = {
     "rdetr_pyramid_masks": [_vp] + [_c_int] * 4 + [_vp, _c_int, _vp, _vp, _vp],
     "rdetr_pyramid_sine_pos_f32": [_vp, _vp] + [_c_int] * 3 + [_vp, _c_int] + [_c_float] * 3 + [_vp, _vp],
     "rdetr_pyramid_sine_pos_bf16": [_vp, _vp] + [_c_int] * 3 + [_vp, _c_int] + [_c_float] * 3 + [_vp, _vp],
+    "rdetr_image_batch": [_vp] + [_c_int] * 4 + [_vp, _vp] + [_c_int] * 3 + [_vp, _vp, _vp],
 }
 
 ERR_INVALID_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = -1, -2, -3            # rdetr_status (include/relation_detr_amd.h)

@@ -4,7 +4,8 @@
 ``RelationDETRHead(transformer, criterion, denoising_generator)`` keeps the reference detector's attribute names, so its
 state-dict keys are the reference's minus ``backbone.*`` and ``neck.*``; ``RelationDETR(neck, position_embedding, transformer, criterion,
 denoising_generator)`` puts the neck and the position encoding in front, so its keys are the reference's minus ``backbone.*`` and its
-``forward`` starts at the backbone's feature maps and the padding mask.  One deviation: when no image of the batch has a box the
+``forward`` starts at the backbone's feature maps and the padding mask; ``RelationDETRWithBackbone(backbone, ..., preprocessor)`` starts at
+the list of images, as the reference's detector does, and in eval mode ends at the detections.  One deviation: when no image of the batch has a box the
 reference still builds (empty) denoising queries and reports ``_dn`` losses of zero; here the transformer then runs without
 denoising queries and the criterion with ``dn_meta=None``, so the dict has no ``_dn`` keys.
 """
@@ -12,12 +13,13 @@ from __future__ import annotations
 
 from typing import Dict, Optional, Sequence
 
+import torch
 from torch import Tensor, nn
 
 from .criterion import RelationCriterion
 from .denoising import GenerateCDNQueries, Noise
 from .neck import build_pyramid
-from .transformer import RelationTransformer
+from .transformer import RelationTransformer, select_detections
 
 
 class RelationDETRHead(nn.Module):
@@ -76,3 +78,38 @@ class RelationDETR(RelationDETRHead):
     def forward(self, features, mask: Tensor, targets: Optional[Sequence[Dict[str, Tensor]]] = None, noise: Optional[Noise] = None):
         feats, masks, pos = self.get_multi_levels(features, mask)
         return RelationDETRHead.forward(self, feats, masks, pos, targets, noise)
+
+
+class RelationDETRWithBackbone(RelationDETR):
+    """``forward(images, targets=None, noise=None)``, the reference's ``RelationDETR.forward(images, targets)``: ``images`` a list of
+    ``[3, h, w]`` tensors (eval: uint8 or float in [0, 1], any sizes; training: augmented, float, normalised), ``targets`` with
+    ``boxes`` in xyxy pixels.  ``preprocessor`` (``frontend.ImagePreprocessor``) makes the batch, the mask and the prepared targets,
+    ``backbone`` -- the caller's module -- maps ``batch.tensors`` to the feature maps ``RelationDETR.forward`` takes.
+
+    Training mode returns the loss dict.  Eval mode returns ``(detections, tensor)``: ``tensor`` is ``select_detections``' ``[B, k, 6]``
+    = (x1, y1, x2, y2, score, label) in pixels of the ORIGINAL images, ``detections`` the reference's list of
+    ``{"scores", "labels", "boxes"}`` as views of it.
+
+    The attributes are the reference detector's, so ``state_dict()`` holds ``backbone.*`` and what ``RelationDETR`` holds; the
+    preprocessor has neither parameters nor buffers."""
+
+    def __init__(self, backbone: nn.Module, neck: nn.Module, position_embedding: nn.Module, transformer: RelationTransformer,
+                 criterion: RelationCriterion, denoising_generator: GenerateCDNQueries, preprocessor: nn.Module, num_select: int = 300):
+        RelationDETR.__init__(self, neck, position_embedding, transformer, criterion, denoising_generator)
+        self.backbone = backbone
+        self.preprocessor = preprocessor
+        self.num_select = num_select
+
+    def forward(self, images, targets: Optional[Sequence[Dict[str, Tensor]]] = None, noise: Optional[Noise] = None):
+        batch, targets = self.preprocessor(images, targets)
+        features = self.backbone(batch.tensors)
+        outputs = RelationDETR.forward(self, features, batch.mask, targets, noise)
+        if self.training:
+            return outputs
+        logits, boxes = outputs
+        return self.detections(logits, boxes, batch.original_sizes)
+
+    def detections(self, logits: Tensor, boxes: Tensor, original_sizes: Tensor):
+        sizes = original_sizes.to(device=logits.device, dtype=torch.int64)
+        dets = select_detections(logits.float(), boxes.float(), sizes, self.num_select)
+        return [{"scores": d[:, 4], "labels": d[:, 5].to(torch.int64), "boxes": d[:, :4]} for d in dets], dets
