@@ -54,7 +54,9 @@ Bounds (err = |kernel - reference|; "exact" = bit equality; each from the unit t
   zero_masked_rows_, row_max,                                                      row_max / topk / detections tests)
   topk (values + tie order), detections_from_topk
   _relation_attention_backward    2^-7 |ref| + 2e-2 max|ref|, the row term         test_gpu_attn_train::_check_grad
-                                  rowsum(dout * out) from the `out` it is handed
+                                  rowsum(dout * out) from the `out` it is handed;
+                                  dv + 2^-9 P^T |dO|, dk + 2^-9 scale |dS|^T |Q|
+                                  (attention_grad_rounding: P and dS in bf16)
   relation_bias_backward          weight 1e-4 |ref| + 2e-3 sqrt(pairs) / 30,       test_gpu_parity::test_relation_bias_backward_kernel
                                   bias 1e-5 |ref| + 1e-3
   ms_deform_attn_backward         value / weights 1e-4 max(1, max|ref|);           test_gpu_msda_train_fused (close_abs, close_offsets)
@@ -74,8 +76,8 @@ to bf16 the kernel makes, plus its fp32 accumulation; tests/test_shadow_train_ho
   ln_train.add_layer_norm_backward  statistics recomputed in float64.  bf16: dx, dgamma, dbeta  test_gpu_ln_train::test_accuracy_against_float64
                                   bf16 form;  fp32: dx 1e-5 max(1, max|ref|), dgamma / dbeta
                                   (1e-6 + 4 2^-24 sqrt(rows)) max(1, max|ref|)
-  attn_rel_train._relation_attention_boxes_train   out as relation_attention_boxes, lse as      test_gpu_attn_rel_train, test_gpu_attn_train
-                                  _relation_attention_train
+  attn_rel_train._relation_attention_boxes_train   out as relation_attention_boxes, lse 1e-3 +  test_gpu_attn_rel_train, test_gpu_attn_train
+                                  2^-9 sum_ch |W[h, ch]| (boxes_lse_bound: the bf16 sine features)
   attn_rel_train._relation_attention_boxes_backward   dq, dk, dv as _relation_attention_backward  test_gpu_attn_rel_train (_check_all, TAU)
                                   with the float64 relation bias;  grad_weight, grad_bias through
                                   the float64 ReLU: 2^-7 |ref| + 2e-2 max|ref| + sum |dS_ref| |feature|
@@ -119,6 +121,13 @@ unless said otherwise; the golden fixtures g10, g11, g12 pin those routes to the
 profiles/r23/ has the two report tables of the detector step (mixed precision with everything on, two steps; fp32 defaults), every
 ratio below 1.  Three bounds that the composed step exceeded changed their FORM, in the unit test and here together, each for a scale the
 earlier form lacked: relation_bias (relation_bias_bound), bias_softmax_ (bias_softmax_bound) and criterion.match_cost (match_cost_scale).
+
+Elements a checker excludes (``Cmp.keep``: the kink points of the sampling-location gradients, the dead columns of a cost table) may
+be inaccurate, never unwritten: a NaN or an infinity there that the reference lacks fails the record like any other element.
+tests/test_gpu_dirty_shapes.py runs the harness at small ragged shapes with every uninitialised allocation filled with 0x00, 0xFF
+and 0x42 first (tests/dirty.py); profiles/r26/ has those report tables.  Two bounds that its training step exceeded on clean memory
+changed their FORM there, in the unit test and here together, for a scale the earlier form lacked: the dk and dv of the attention
+backwards (attention_grad_rounding) and the log-sum-exp of the attention forward that generates its bias (boxes_lse_bound).
 """
 from __future__ import annotations
 
@@ -206,6 +215,10 @@ def _compare(c: Cmp):
     ratio = torch.nan_to_num(ratio, nan=math.inf)
     if c.keep is not None:
         ratio = torch.where(c.keep.to(ratio.device).expand_as(ratio), ratio, torch.zeros_like(ratio))
+        # an excluded element (a kink point) may be inaccurate, it may not be unwritten: a NaN or inf where the reference is finite
+        # fails there too
+        unwritten = ~torch.isfinite(got) & torch.isfinite(ref)
+        ratio = torch.where(unwritten, torch.full_like(ratio, math.inf), ratio)
     checked = int(ratio.numel() if c.keep is None else c.keep.expand_as(ratio).sum().item())
     if ratio.numel() == 0:
         return 0.0, 0, 0, c.label
@@ -450,12 +463,28 @@ def _attention_backward64(a, bias):
     ds = torch.where(p > 0, p * (dp - dterm), torch.zeros_like(p))                                   # a dead row's `out` is NaN
     refs = {"dq": (ds @ heads(k, M) * scale).transpose(1, 2).reshape(B, N, C),
             "dk": (ds.transpose(-1, -2) @ heads(q, N) * scale).transpose(1, 2).reshape(B, M, C),
-            "dv": (p.transpose(-1, -2) @ heads(dout, N)).transpose(1, 2).reshape(B, M, C)}
+            "dv": (p.transpose(-1, -2) @ heads(dout, N)).transpose(1, 2).reshape(B, M, C),
+            "rounding": attention_grad_rounding(p, ds, q, dout, H, scale)}
     return refs, ds
 
 
 def _attn_grad_bound(ref):
     return 2.0 ** -7 * ref.abs() + 2e-2 * ref.abs().max() + 1e-30
+
+
+def attention_grad_rounding(p, ds, q, dout, num_heads, scale):
+    """The scale the dk and dv bounds lacked.  dV = P^T dO and dK = scale dS^T Q run on the matrix pipe with P and dS rounded to
+    bf16, a relative error of up to 2^-9 per element, so whatever else the kernel does exactly
+        |dv_kernel - dv| <= 2^-9 (P^T |dO|),    |dk_kernel - dk| <= 2^-9 scale (|dS|^T |Q|).
+    Where the sums cancel -- a nearly flat softmax over 1,500 keys, as the hybrid pass of the ragged training step of
+    tests/test_gpu_dirty_shapes.py has it, where max |dv| is 6e-5 and max |dk| 3e-6 -- max |ref| falls orders below these sums
+    and 2e-2 max |ref| below that rounding.  (dq = scale dS K has the same term; no composition has needed it, so it keeps the
+    narrower form.)  p, ds [B,H,N,M] float64, q [B,N,C], dout [B,N,C] -> {"dk", "dv"} [B,M,C]."""
+    B, H, N, M = p.shape
+    heads = lambda t: t.double().abs().view(B, N, num_heads, -1).transpose(1, 2)                      # noqa: E731
+    back = lambda t: t.transpose(1, 2).reshape(B, M, -1)                                             # noqa: E731
+    return {"dv": 2.0 ** -9 * back(p.transpose(-1, -2) @ heads(dout)),
+            "dk": 2.0 ** -9 * scale * back(ds.abs().transpose(-1, -2) @ heads(q))}
 
 
 def chk__relation_attention_backward(a, res):
@@ -465,7 +494,8 @@ def chk__relation_attention_backward(a, res):
     for name, got in zip(("dq", "dk", "dv", "dbias"), res[:4]):
         ref = refs[name]
         if ref is not None:
-            cmps.append(Cmp(name, got, ref.reshape(got.shape), _attn_grad_bound(ref.reshape(got.shape))))
+            extra = refs["rounding"][name].reshape(got.shape) if name in refs["rounding"] else 0.0
+            cmps.append(Cmp(name, got, ref.reshape(got.shape), _attn_grad_bound(ref.reshape(got.shape)) + extra))
     return cmps
 
 
@@ -839,10 +869,21 @@ def _boxes_bias64(a):
                                    a["num_pos_feats"], a["temperature"], a["rel_scale"])
 
 
+def boxes_lse_bound(proj_weight, num_heads, rows):
+    """1e-3 (the bound of the materialised-bias forward) + 2^-9 sum_ch |W[h, ch]| for a row of head h: the kernel rounds the 64
+    sine features, each within [-1, 1], to bf16, so the bias it generates for a pair is off by up to that sum, and the row's
+    log-sum-exp moves by at most the largest bias error of its pairs.  With Conv2d's default initialisation (|W| <= 1/8) the sum
+    is at most 7.8e-3, the TAU of tests/test_gpu_attn_rel_train.py; weights of another scale move it with them, which the
+    constant alone did not.  -> [B * H, N] for `rows` = B * H rows."""
+    per_head = 1e-3 + 2.0 ** -9 * _d(proj_weight).reshape(num_heads, -1).abs().sum(1)
+    return per_head.repeat(rows // num_heads)[:, None]
+
+
 def chk__relation_attention_boxes_train(a, res):
     ref, s = _attention(a["q"], a["k"], a["v"], a["num_heads"], _boxes_bias64(a), a["mask"], a["scale"])
     lse = torch.logsumexp(s, -1).reshape(-1, s.shape[2])
-    return [_attn_cmp("out", res[0], ref), Cmp("lse", res[1].double() * math.log(2.0), lse, 1e-3)]
+    bound = boxes_lse_bound(a["proj_weight"], a["num_heads"], lse.shape[0]).expand_as(lse)
+    return [_attn_cmp("out", res[0], ref), Cmp("lse", res[1].double() * math.log(2.0), lse, bound)]
 
 
 def chk__relation_attention_boxes_backward(a, res):
@@ -862,7 +903,8 @@ def chk__relation_attention_boxes_backward(a, res):
     pairs = kink.any(0).any(0)                                                                        # [N, M]
     share = pairs.double().mean().reshape(1)
     full_rows = pairs.all(1).sum().double().reshape(1)
-    cmps = [Cmp(n, got, refs[n].reshape(got.shape), _attn_grad_bound(refs[n].reshape(got.shape))) for n, got in zip(("dq", "dk", "dv"), res[:3])]
+    cmps = [Cmp(n, got, refs[n].reshape(got.shape), _attn_grad_bound(refs[n].reshape(got.shape)) + (refs["rounding"][n].reshape(got.shape) if n in refs["rounding"] else 0.0))
+            for n, got in zip(("dq", "dk", "dv"), res[:3])]
     cmps.append(Cmp("grad_weight", res[3].reshape(H, -1), gw, _attn_grad_bound(gw) + allow_w))
     if res[4] is not None:
         cmps.append(Cmp("grad_bias", res[4].reshape(-1), gb, _attn_grad_bound(gb) + allow_b))

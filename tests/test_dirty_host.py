@@ -1,0 +1,202 @@
+"""tests/dirty.py on the CPU: the poison fills what it should with the byte it was given, leaves host tensors alone and restores
+torch on exit; and a scan of the package's source: every allocation there that yields uninitialised memory is a form the poison
+covers, reached through ``torch`` / a tensor at call time."""
+import ast
+import math
+import os
+
+import pytest
+import torch
+
+import dirty
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ANY = lambda t: True                                                          # "every tensor is a device tensor": the CPU path, forced
+
+
+# ------------------------------------------------------------------------------------------------------------ the helper
+def _expected(byte, dtype):
+    raw = torch.full((8,), byte, dtype=torch.uint8)
+    return raw.view(dtype)[0]
+
+
+@pytest.mark.parametrize("byte", dirty.PATTERNS)
+def test_every_covered_form_is_filled(byte):
+    like = torch.zeros(2, 3, 4, 5).contiguous(memory_format=torch.channels_last)
+    with dirty.poisoned(byte, ANY) as p:
+        made = {
+            "empty": torch.empty(3, 5),
+            "empty, shape as a tuple": torch.empty((7,), dtype=torch.bfloat16),
+            "empty_like": torch.empty_like(like),
+            "empty_like, dtype": torch.empty_like(like, dtype=torch.int32),
+            "empty_strided": torch.empty_strided((3, 4), (8, 1), dtype=torch.int64),         # gaps between the rows
+            "new_empty": like.new_empty(11, dtype=torch.bool),
+            "zeros-or-empty": (torch.zeros if byte > 255 else torch.empty)(6, dtype=torch.int32),
+            "a leaf that requires grad": torch.empty(4, requires_grad=True),
+        }
+        assert torch.empty(0).numel() == 0 and p.fills == len(made)                          # an empty tensor: nothing to fill
+    for name, t in made.items():
+        raw = torch.tensor([], dtype=torch.uint8).set_(t.untyped_storage())
+        assert raw.numel() >= t.numel() * t.element_size() and bool((raw == byte).all()), name
+        want = _expected(byte, t.dtype)
+        got = t.detach().flatten()
+        assert bool(torch.isnan(got).all()) if t.is_floating_point() and math.isnan(float(want)) else bool((got.view(torch.uint8) == byte).all()), name
+    assert made["empty_like"].is_contiguous(memory_format=torch.channels_last) and made["empty_strided"].stride() == (8, 1)
+    assert made["a leaf that requires grad"].requires_grad and made["a leaf that requires grad"].is_leaf
+
+
+def test_the_patterns_are_what_the_table_says():
+    with dirty.poisoned(0xFF, ANY):
+        assert bool(torch.isnan(torch.empty(5)).all()) and bool(torch.isnan(torch.empty(5, dtype=torch.bfloat16).float()).all())
+        assert torch.empty(5, dtype=torch.int32).tolist() == [-1] * 5 and torch.empty(5, dtype=torch.int64).tolist() == [-1] * 5
+        assert torch.empty(5, dtype=torch.bool).view(torch.uint8).tolist() == [255] * 5
+    with dirty.poisoned(0x42, ANY):
+        assert torch.empty(3).tolist() == pytest.approx([48.564706] * 3, rel=1e-6)
+        assert torch.empty(3, dtype=torch.bfloat16).float().tolist() == [48.5] * 3
+        assert torch.empty(3, dtype=torch.int32).tolist() == [1111638594] * 3
+        assert torch.empty(3, dtype=torch.int64).tolist() == [0x4242424242424242] * 3
+        assert bool(torch.empty(3, dtype=torch.bool).all())
+    with dirty.poisoned(0x00, ANY):
+        assert not torch.empty(9).any() and not torch.empty(9, dtype=torch.bool).any() and not torch.empty(9, dtype=torch.int64).any()
+
+
+def test_host_tensors_are_left_alone():
+    """The default predicate is ``tensor.is_cuda``: on this path nothing is a device tensor, nothing is filled."""
+    with dirty.poisoned(0xFF) as p:
+        a, b, c = torch.empty(64), torch.empty_like(torch.zeros(3)), torch.zeros(2).new_empty(5)
+        d = torch.empty_strided((2, 2), (2, 1))
+        assert p.fills == 0 and p.bytes == 0
+    assert all(t.device.type == "cpu" for t in (a, b, c, d))
+    # a predicate that tells "device" tensors by a property of the tensor: only those are filled
+    with dirty.poisoned(0xFF, lambda t: t.dtype == torch.float32) as p:
+        dev, host = torch.empty(16), torch.zeros(16, dtype=torch.int32).new_empty(16)
+        host.fill_(7)
+        assert p.fills == 1 and p.bytes == 64 and bool(torch.isnan(dev).all()) and host.tolist() == [7] * 16
+
+
+def test_everything_is_restored():
+    before = {(o.__name__, n): getattr(o, n) for o, n in dirty.COVERED}
+    assert "new_empty" not in vars(torch.Tensor)
+    with dirty.poisoned(0x42, ANY):
+        assert all(getattr(o, n) is not before[o.__name__, n] for o, n in dirty.COVERED)
+        assert all(getattr(o, n).__wrapped__ is before[o.__name__, n] for o, n in dirty.COVERED)
+    assert all(getattr(o, n) is before[o.__name__, n] for o, n in dirty.COVERED) and "new_empty" not in vars(torch.Tensor)
+    with pytest.raises(RuntimeError, match="inside"):
+        with dirty.poisoned(0x42, ANY):
+            raise RuntimeError("inside")
+    assert all(getattr(o, n) is before[o.__name__, n] for o, n in dirty.COVERED)
+    mp = pytest.MonkeyPatch()
+    p = dirty.poison(mp, 0xFF, ANY)                                           # the fixture style
+    assert bool(torch.isnan(torch.empty(3)).all()) and p.fills == 1
+    mp.undo()
+    assert all(getattr(o, n) is before[o.__name__, n] for o, n in dirty.COVERED)
+    with pytest.raises(ValueError):
+        dirty.Poison(256)
+
+
+# --------------------------------------------------------------------------------------------------------- the source scan
+# constructors and methods that yield (or re-expose) uninitialised memory without going through a covered form
+LEGACY = {"Tensor", "FloatTensor", "DoubleTensor", "HalfTensor", "BFloat16Tensor", "ByteTensor", "CharTensor", "ShortTensor", "IntTensor",
+          "LongTensor", "BoolTensor", "UntypedStorage", "TypedStorage", "FloatStorage", "ByteStorage"}
+UNCOVERED = {"resize_", "resize_as_", "set_", "new", "empty_permuted", "empty_quantized", "_empty_affine_quantized",
+             "_empty_per_channel_affine_quantized", "_resize_output_"}
+
+
+def _name(node):
+    """Dotted name of a Name / Attribute chain, '' for anything else."""
+    parts = []
+    while isinstance(node, ast.Attribute):
+        parts.append(node.attr)
+        node = node.value
+    return ".".join(reversed(parts + [node.id])) if isinstance(node, ast.Name) else ""
+
+
+def scan(source, filename="<source>"):
+    """-> a list of 'file:line: what' for every allocation of uninitialised memory the poison would miss."""
+    tree, found = ast.parse(source, filename), []
+    parent = {child: node for node in ast.walk(tree) for child in ast.iter_child_nodes(node)}
+
+    def flag(node, what):
+        found.append(f"{filename}:{node.lineno}: {what}")
+
+    def is_callee(node):
+        up = parent.get(node)
+        if isinstance(up, ast.IfExp) and node in (up.body, up.orelse):         # (torch.zeros if x else torch.empty)(...)
+            node, up = up, parent.get(up)
+        return isinstance(up, ast.Call) and up.func is node
+
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ImportFrom) and (node.module or "").split(".")[0] == "torch":
+            for alias in node.names:
+                if alias.name in dirty.COVERED_NAMES | UNCOVERED or alias.name == "*":
+                    flag(node, f"`from {node.module} import {alias.name}` binds the allocator before the poison can replace it")
+        elif isinstance(node, ast.Attribute):
+            if node.attr in UNCOVERED:
+                flag(node, f"`.{node.attr}` hands out uninitialised memory the poison does not cover")
+            elif node.attr in dirty.COVERED_NAMES:
+                if not is_callee(node):
+                    flag(node, f"`{_name(node) or node.attr}` is taken as a value, not called: an alias outlives the poison's patch")
+                elif node.attr != "new_empty" and _name(node) != f"torch.{node.attr}":
+                    flag(node, f"`{_name(node) or node.attr}(...)`: the covered form is `torch.{node.attr}(...)`")
+        if isinstance(node, ast.Call):
+            callee = _name(node.func)
+            if callee.split(".")[-1] in LEGACY and (callee.startswith("torch.") or callee in LEGACY):
+                flag(node, f"`{callee}(...)` is a legacy constructor: uninitialised when given sizes")
+            if callee.split(".")[-1] in dirty.COVERED_NAMES and any(k.arg == "out" for k in node.keywords):
+                flag(node, f"`{callee}(..., out=)` resizes a tensor the poison never sees")
+    return found
+
+
+def _package_sources():
+    top = os.path.join(ROOT, "relation_detr_amd")
+    for folder, _, files in sorted(os.walk(top)):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                yield os.path.join(folder, f)
+
+
+def test_every_uninitialised_allocation_of_the_package_is_a_covered_form():
+    found, allocations, files = [], 0, 0
+    for path in _package_sources():
+        with open(path) as f:
+            source = f.read()
+        rel = os.path.relpath(path, ROOT)
+        found += scan(source, rel)
+        allocations += sum(isinstance(n, ast.Attribute) and n.attr in dirty.COVERED_NAMES for n in ast.walk(ast.parse(source)))
+        files += 1
+    assert files >= 20 and allocations >= 100, (files, allocations)          # the scan did read the package
+    assert not found, "\n".join(found)
+
+
+SLIPS = {
+    "a legacy constructor": "import torch\ndef f(n):\n    return torch.Tensor(n)\n",
+    "a typed legacy constructor": "import torch\ndef f(n):\n    return torch.cuda.FloatTensor(n)\n",
+    "a legacy constructor by its bare name": "from torch import Tensor\ndef f(n):\n    return Tensor(n)\n",
+    "resize_": "import torch\ndef f(x, n):\n    return x.resize_(n)\n",
+    "resize_as_": "import torch\ndef f(x, y):\n    return x.resize_as_(y)\n",
+    "set_ on a storage": "import torch\ndef f(x, s):\n    return x.set_(s)\n",
+    "Tensor.new": "import torch\ndef f(x, n):\n    return x.new(n)\n",
+    "empty with out=": "import torch\ndef f(x, n):\n    return torch.empty(n, out=x)\n",
+    "empty_permuted": "import torch\ndef f(n):\n    return torch.empty_permuted((n, 2), (1, 0))\n",
+    "an imported allocator": "from torch import empty\ndef f(n):\n    return empty(n)\n",
+    "an aliased allocator": "import torch\n_alloc = torch.empty\ndef f(n):\n    return _alloc(n)\n",
+    "an allocator as a default argument": "import torch\ndef f(n, alloc=torch.empty_like):\n    return alloc(n)\n",
+    "an allocator through another name of torch": "import torch as th\ndef f(n):\n    return th.empty(n)\n",
+}
+FINE = {
+    "the covered forms": "import torch\ndef f(x, n, z):\n    a = torch.empty(n, device=x.device)\n    b = torch.empty_like(x)\n"
+                         "    c = torch.empty_strided((n,), (1,))\n    d = x.new_empty(n)\n    e = (torch.zeros if z else torch.empty)(n)\n"
+                         "    return a, b, c, d, e\n",
+    "Tensor as a type": "import torch\nfrom torch import Tensor\ndef f(x: Tensor) -> torch.Tensor:\n    return x if isinstance(x, torch.Tensor) else None\n",
+    "a variable called empty": "def f(xs):\n    empty = not xs\n    return empty\n",
+}
+
+
+@pytest.mark.parametrize("label", list(SLIPS))
+def test_the_scan_reports(label):
+    assert scan(SLIPS[label]), f"the scan let {label} pass"
+
+
+@pytest.mark.parametrize("label", list(FINE))
+def test_the_scan_accepts(label):
+    assert scan(FINE[label]) == []

@@ -163,6 +163,8 @@ def test_train_forward_is_the_inference_kernel_and_lse(rd, B, N, M, masked):
     err = (lse.double() - ref).abs()
     print(f"B {B} N {N} M {M} masked {masked}: max |lse - ref| {err.max().item():.3e}")
     assert not (err > 2.0 ** -7 * ref.abs() + 4e-3).any(), err.max().item()
+    import shadow
+    assert not (err > shadow.boxes_lse_bound(w, H, B * H).to(err.device)).any(), err.max().item()   # the form the shadow harness holds it to
 
 
 @pytest.mark.parametrize("masked", [False, True], ids=["kink", "kink+mask"])

@@ -84,37 +84,53 @@ def mixed_model():
     return options.apply(model, **dict.fromkeys(TRAIN_SWITCHES, True))
 
 
-def mixed_inputs():
+def mixed_inputs(batch=2, maps=MAPS, counts=(BOXES, 0), hard=()):
+    """Backbone maps [batch, c, h, w], the image mask and the targets (`counts` boxes per image).  The last image is padded right and
+    bottom; the images in `hard` so far that the coarsest level (the neck's extra one) keeps two valid rows and one valid column."""
     g = torch.Generator().manual_seed(23)
-    feats = [torch.randn(2, c, h, w, generator=g).to(DEV) for c, (h, w) in zip(IN_CHANNELS, MAPS)]
-    mask = torch.zeros(2, 8 * MAPS[0][0], 8 * MAPS[0][1], dtype=torch.bool)
-    mask[1, :, 700:] = True                                                     # the last image: padded right and bottom
-    mask[1, 450:, :] = True
-    labels = (torch.arange(BOXES) * (CLASSES - 1)) // (BOXES - 1)               # 0 .. 90
-    boxes = torch.cat((0.1 + 0.8 * torch.rand(BOXES, 2, generator=g), 0.03 + 0.3 * torch.rand(BOXES, 2, generator=g)), -1)
-    targets = [{"labels": labels.to(DEV), "boxes": boxes.to(DEV)},
-               {"labels": torch.zeros(0, dtype=torch.int64, device=DEV), "boxes": torch.zeros(0, 4, device=DEV)}]
+    feats = [torch.randn(batch, c, h, w, generator=g).to(DEV) for c, (h, w) in zip(IN_CHANNELS, maps)]
+    H, W = 8 * maps[0][0], 8 * maps[0][1]
+    mask = torch.zeros(batch, H, W, dtype=torch.bool)
+    mask[batch - 1, :, W * 7 // 8:] = True                                      # the last image: padded right and bottom
+    mask[batch - 1, H * 450 // 512:, :] = True
+    hc, wc = (maps[-1][0] + 1) // 2, (maps[-1][1] + 1) // 2                      # the extra level: a stride-2 3 x 3 convolution
+    for b in hard:                                                              # level pixel (y, x) reads mask[y H // hc, x W // wc]
+        mask[b, 2 * H // hc:, :] = True
+        mask[b, :, W // wc:] = True
+    targets = []
+    for n in counts:
+        labels = (torch.arange(n) * (CLASSES - 1)) // max(n - 1, 1)             # 0 .. 90
+        boxes = torch.cat((0.1 + 0.8 * torch.rand(n, 2, generator=g), 0.03 + 0.3 * torch.rand(n, 2, generator=g)), -1) if n else torch.zeros(0, 4)
+        targets.append({"labels": labels.to(DEV), "boxes": boxes.to(DEV)})
     return feats, mask.to(DEV), targets
 
 
 def test_shadow_mixed_precision_detector_two_steps(monkeypatch):
+    mixed_two_steps(monkeypatch, mixed_inputs(), MAPS, "mixed-precision detector, all six training switches, device matcher, two steps",
+                    "shadow_detector_mixed.txt")
+
+
+def mixed_two_steps(monkeypatch, inputs, maps, title, report_name):
+    """(a) on `inputs` = mixed_inputs(...) over the backbone maps `maps`: the two steps, then every assertion of the test."""
     from relation_detr_amd import denoising as dn
     from relation_detr_amd.criterion import MAX_ASSIGN
     from relation_detr_amd.optim import FusedAdamW, relation_param_groups, train_step
     model = mixed_model()
-    feats, mask, targets = mixed_inputs()
+    feats, mask, targets = inputs
+    counts = [int(t["labels"].numel()) for t in targets]
+    assert max(counts) == BOXES
     groups = dn.denoising_groups(DN_NUMS, BOXES)
     n_dn = 2 * groups * BOXES
     assert (groups, n_dn) == (5, 170) and (n_dn + QUERIES) % 8 and BOXES * 6 <= MAX_ASSIGN
-    S = sum(h * w for h, w in MAPS + ((8, 13),))
-    assert S >= 4096 and 2 * S >= 16384
+    S = sum(h * w for h, w in tuple(maps) + (((maps[-1][0] + 1) // 2, (maps[-1][1] + 1) // 2),))
+    assert S >= 4096 and len(counts) * S >= 16384
     opt = FusedAdamW(relation_param_groups(model, 1e-4), lr=1e-4, weight_decay=1e-4, fused=True)
     assert sum(len(g_["params"]) for g_ in opt.param_groups) == len(list(model.parameters()))
     sh = shadow.Shadow(monkeypatch)
     steps, started, unchanged = 2, time.perf_counter(), []
     for step in range(steps):
         before = {k: p.detach().clone() for k, p in model.named_parameters()}
-        noise = dn.cdn_noise(1234 + step, 2 * groups * BOXES, CLASSES, DEV)
+        noise = dn.cdn_noise(1234 + step, 2 * groups * sum(counts), CLASSES, DEV)
         with torch.autocast("cuda", dtype=torch.bfloat16):
             losses, norm = train_step(model, opt, feats, mask, None, targets, max_norm=0.1, noise=noise)
         torch.cuda.synchronize()
@@ -122,7 +138,7 @@ def test_shadow_mixed_precision_detector_two_steps(monkeypatch):
         unchanged += [(step + 1, k) for k, p in model.named_parameters() if torch.equal(p.detach(), before[k])]
         assert all(float(opt.state[p]["step"]) == step + 1 for p in model.parameters())
     print(f"two mixed-precision detector steps under the harness: {time.perf_counter() - started:.1f} s")
-    _report(sh, "mixed-precision detector, all six training switches, device matcher, two steps", "shadow_detector_mixed.txt")
+    _report(sh, title, report_name)
     assert not sh.errors, sorted(set(sh.errors))
     assert not unchanged, f"(step, parameter) the step left unchanged: {unchanged}"
     called = sh.called()
@@ -173,20 +189,27 @@ MIXED_OPS = STEP_OPS | AMP_OPS | {"criterion.assign_match", "ln_train.add_layer_
 
 
 # ------------------------------------------------------------------------------------------------------------------ (b), (c)
-def tiny_step(monkeypatch, fault=None):
-    """One fp32 step of tests/test_gpu_neck.py's tiny model (g12 maps, g10 targets) under the harness -> (harness, model)."""
+def tiny_inputs():
+    """tests/test_gpu_neck.py's inputs: the g12 maps and image mask, the g10 targets -> (maps, mask, targets)."""
+    g12, z = load_golden("g12_neck.npz"), load_golden("g10_criterion.npz")
+    targets = [{"labels": T(z[f"tgt.labels.{b}"]).to(DEV), "boxes": T(z[f"tgt.boxes.{b}"]).to(DEV)} for b in range(2)]
+    return [T(g12[f"x{i}"]).to(DEV) for i in range(3)], T(g12["img_mask"]).to(DEV), targets
+
+
+def tiny_step(monkeypatch, fault=None, inputs=None):
+    """One fp32 step of tests/test_gpu_neck.py's tiny model (`inputs`: tiny_inputs() unless given) under the harness
+    -> (harness, model, the parameters before the step)."""
     from relation_detr_amd import denoising as dn
     from relation_detr_amd.optim import FusedAdamW, relation_param_groups, train_step
     from test_denoising_host import C
     from test_gpu_neck import tiny_model
-    g12, z = load_golden("g12_neck.npz"), load_golden("g10_criterion.npz")
-    targets = [{"labels": T(z[f"tgt.labels.{b}"]).to(DEV), "boxes": T(z[f"tgt.boxes.{b}"]).to(DEV)} for b in range(2)]
-    feats, mask = [T(g12[f"x{i}"]).to(DEV) for i in range(3)], T(g12["img_mask"]).to(DEV)
+    feats, mask, targets = inputs or tiny_inputs()
+    counts = [int(t["labels"].numel()) for t in targets]
     model = tiny_model(True).train()
     opt = FusedAdamW(relation_param_groups(model, 1e-3), lr=1e-3, weight_decay=1e-4, fused=True)
     before = {k: p.detach().clone() for k, p in model.named_parameters()}
     sh = shadow.Shadow(monkeypatch, fault=fault)
-    noise = dn.cdn_noise(11, 2 * dn.denoising_groups(6, 3) * 5, C, DEV)
+    noise = dn.cdn_noise(11, 2 * dn.denoising_groups(6, max(counts)) * sum(counts), C, DEV)
     losses, norm = train_step(model, opt, feats, mask, None, targets, max_norm=0.1, noise=noise)
     torch.cuda.synchronize()
     assert len(losses) == 3 * (3 * 2 + 2) and bool(torch.isfinite(norm))   # 2 decoder layers: 8 sets x 3 losses
@@ -194,8 +217,13 @@ def tiny_step(monkeypatch, fault=None):
 
 
 def test_shadow_fp32_detector_step(monkeypatch):
-    sh, model, before = tiny_step(monkeypatch)
-    _report(sh, "fp32 detector step, defaults, scipy matcher", "shadow_detector_fp32.txt")
+    fp32_step(monkeypatch, None, "fp32 detector step, defaults, scipy matcher", "shadow_detector_fp32.txt")
+
+
+def fp32_step(monkeypatch, inputs, title, report_name):
+    """(b) on `inputs` (tiny_inputs() unless given): the step, then every assertion of the test."""
+    sh, model, before = tiny_step(monkeypatch, inputs=inputs)
+    _report(sh, title, report_name)
     assert not sh.errors, sorted(set(sh.errors))
     sh.assert_ok(FP32_OPS)
     assert max(_ratio_table(sh).values()) < 1.0

@@ -274,6 +274,13 @@ def test_shadow_all_training_routes_step(bench, monkeypatch, deterministic):
     finally:
         torch.use_deterministic_algorithms(was)
     _report(sh, f"mid-size bf16 training step, all six training switches ({'deterministic' if deterministic else 'atomic'})")
+    assert_all_training_routes(sh, net)
+
+
+def assert_all_training_routes(sh, net):
+    """What a bf16 training step with all six switches on has to show, whatever its shapes (tall enough for every route): no error,
+    every ratio below 1, the op set, the launch counts as the layer counts give them, a finite gradient for every parameter of the
+    encoder and the decoder."""
     assert not sh.errors, sorted(set(sh.errors))
     sh.assert_ok(TRAIN_ALL_OPS)
     assert max(_ratio_table(sh).values()) < 1.0

@@ -185,7 +185,11 @@ def test_attention_checkers(attn):
     _passes(fwd, attn["fwd"], (out, lse2))
     _passes(bwd, attn["bwd"], grads)
     assert "out" in _fails(fwd, attn["fwd"], (_scale_column(out), lse2), "out column scaled")[0][0]
-    assert "lse" in _fails(fwd, attn["fwd"], (out, lse2 + 2e-3 / math.log(2.0)), "lse shifted by 2e-3")[0][0]
+    # the log-sum-exp bound carries the scale of the projection (shadow.boxes_lse_bound): twice a row's bound fails, half of it passes
+    room = shadow.boxes_lse_bound(attn["fwd"]["proj_weight"], 8, lse2.shape[0]).float()
+    assert 1e-3 < float(room.min()) and float(room.max()) < 1e-3 + 2.0 ** -9 * 64 * float(attn["fwd"]["proj_weight"].abs().max()) + 1e-12
+    assert "lse" in _fails(fwd, attn["fwd"], (out, lse2 + 2 * room / math.log(2.0)), "lse shifted by twice its bound")[0][0]
+    _passes(fwd, attn["fwd"], (out, lse2 + 0.5 * room / math.log(2.0)))
     for i, name in enumerate(("dq", "dk", "dv")):
         sw = list(grads)
         sw[i] = torch.cat([_swap_blocks(grads[i][0])[None], grads[i][1:]])
@@ -262,6 +266,22 @@ def test_msda_checkers(msda):
     low = want.masked_fill(mask[..., None], 0).clone()
     low.view(torch.int16)[0, 0, 0] ^= 1                                     # one bit of one element
     _fails(relayout, a, low, "one ulp in one element")
+
+
+@pytest.mark.parametrize("junk", [math.nan, math.inf, -math.inf])
+def test_excluded_element_may_be_inaccurate_but_not_unwritten(junk):
+    """`keep` takes an element out of the comparison (a kink point of grad_loc): any finite value passes there, a NaN or inf the
+    reference lacks does not."""
+    ref, keep = torch.tensor([1.0, 2.0, 3.0, math.inf]), torch.tensor([True, False, True, False])
+    got = ref.clone()
+    got[1] = 1e9                                                            # excluded and finite: not looked at
+    assert shadow._compare(shadow.Cmp("x", got, ref, 1e-6, keep))[:3] == (0.0, 0, 2)
+    assert shadow._compare(shadow.Cmp("x", got, ref.nan_to_num(posinf=7.0), 1e-6, keep))[:2] == (math.inf, 1)   # inf the reference lacks
+    got[1] = junk
+    worst, failing, checked, where = shadow._compare(shadow.Cmp("x", got, ref, 1e-6, keep))
+    assert (worst, failing, checked) == (math.inf, 1, 2) and where.startswith("x[1]")
+    both = torch.tensor([math.nan, math.nan, 3.0, math.inf])                # NaN on both sides stays equal, kept or not
+    assert shadow._compare(shadow.Cmp("x", both.clone(), both, 1e-6, keep))[:2] == (0.0, 0)
 
 
 # ====================================================================================== the detector step's checkers
