@@ -978,6 +978,41 @@ typedef struct rdetr_image_desc {
 int rdetr_image_batch(const rdetr_image_desc *images, int B, int src_is_u8, int Hp, int Wp, const float *mean, const float *std,
                       int normalize, int out_bf16, int channels_last, void *out, void *mask, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The ResNet backbone's epilogues (csrc/backbone.hip; models/bricks/misc.py: FrozenBatchNorm2d, models/backbones/resnet.py): what
+ * follows each library convolution, in one read and one write.
+ *
+ * Tensors are [B, C, H, W], dense NCHW, or with channels_last = 1 the same tensor stored [B, H, W, C]; fp32 or bf16 by the entry's
+ * suffix, bases 16-byte aligned.  scale, shift: fp32 [C].  An NCHW plane whose H * W is no multiple of the vector width starts off
+ * the 16-byte grid; the kernels take its head and tail as scalars.  In channels-last C may be any size.
+ *
+ * rdetr_frozen_bn_act_*:  out = act(x * scale[c] + shift[c] (+ residual)).  fp32: one rounded multiply, one rounded add, one
+ *   rounded add of the residual, never contracted, so the result is torch's relu(x * s + b + r) bit for bit; bf16 computes in fp32 and
+ *   rounds once.  relu: 0 | 1, a NaN stays a NaN.  residual: NULL for none.  out == x (in place) is allowed; out overlapping x in any
+ *   other way, or overlapping residual, is RDETR_ERR_INVALID_ARG.
+ * rdetr_frozen_bn_act_backward_*:  from dy, the saved output y and scale: dx = (dy * [y > 0]) * scale[c] and, with dres != NULL,
+ *   dres = dy * [y > 0], in the same launch; relu = 0 makes the mask all ones (y may then be NULL).  fp32: autograd's result for
+ *   the operator sequence above, bit for bit.  dx == dy is allowed; dres overlapping dx, or either overlapping y, is
+ *   RDETR_ERR_INVALID_ARG.
+ * rdetr_stem_pool_*:  out = maxpool 3x3 / stride 2 / padding 1 of relu(x * scale[c] + shift[c]); x [B, C, H, W], out [B, C,
+ *   (H - 1) / 2 + 1, (W - 1) / 2 + 1], the same arithmetic rule.  Padding never wins; a window that holds a NaN gives NaN.  out must
+ *   not overlap x.
+ *
+ * RDETR_ERR_INVALID_ARG: a NULL required pointer, B, C, H or W <= 0, a flag outside {0, 1}, a forbidden overlap.
+ * RDETR_ERR_UNSUPPORTED: B * C * H * W >= 2^31, a base off the 16-byte grid.  All checks precede any HIP call. */
+int rdetr_frozen_bn_act_f32(const void *x, const float *scale, const float *shift, const void *residual, int B, int C, int H, int W,
+                            int channels_last, int relu, void *out, void *stream);
+int rdetr_frozen_bn_act_bf16(const void *x, const float *scale, const float *shift, const void *residual, int B, int C, int H, int W,
+                             int channels_last, int relu, void *out, void *stream);
+int rdetr_frozen_bn_act_backward_f32(const void *dy, const void *y, const float *scale, int B, int C, int H, int W, int channels_last,
+                                     int relu, void *dx, void *dres, void *stream);
+int rdetr_frozen_bn_act_backward_bf16(const void *dy, const void *y, const float *scale, int B, int C, int H, int W, int channels_last,
+                                      int relu, void *dx, void *dres, void *stream);
+int rdetr_stem_pool_f32(const void *x, const float *scale, const float *shift, int B, int C, int H, int W, int channels_last, void *out,
+                        void *stream);
+int rdetr_stem_pool_bf16(const void *x, const float *scale, const float *shift, int B, int C, int H, int W, int channels_last, void *out,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,11 +17,12 @@ from .amp_train import AddLayerNormMixedFunction, FeedForwardMixedFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
 from .criterion import RelationCriterion, SetLossFunction, assign_match, hungarian_match, match_cost, set_loss
 from .denoising import CdnQueryFunction, GenerateCDNQueries, cdn_noise, cdn_queries, denoising_mask
-from .detector import RelationDETR, RelationDETRHead, RelationDETRWithBackbone
+from .detector import RelationDETR, RelationDETRHead, RelationDETRWithBackbone, relation_detr_r50
 from .neck import (ChannelMapper, GroupNormLevelsFunction, PositionEmbeddingSine, PyramidBuilder, group_norm_levels, pyramid_masks,
                    pyramid_sine_pos)
 from .optim import FusedAdamW, relation_param_groups, train_step
 from .frontend import ImageBatch, ImagePreprocessor, batch_images, resized_size
+from .backbones import FrozenBatchNorm2d, ResNet, ResNetBackbone
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -39,4 +40,5 @@ __all__ = [
     "ChannelMapper", "PositionEmbeddingSine", "PyramidBuilder", "RelationDETR", "GroupNormLevelsFunction", "group_norm_levels",
     "pyramid_masks", "pyramid_sine_pos",
     "ImageBatch", "ImagePreprocessor", "batch_images", "resized_size", "RelationDETRWithBackbone",
+    "FrozenBatchNorm2d", "ResNet", "ResNetBackbone", "relation_detr_r50",
 ]

@@ -84,7 +84,8 @@ class RelationDETRWithBackbone(RelationDETR):
     """``forward(images, targets=None, noise=None)``, the reference's ``RelationDETR.forward(images, targets)``: ``images`` a list of
     ``[3, h, w]`` tensors (eval: uint8 or float in [0, 1], any sizes; training: augmented, float, normalised), ``targets`` with
     ``boxes`` in xyxy pixels.  ``preprocessor`` (``frontend.ImagePreprocessor``) makes the batch, the mask and the prepared targets,
-    ``backbone`` -- the caller's module -- maps ``batch.tensors`` to the feature maps ``RelationDETR.forward`` takes.
+    ``backbone`` -- ``backbones.ResNetBackbone`` or the caller's module -- maps ``batch.tensors`` to the feature maps
+    ``RelationDETR.forward`` takes.  ``relation_detr_r50`` assembles the reference's R50 configuration.
 
     Training mode returns the loss dict.  Eval mode returns ``(detections, tensor)``: ``tensor`` is ``select_detections``' ``[B, k, 6]``
     = (x1, y1, x2, y2, score, label) in pixels of the ORIGINAL images, ``detections`` the reference's list of
@@ -113,3 +114,29 @@ class RelationDETRWithBackbone(RelationDETR):
         sizes = original_sizes.to(device=logits.device, dtype=torch.int64)
         dets = select_detections(logits.float(), boxes.float(), sizes, self.num_select)
         return [{"scores": d[:, 4], "labels": d[:, 5].to(torch.int64), "boxes": d[:, :4]} for d in dets], dets
+
+
+def relation_detr_r50(num_classes: int = 91, weights=None, num_queries: int = 900, hybrid_num_proposals: int = 1500, hybrid_assign: int = 6,
+                      enc_layers: int = 6, dec_layers: int = 6, d_ffn: int = 2048, denoising_nums: int = 100, min_size: int = 800,
+                      max_size: int = 1333, num_select: int = 300, fused: bool = True, **transformer_kwargs) -> RelationDETRWithBackbone:
+    """``configs/relation_detr/relation_detr_resnet50_800_1333.py`` from this package's parts: ``ResNetBackbone("resnet50",
+    return_indices=(1, 2, 3), freeze_indices=(0,))`` with ``FrozenBatchNorm2d``, a four-level ``ChannelMapper`` to 256 channels, the
+    normalised sine position encoding with offset -0.5, the 6 + 6 layer transformer, the hybrid criterion, 100 denoising pairs and
+    the 800 / 1333 front end.  ``weights``: the backbone's state dict or a local path (``ResNetBackbone``'s argument).  The size
+    arguments are there for reduced models; ``transformer_kwargs`` go to ``build_relation_transformer``."""
+    from .backbones import ResNetBackbone
+    from .frontend import ImagePreprocessor
+    from .neck import ChannelMapper, PositionEmbeddingSine
+    from .transformer import build_relation_transformer
+    embed_dim, levels = 256, 4
+    backbone = ResNetBackbone("resnet50", weights=weights, return_indices=(1, 2, 3), freeze_indices=(0,), fused=fused)
+    transformer = build_relation_transformer(num_classes=num_classes, embed_dim=embed_dim, d_ffn=d_ffn, num_levels=levels,
+                                             enc_layers=enc_layers, dec_layers=dec_layers, num_queries=num_queries,
+                                             hybrid_num_proposals=hybrid_num_proposals, **transformer_kwargs)
+    return RelationDETRWithBackbone(
+        backbone, ChannelMapper(backbone.num_channels, embed_dim, levels, fused=fused),
+        PositionEmbeddingSine(embed_dim // 2, 10000, True, offset=-0.5, fused=fused), transformer,
+        RelationCriterion(num_classes, hybrid_assign=hybrid_assign, fused=fused),
+        GenerateCDNQueries(num_queries=num_queries, num_classes=num_classes, label_embed_dim=embed_dim, denoising_nums=denoising_nums,
+                           fused=fused),
+        ImagePreprocessor(min_size, max_size, fused=fused), num_select)
