@@ -112,3 +112,42 @@ def torch_route_step(opt, rows, max_norm, dtype):
         s = route.state.get(q) or {}
         out.append((q.detach(), s.get("exp_avg"), s.get("exp_avg_sq"), q.grad))
     return norm, out
+
+
+# the backbone epilogues' references and bounds (tests/test_gpu_backbone.py and the shadow harness, tests/shadow.py): one copy
+def torch_bn_act(x, s, h, r, relu):
+    """The reference's passes, one operator each."""
+    y = x * s.reshape(1, -1, 1, 1)
+    y = y + h.reshape(1, -1, 1, 1)
+    if r is not None:
+        y = y + r
+    return torch.relu(y) if relu else y
+
+
+def torch_stem(x, s, h):
+    return torch.nn.functional.max_pool2d(torch.relu(x * s.reshape(1, -1, 1, 1) + h.reshape(1, -1, 1, 1)), 3, 2, 1)
+
+
+def bf16_slack(x, s, h, r):
+    s4, h4 = s.double().reshape(1, -1, 1, 1), h.double().reshape(1, -1, 1, 1)
+    return 2.0 ** -20 * ((x.double() * s4).abs() + h4.abs() + (r.double().abs() if r is not None else 0.0))
+
+
+# the images of the detector steps that start at the front end (tests/test_gpu_shadow_detector.py (d), (e), (f), tests/test_gpu_dirty_shapes.py
+# T4); tests/test_shadow_train_host.py checks on the CPU that the uint8 batch is well-posed under the near-tie rule
+DETECTOR_BATCH = (160, 224)                       # the padded batch: stem 80 x 112, pool 40 x 56, stages 20 x 28, 10 x 14, 5 x 7, extra level 3 x 4
+DETECTOR_FLOAT_SIZES = ((160, 200), (131, 224), (50, 70))          # the last: 3,500 of 35,840 pixels, the rest padding
+DETECTOR_UINT8_SIZES = ((211, 300), (100, 400), (333, 410))        # resized to (150, 213), (56, 224), (150, 184) by min_size / max_size
+DETECTOR_RESIZE = (150, 224)                      # ImagePreprocessor's min_size, max_size for the uint8 images
+
+
+def detector_float_images():
+    """Three augmented-and-normalised training images, CPU float32."""
+    g = torch.Generator().manual_seed(61)
+    return [torch.randn(3, h, w, generator=g) for h, w in DETECTOR_FLOAT_SIZES]
+
+
+def detector_uint8_images():
+    """Three eval images of ragged sizes, CPU uint8."""
+    g = torch.Generator().manual_seed(62)
+    return [torch.randint(0, 256, (3, h, w), dtype=torch.uint8, generator=g) for h, w in DETECTOR_UINT8_SIZES]

@@ -1,9 +1,13 @@
 """Shadow checks of every kernel launch on a forward (or training step) of the stack.
 
-``Shadow(monkeypatch)`` replaces the module-level functions of ``relation_detr_amd.ops`` with wrappers, and those of the nine
+``Shadow(monkeypatch)`` replaces the module-level functions of ``relation_detr_amd.ops`` with wrappers, and those of the eleven
 modules that call the library themselves: the training routes ``ffn_train``, ``ln_train``, ``attn_rel_train``, ``msda_train_hm`` and
-``amp_train``, and the rest of a detector's training step, ``neck``, ``denoising``, ``criterion`` and ``optim`` (there also the two
-launching methods of ``FusedAdamW``, patched on the class).  Every call
+``amp_train``, the rest of a detector's training step, ``neck``, ``denoising``, ``criterion`` and ``optim`` (there also the two
+launching methods of ``FusedAdamW``, patched on the class), and what runs in front of the neck, in the subpackages:
+``backbones.epilogue`` and ``frontend.images`` (TRAIN_MODULES names a module by its dotted path below the package, and that path
+starts the op name of its records).  A wrapper is installed in the defining module AND wherever another module of the package holds
+the same function object as a global: backbones/resnet.py binds ``stem_bn_relu_maxpool`` by name, and the ``__init__`` files re-export
+entries; tests/test_shadow_complete.py holds from the source that every such binding is patched.  Every call
 site in transformer.py, ms_deform_attn.py, self_attn.py and relation.py looks the former up as ``ops.<name>``; the autograd
 Functions in ops.py and in the training modules reach their entries through their own module's globals, so a wrapper sees every
 launch of the stack, forward or training step, whichever opt-in training route is on.  A wrapper copies the tensor
@@ -122,6 +126,20 @@ profiles/r23/ has the two report tables of the detector step (mixed precision wi
 ratio below 1.  Three bounds that the composed step exceeded changed their FORM, in the unit test and here together, each for a scale the
 earlier form lacked: relation_bias (relation_bias_bound), bias_softmax_ (bias_softmax_bound) and criterion.match_cost (match_cost_scale).
 
+From the images (cases (d), (e), (f) of tests/test_gpu_shadow_detector.py and T4 of tests/test_gpu_dirty_shapes.py; the operands are the
+wrapper's copies, so an in-place ``frozen_bn_act_forward(x, ..., out=x)`` is checked against what x held before the launch):
+
+  backbones.epilogue.frozen_bn_act_forward   fp32: exact, x * s, + shift, + residual, relu as separate fp32 torch operators;     test_gpu_backbone (check_forward, bf16_slack)
+                                  bf16: 2^-8 |ref| + 2^-20 (|x s| + |shift| + |res|) against float64
+  backbones.epilogue.frozen_bn_act_backward  the mask from the y the call was handed: dres = dy where not (y <= 0), else 0, exact;   test_gpu_backbone::test_frozen_bn_act_backward
+                                  dx = dres * s, fp32 exact (torch's fp32 product), bf16 2^-8 |ref|; dres None exactly when not asked for
+  backbones.epilogue.stem_bn_relu_maxpool    fp32: exact, max_pool2d(relu(x * s + h), 3, 2, 1); bf16: 2^-8 |ref| + the forward's slack   test_gpu_backbone::test_stem_pool
+                                  max-pooled
+  frontend.images.batch_images    mask, sizes and padding (+0 to the bit) exact; uint8 sources by the near-tie rule (exact off the ties, one   test_gpu_images (check_batch),
+                                  of three neighbouring table values on them, at most NEAR_TIE_SHARE = 2 % of the batch near ties or the call   test_images_host (the float64 filter,
+                                  fails); float sources max(4 e32, 2^-20 max(1, |ref|)); copies exact; bf16 the rounding of the fp32 value       the near-tie rule)
+profiles/r28/ has the report tables of those cases, every ratio below 1; no bound changed.
+
 Elements a checker excludes (``Cmp.keep``: the kink points of the sampling-location gradients, the dead columns of a cost table) may
 be inaccurate, never unwritten: a NaN or an infinity there that the reference lacks fails the record like any other element.
 tests/test_gpu_dirty_shapes.py runs the harness at small ragged shapes with every uninitialised allocation filled with 0x00, 0xFF
@@ -223,7 +241,7 @@ def _compare(c: Cmp):
     if ratio.numel() == 0:
         return 0.0, 0, 0, c.label
     flat = int(torch.argmax(ratio).item())
-    worst = float(ratio.view(-1)[flat].item())
+    worst = float(ratio.reshape(-1)[flat].item())              # reshape: a channels-last result is not viewable flat
     failing = int((ratio > 1).sum().item())
     idx = []
     for s in reversed(ratio.shape):
@@ -776,19 +794,32 @@ HOST_ONLY = frozenset({
 
 
 # ------------------------------------------------------------------------------ training entries outside ops.py
-TRAIN_MODULES = ("ffn_train", "ln_train", "attn_rel_train", "msda_train_hm", "amp_train", "neck", "denoising", "criterion", "optim")
-TRAIN_CLASSES = {"optim": ("FusedAdamW",)}       # classes whose methods are classified like module-level functions ("module.Class.method")
+# modules of the package, dotted below it ("backbones.epilogue" is relation_detr_amd/backbones/epilogue.py)
+TRAIN_MODULES = ("ffn_train", "ln_train", "attn_rel_train", "msda_train_hm", "amp_train", "neck", "denoising", "criterion", "optim",
+                 "backbones.epilogue", "frontend.images")
+# classes whose methods (static ones too) are classified like module-level functions ("module.Class.method")
+TRAIN_CLASSES = {"optim": ("FusedAdamW",), "backbones.epilogue": ("FrozenBNActFunction",), "frontend.images": ("ImagePreprocessor",)}
+PACKAGE = "relation_detr_amd"
 LN_EPS = 1e-5                    # add_layer_norm_backward takes no eps: every norm of the network keeps nn.LayerNorm's default
 TAU = 8e-3                       # |pre-activation relation bias| below which the bf16 sine features may switch the ReLU branch
 
 
 def train_functions(module) -> List[str]:
     """Every module-level function defined in one of the training modules, as "module.function"."""
-    short = module.__name__.rsplit(".", 1)[-1]
+    short = module_key(module)
     names = [f"{short}.{n}" for n, f in vars(module).items() if inspect.isfunction(f) and f.__module__ == module.__name__]
     for cls in TRAIN_CLASSES.get(short, ()):                   # and the methods of the classes named there, "module.Class.method"
-        names += [f"{short}.{cls}.{n}" for n, f in vars(getattr(module, cls)).items() if inspect.isfunction(f) and f.__module__ == module.__name__]
+        for n, f in vars(getattr(module, cls)).items():
+            f = f.__func__ if isinstance(f, (staticmethod, classmethod)) else f
+            if inspect.isfunction(f) and f.__module__ == module.__name__:
+                names.append(f"{short}.{cls}.{n}")
     return sorted(names)
+
+
+def module_key(module) -> str:
+    """relation_detr_amd.backbones.epilogue -> "backbones.epilogue": the module's name below the package."""
+    assert module.__name__.startswith(PACKAGE + "."), module.__name__
+    return module.__name__[len(PACKAGE) + 1:]
 
 
 def _bf16_form(ref):
@@ -1345,6 +1376,164 @@ def chk_step_fused(a, res):
 
 chk_step_fused.snapshot = _optim_snapshot
 
+
+# -- the backbone's epilogues (tests/test_gpu_backbone.py): the operands are the COPIES, so an in-place call (out is x) is checked
+#    against what x held before the launch
+def _present(label, got, wanted):
+    """One exact element: a result that is there (1) or None (0), against whether the call asked for it."""
+    return Cmp(label, torch.tensor([0.0 if got is None else 1.0], dtype=F64), torch.tensor([1.0 if wanted else 0.0], dtype=F64))
+
+
+def _epilogue_operands(a):
+    x, r = a["x"], a["residual"]
+    return x, a["scale"], a["shift"], (None if r is None else r.to(x.dtype))      # the entry converts the residual to x's dtype
+
+
+def chk_frozen_bn_act_forward(a, res):
+    """fp32: x * s, + shift, + residual, relu as separate fp32 torch operators, exact.  bf16: float64 of the same, within
+    2^-8 |ref| + 2^-20 (|x s| + |shift| + |res|) (test_gpu_backbone.check_forward)."""
+    from helpers import bf16_slack, torch_bn_act
+    x, s, h, r = _epilogue_operands(a)
+    relu = bool(a["relu"])
+    if x.dtype == F32:
+        return [Cmp("out", res, torch_bn_act(x, s, h, r, relu))]
+    ref = torch_bn_act(x.double(), s.double(), h.double(), None if r is None else r.double(), relu)
+    return [Cmp("out", res, ref, 2.0 ** -8 * ref.abs() + bf16_slack(x, s, h, r))]
+
+
+def chk_frozen_bn_act_backward(a, res):
+    """What autograd makes of the operator sequence, from the y the call was handed: relu's backward passes dy where not (y <= 0)
+    and writes 0 elsewhere, the residual's gradient is that masked dy, x's is the masked dy times s.  fp32: both as fp32 torch
+    operators, exact.  bf16: dx within 2^-8 |ref| of the float64 product, dres the masked dy exactly
+    (test_gpu_backbone.test_frozen_bn_act_backward).  dres is None exactly when it was not asked for."""
+    dy, y, s, relu = a["dy"], a["y"], a["scale"], bool(a["relu"])
+    dx, dres = res
+    masked = torch.where(y <= 0, torch.zeros_like(dy), dy) if relu else dy
+    cmps = [_present("dres_returned", dres, a["want_dres"])]
+    if dy.dtype == F32:
+        cmps.append(Cmp("dx", dx, masked * s.reshape(1, -1, 1, 1)))
+    else:
+        ref = masked.double() * s.double().reshape(1, -1, 1, 1)
+        cmps.append(Cmp("dx", dx, ref, 2.0 ** -8 * ref.abs()))
+    if dres is not None:
+        cmps.append(Cmp("dres", dres, masked))
+    return cmps
+
+
+def chk_stem_bn_relu_maxpool(a, res):
+    """fp32: max_pool2d(relu(x * s + h), 3, 2, 1) in fp32 torch operators, exact.  bf16: float64 of the same, within 2^-8 |ref| + the
+    forward's slack max-pooled (test_gpu_backbone.test_stem_pool)."""
+    from helpers import bf16_slack, torch_stem
+    x, s, h = a["x"], a["scale"], a["shift"]
+    if x.dtype == F32:
+        return [Cmp("out", res, torch_stem(x, s, h))]
+    ref = torch_stem(x.double(), s.double(), h.double())
+    return [Cmp("out", res, ref, 2.0 ** -8 * ref.abs() + F.max_pool2d(bf16_slack(x, s, h, None), 3, 2, 1))]
+
+
+# -- the image front end (tests/test_gpu_images.check_batch, with the float64 filter and the near-tie rule of tests/test_images_host.py)
+def _frontend():
+    from relation_detr_amd.frontend import images
+    return images
+
+
+def _batch_images_operands(a):
+    """(images, sizes) as batch_images forms them, or None where it raises before it looks at the kernel's conditions."""
+    images = a["images"]
+    images = list(images.unbind(0)) if torch.is_tensor(images) else list(images)
+    if not all(torch.is_tensor(im) and im.dim() >= 2 for im in images):
+        return images, None
+    sizes = [(int(im.shape[-2]), int(im.shape[-1])) for im in images] if a["sizes"] is None else [(int(s[0]), int(s[1])) for s in a["sizes"]]
+    return images, (sizes if len(sizes) == len(images) and a["dtype"] in (F32, BF16) else None)
+
+
+def _batch_images_applies(a):
+    images, sizes = _batch_images_operands(a)
+    return sizes is not None and _frontend()._kernel_takes(images, sizes, a["size_divisible"], a["normalize"]) is None
+
+
+def _normalised(values, mean, std):
+    """(values - mean) / std per channel with torch's two in-place fp32 operations (ImagePreprocessor.batch_torch); values [3, ...] fp32."""
+    shape = (3,) + (1,) * (values.dim() - 1)
+    return values.clone().sub_(torch.tensor(mean, dtype=F32).view(shape)).div_(torch.tensor(std, dtype=F32).view(shape))
+
+
+def _resize64(image, oh, ow):
+    """test_images_host.resize64, the exact antialias filter in float64, as two matrix products (its three-operand einsum takes
+    seconds at 300 x 400 pixels)."""
+    from test_images_host import filter_matrix
+    x = image.astype("float64")
+    return filter_matrix(x.shape[1], oh) @ x @ filter_matrix(x.shape[2], ow).T
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32 if t.dtype == F32 else torch.int16)
+
+
+def chk_batch_images(a, res):
+    """Every element of the batch, the mask and the two size tables.  The mask, the sizes and the padding (+0 to the bit) exact.  The
+    valid region per image, ``got`` against the float64 filter v64 = resize64(source):
+      uint8 source   off the near ties the table value (float(rint(v64)) / 255 - mean) / std, exact; on them one of the three
+                     neighbouring table values; near ties above NEAR_TIE_SHARE of the batch's valid values fail the call as ill-posed
+      float source   resized: within max(4 e32, 2^-20 max(1, |ref|)) of ref = (v64 - mean) / std (v64 itself without normalisation);
+                     not resized: the torch route's fp32 value, exact (a copy without normalisation)
+    A bf16 batch is the rounding of the fp32 value (tests/test_gpu_images.py): exact wherever the fp32 value is; for a resized float
+    source, whose fp32 value f is only known to lie in [ref - b, ref + b], rounding is monotonic, so got lies in
+    [bf16(ref - b), bf16(ref + b)]."""
+    import numpy as np
+    from test_images_host import NEAR_TIE_SHARE, interpolate_error, near_tie
+    resize64 = _resize64
+    images, sizes = _batch_images_operands(a)
+    mean, std, normalize, dtype = tuple(a["mean"]), tuple(a["std"]), bool(a["normalize"]), a["dtype"]
+    Hp, Wp = _frontend().batched_size(sizes, a["size_divisible"])
+    B = len(images)
+    tensors = res.tensors.detach().cpu()
+    want_mask = torch.ones(B, Hp, Wp, dtype=torch.bool)
+    for i, (oh, ow) in enumerate(sizes):
+        want_mask[i, :oh, :ow] = False
+    original = [[int(im.shape[-2]), int(im.shape[-1])] for im in images]
+    cmps = [Cmp("mask", res.mask.detach().cpu().to(torch.uint8), want_mask.to(torch.uint8)),
+            Cmp("image_sizes", res.image_sizes, torch.tensor(sizes, dtype=torch.int64).reshape(B, 2)),
+            Cmp("original_sizes", res.original_sizes, torch.tensor(original, dtype=torch.int64).reshape(B, 2))]
+    cmps.append(Cmp("batch_dtype", torch.tensor([float(tensors.dtype == dtype)], dtype=F64), torch.ones(1, dtype=F64)))
+    if tuple(tensors.shape) != (B, 3, Hp, Wp) or tensors.dtype != dtype:
+        return cmps + [Cmp("batch", tensors, torch.zeros(B, 3, Hp, Wp, dtype=F64))]
+    pad = want_mask[:, None].expand(B, 3, Hp, Wp)
+    cmps.append(Cmp("padding_bits", torch.where(pad, _bits(tensors), torch.zeros((), dtype=_bits(tensors).dtype)), torch.zeros(B, 3, Hp, Wp, dtype=F64)))
+    n_near = n_all = 0
+    for i, (im, (oh, ow)) in enumerate(zip(images, sizes)):
+        got = tensors[i, :, :oh, :ow]
+        src = im.detach().cpu()
+        copied = (oh, ow) == tuple(src.shape[-2:])
+        if src.dtype == torch.uint8:
+            v64 = resize64(src.numpy(), oh, ow)
+            q64, near = near_tie(v64, interpolate_error(src.numpy(), v64))
+            table = _normalised(torch.arange(256, dtype=F32).view(1, 256).repeat(3, 1) / 255, mean, std).to(dtype)
+            q, near, rows = torch.from_numpy(q64).long(), torch.from_numpy(near), torch.arange(3).view(3, 1, 1)
+            cmps.append(Cmp(f"image{i}", got, table[rows, q], keep=~near))
+            if bool(near.any()):
+                ok = (got == table[rows, q]) | (got == table[rows, (q - 1).clamp(0, 255)]) | (got == table[rows, (q + 1).clamp(0, 255)])
+                cmps.append(Cmp(f"image{i}_near_ties", ok[near].double(), torch.ones(int(near.sum()), dtype=F64)))
+            n_near, n_all = n_near + int(near.sum()), n_all + near.numel()
+        elif copied:
+            cmps.append(Cmp(f"image{i}", got, (_normalised(src, mean, std) if normalize else src).to(dtype)))
+        else:
+            v64 = resize64(src.numpy(), oh, ow)
+            e32 = interpolate_error(src.numpy(), v64)
+            ref = (v64 - np.array(mean).reshape(3, 1, 1)) / np.array(std).reshape(3, 1, 1) if normalize else v64
+            ref = torch.from_numpy(ref)
+            bound = torch.clamp(2.0 ** -20 * ref.abs().clamp(min=1.0), min=4.0 * e32)
+            if dtype == BF16:
+                lo, hi = (ref - bound).float().to(BF16).double(), (ref + bound).float().to(BF16).double()
+                ref, bound = (lo + hi) / 2, (hi - lo) / 2
+            cmps.append(Cmp(f"image{i}", got, ref, bound))
+    if n_all:
+        cmps.append(Cmp("near_tie_share", torch.tensor([float(n_near)], dtype=F64), torch.zeros(1, dtype=F64), NEAR_TIE_SHARE * n_all, gate=True))
+    return cmps
+
+
+chk_batch_images.applies = _batch_images_applies
+
 # ------------------------------------------------------------------------------------------ every entry outside ops.py, one table
 TRAIN_ENTRIES: Dict[str, Callable] = {
     "ffn_train.ffn_k256_train": chk_ffn_k256_train,
@@ -1372,6 +1561,10 @@ TRAIN_ENTRIES: Dict[str, Callable] = {
     "criterion.set_loss_forward": chk_set_loss_forward,
     "optim.FusedAdamW._clip_fused": chk_clip_fused,
     "optim.FusedAdamW._step_fused": chk_step_fused,
+    "backbones.epilogue.frozen_bn_act_forward": chk_frozen_bn_act_forward,
+    "backbones.epilogue.frozen_bn_act_backward": chk_frozen_bn_act_backward,
+    "backbones.epilogue.stem_bn_relu_maxpool": chk_stem_bn_relu_maxpool,
+    "frontend.images.batch_images": chk_batch_images,
 }
 
 # the rest of the four training modules: routing predicates and argument helpers that launch nothing; ffn_train._pack, which launches a
@@ -1397,10 +1590,24 @@ TRAIN_HOST_ONLY = frozenset({
     "criterion._check_stack", "criterion.hungarian_match", "criterion._dn_groups", "criterion.set_loss", "criterion._layer_keys",
     "optim.build_chunk_map", "optim.step_scalars", "optim.fused_refusal", "optim.relation_param_groups", "optim.train_step",
     "optim.FusedAdamW.__init__", "optim.FusedAdamW.add_param_group", "optim.FusedAdamW._params", "optim.FusedAdamW._on_fused_route",
-    "optim.FusedAdamW._first_param", "optim.FusedAdamW._check_flags", "optim.FusedAdamW._check_groups", "optim.FusedAdamW._init_state",
+    "optim.FusedAdamW._first_param", "optim.FusedAdamW._grad_of", "optim.FusedAdamW._check_flags", "optim.FusedAdamW._check_groups", "optim.FusedAdamW._init_state",
     "optim.FusedAdamW._clip_torch", "optim.FusedAdamW._step_torch", "optim.FusedAdamW._gather", "optim.FusedAdamW._group_keys",
     "optim.FusedAdamW._build_tables", "optim.FusedAdamW._prepare", "optim.FusedAdamW._prepared_still_holds",
     "optim.FusedAdamW.clip_grad_norm_", "optim.FusedAdamW.step", "optim.FusedAdamW.load_state_dict",
+    # the backbone's epilogues: layout and argument helpers, and the differentiable wrapper with its autograd Function, which reach the
+    # two checked entries through the module's own globals
+    "backbones.epilogue._need_device", "backbones.epilogue._channels_last", "backbones.epilogue._dense", "backbones.epilogue._constants",
+    "backbones.epilogue._shape", "backbones.epilogue._stream", "backbones.epilogue.frozen_bn_act",
+    "backbones.epilogue.FrozenBNActFunction.forward", "backbones.epilogue.FrozenBNActFunction.backward",
+    # the image front end: the size rules, the kernel's conditions, the torch route (the reference of the host test), the targets, and
+    # every method of the module, whose one launching call is the checked batch_images
+    "frontend.images.resized_size", "frontend.images._resize_bounds", "frontend.images.batched_size", "frontend.images._kernel_takes",
+    "frontend.images.resize_image", "frontend.images.check_boxes", "frontend.images.prepare_targets",
+    "frontend.images.ImagePreprocessor.__init__", "frontend.images.ImagePreprocessor.target_sizes",
+    "frontend.images.ImagePreprocessor.takes_fused_route", "frontend.images.ImagePreprocessor.batch_torch",
+    "frontend.images.ImagePreprocessor.batch_fused", "frontend.images.ImagePreprocessor._targets",
+    "frontend.images.ImagePreprocessor.forward_torch", "frontend.images.ImagePreprocessor.forward_fused",
+    "frontend.images.ImagePreprocessor.forward",
 })
 
 
@@ -1416,6 +1623,36 @@ LAUNCH_INSIDE_ENTRY = frozenset({
 
 
 # ----------------------------------------------------------------------------------------------------------------- harness
+def patch_targets():
+    """(owner, attribute, key, entries, host-only set) of every function the harness classifies: the functions of ops, and of every
+    module of TRAIN_MODULES with the methods of its TRAIN_CLASSES (owner: the class)."""
+    import importlib
+    ops = importlib.import_module(PACKAGE + ".ops")
+    targets = [(ops, name, name, KERNEL_ENTRIES, HOST_ONLY) for name in ops_functions(ops)]
+    for short in TRAIN_MODULES:
+        module = importlib.import_module(f"{PACKAGE}.{short}")
+        for key in train_functions(module):
+            *owners, attr = key[len(short) + 1:].split(".")
+            owner = module
+            for name in owners:                                    # "module.Class.method": patched on the class
+                owner = getattr(owner, name)
+            targets.append((owner, attr, key, TRAIN_ENTRIES, TRAIN_HOST_ONLY))
+    return targets
+
+
+def aliases(fn, owner, attr):
+    """Every (module, name) of the package, other than (owner, attr), whose global ``name`` is the function object ``fn``."""
+    import sys
+    found = []
+    for mod_name, module in sorted(sys.modules.items()):
+        if module is None or not (mod_name == PACKAGE or mod_name.startswith(PACKAGE + ".")):
+            continue
+        for name, value in list(vars(module).items()):
+            if value is fn and (module is not owner or name != attr):
+                found.append((module, name))
+    return found
+
+
 def _copy(x):
     if torch.is_tensor(x):
         return x.detach().clone()
@@ -1430,9 +1667,7 @@ class Shadow:
     tripwires at the C boundary (``launches``): no wrapper, no reference, no error for a launch outside an entry."""
 
     def __init__(self, monkeypatch, fault: Optional[Callable] = None, check: bool = True):
-        import importlib
-
-        from relation_detr_amd import _lib, ops
+        from relation_detr_amd import _lib
         self.records: List[Record] = []
         self.calls: collections.Counter = collections.Counter()
         self.checked: collections.Counter = collections.Counter()
@@ -1441,20 +1676,17 @@ class Shadow:
         self.depth = 0
         self.fault = fault
         self.check = check
-        targets = [(ops, name, name, KERNEL_ENTRIES, HOST_ONLY) for name in ops_functions(ops)]
-        for short in TRAIN_MODULES:
-            module = importlib.import_module(f"relation_detr_amd.{short}")
-            for key in train_functions(module):
-                *owners, attr = key.split(".")[1:]
-                owner = module
-                for name in owners:                                # "module.Class.method": patched on the class
-                    owner = getattr(owner, name)
-                targets.append((owner, attr, key, TRAIN_ENTRIES, TRAIN_HOST_ONLY))
-        for module, attr, key, entries, host_only in targets if check else ():
+        for owner, attr, key, entries, host_only in patch_targets() if check else ():
             if key in host_only:
                 continue
-            fn = getattr(module, attr)
-            monkeypatch.setattr(module, attr, self._checked(key, fn, entries[key]) if key in entries else self._unclassified(key, fn))
+            fn = getattr(owner, attr)
+            wrapper = self._checked(key, fn, entries[key]) if key in entries else self._unclassified(key, fn)
+            wrapper.shadow_key = key
+            monkeypatch.setattr(owner, attr, wrapper)
+            # ... and wherever another module of the package holds the same function object as a global (``from .epilogue import
+            # stem_bn_relu_maxpool`` in backbones/resnet.py, the re-exports of an __init__): a call through that name is the same launch
+            for other, name in aliases(fn, owner, attr) if inspect.ismodule(owner) else ():
+                monkeypatch.setattr(other, name, wrapper)
         lib = _lib.load()
         for sym in launching_symbols(_lib.SIGNATURES):
             monkeypatch.setattr(lib, sym, self._tripwire(sym, getattr(lib, sym)))

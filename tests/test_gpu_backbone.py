@@ -16,6 +16,7 @@ from torch.nn import functional as F
 
 import relation_detr_amd
 from dirty import poisoned
+from helpers import bf16_slack, torch_bn_act, torch_stem
 from relation_detr_amd import backbones
 from relation_detr_amd.backbones import FrozenBatchNorm2d, ResNetBackbone, frozen_bn_act, frozen_bn_act_backward, stem_bn_relu_maxpool
 
@@ -45,23 +46,9 @@ def constants(C, seed):
     return s.to(DEV), (torch.randn(C, generator=g) * 0.5).to(DEV)
 
 
-def torch_bn_act(x, s, h, r, relu):
-    """The reference's passes, one operator each."""
-    y = x * s.reshape(1, -1, 1, 1)
-    y = y + h.reshape(1, -1, 1, 1)
-    if r is not None:
-        y = y + r
-    return torch.relu(y) if relu else y
-
-
 def same(a, b):
     """Equal element by element, a NaN equal to a NaN."""
     return a.shape == b.shape and a.dtype == b.dtype and bool(((a == b) | (a.isnan() & b.isnan())).all())
-
-
-def bf16_slack(x, s, h, r):
-    s4, h4 = s.double().reshape(1, -1, 1, 1), h.double().reshape(1, -1, 1, 1)
-    return 2.0 ** -20 * ((x.double() * s4).abs() + h4.abs() + (r.double().abs() if r is not None else 0.0))
 
 
 def check_forward(got, x, s, h, r, relu, dtype, what):
@@ -169,10 +156,6 @@ def test_residual_without_a_gradient_gets_none():
 
 
 # ------------------------------------------------------------------------------------------------------------- stem_pool
-def torch_stem(x, s, h):
-    return F.max_pool2d(torch.relu(x * s.reshape(1, -1, 1, 1) + h.reshape(1, -1, 1, 1)), 3, 2, 1)
-
-
 @pytest.mark.parametrize("dtype", [F32, BF16], ids=["f32", "bf16"])
 @pytest.mark.parametrize("cl", [False, True], ids=["nchw", "nhwc"])
 def test_stem_pool(cl, dtype):

@@ -37,8 +37,11 @@ Training steps:
       composition that reaches msda_train_head_major and rel_train_fused
   T2  the mixed-precision detector step of tests/test_gpu_shadow_detector.py, two steps: M, B = 3, 17 boxes / none / one, device matcher
   T3  its fp32 default step: the tiny model on three images of odd maps (13,21) (7,11) (4,6) + (2,3)
+  T4  case (e) of tests/test_gpu_shadow_detector.py, one step: the reduced R50 detector from three float images under
+      torch.autocast(bfloat16), the front end's batch and every epilogue output of the ResNet-50 (5 x 7 planes at layer4) allocated
+      under the pattern; the routes pinned by the launch counts the module gives (52 epilogues, 42 backwards, one stem pool)
 
-With ``RDETR_SHADOW_REPORTS=<directory>`` every case writes its report table there (profiles/r26/)."""
+With ``RDETR_SHADOW_REPORTS=<directory>`` every case writes its report table there (profiles/r26/; T4: profiles/r28/)."""
 import time
 
 import pytest
@@ -47,7 +50,8 @@ import torch
 import dirty
 import shadow
 from helpers import synthetic_state_dict
-from test_gpu_shadow_detector import _write_report, fp32_step, mixed_inputs, mixed_two_steps
+from test_gpu_shadow_detector import (IMAGES_MIXED_OPS, _write_report, check_image_case, fp32_step, image_steps, mixed_inputs,
+                                      mixed_two_steps)
 from test_gpu_shadow_stack import (EVAL_BF16_OPS, EVAL_FP32_OPS, TRAIN_SWITCHES, _dn_inputs, _eval_run, _loss, _ratio_table,
                                    assert_all_training_routes)
 
@@ -236,4 +240,15 @@ def test_t3_fp32_detector_step(monkeypatch, pattern):
     poison = dirty.poison(monkeypatch, pattern)
     fp32_step(monkeypatch, (feats, mask.to(DEV), targets), f"T3: fp32 detector step, three images, maps {maps}; scratch memory 0x{pattern:02X}",
               f"dirty_T3_0x{pattern:02X}.txt")
+    assert poison.fills > 0
+
+
+@PATTERNS
+def test_t4_mixed_precision_detector_step_from_images(monkeypatch, pattern):
+    poison = dirty.poison(monkeypatch, pattern)
+    started = time.perf_counter()
+    sh, model = image_steps(monkeypatch, 1, autocast=True)
+    print(f"T4 under the harness: {time.perf_counter() - started:.1f} s")
+    check_image_case(sh, model, f"T4: mixed-precision detector step from three float images, R50 backbone; scratch memory 0x{pattern:02X}",
+                     f"dirty_T4_0x{pattern:02X}.txt", IMAGES_MIXED_OPS, 1, 1, "_bf16")
     assert poison.fills > 0

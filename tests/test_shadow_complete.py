@@ -48,6 +48,8 @@ def test_every_training_module_function_is_classified():
     for short in shadow.TRAIN_MODULES:
         names |= set(shadow.train_functions(importlib.import_module(f"relation_detr_amd.{short}")))
     assert {"ln_train.add_layer_norm_backward", "ffn_train._pack", "msda_train_hm.split_merged_projection"} <= names
+    assert {"backbones.epilogue.frozen_bn_act_backward", "backbones.epilogue.FrozenBNActFunction.backward", "frontend.images.batch_images",
+            "frontend.images.ImagePreprocessor.batch_fused"} <= names
     assert {"amp_train.ffn_mixed_backward", "amp_train.ffn_pack_f32", "neck.group_norm_levels_backward", "neck._sine_pos_packed",
             "denoising.cdn_embed_backward", "criterion.assign_match", "criterion._set_loss_torch", "optim.train_step",
             "optim.FusedAdamW._clip_fused", "optim.FusedAdamW._step_fused", "optim.FusedAdamW._prepare"} <= names
@@ -59,19 +61,49 @@ def test_every_training_module_function_is_classified():
     assert not set(shadow.TRAIN_ENTRIES) & set(shadow.KERNEL_ENTRIES)            # one namespace of op names in the records
 
 
-def _package_functions():
-    """(module, "function" or "Class.method") -> (ast node, names imported with ``from .x import name`` as {name: x}) for every
-    module-level function and every method of a module-level class of relation_detr_amd/*.py."""
-    out = {}
+def _package_files():
+    """{module key: path} of every .py the recursive walk of relation_detr_amd/ visits, and the subpackages it opened.  Keys are the
+    dotted path below the package: "ops", "backbones.epilogue", "backbones.__init__", "__init__"."""
     package = os.path.join(ROOT, "relation_detr_amd")
-    for file in sorted(os.listdir(package)):
-        if not file.endswith(".py"):
-            continue
-        module = file[:-3]
-        with open(os.path.join(package, file)) as f:
+    files, subpackages = {}, set()
+    for folder, dirs, names in sorted(os.walk(package)):
+        dirs[:] = sorted(d for d in dirs if d != "__pycache__")
+        below = os.path.relpath(folder, package)
+        parts = [] if below == "." else below.split(os.sep)
+        if parts and any(n.endswith(".py") for n in names):
+            subpackages.add(".".join(parts))
+        for file in sorted(names):
+            if file.endswith(".py"):
+                files[".".join(parts + [file[:-3]])] = os.path.join(folder, file)
+    return files, subpackages
+
+
+def _resolve(module, level, target):
+    """The module key that ``from <level dots><target> import ...`` names inside module ``module`` ("" for the package itself)."""
+    base = module.split(".")[:-1]                                   # the module's own package
+    base = base[:len(base) - (level - 1)] if level > 1 else base
+    return ".".join(base + (target.split(".") if target else []))
+
+
+def _imports(tree, module, level_limit=2):
+    """The relative imports of a module's top level, levels 1 and 2: ``{local name: (module key, original name)}`` for ``from .x import
+    name`` and ``from . import x`` alike (the latter: ("", "x") below the package, ("backbones", "epilogue") inside a subpackage)."""
+    found = {}
+    for node in tree.body:
+        if isinstance(node, ast.ImportFrom) and 1 <= node.level <= level_limit:
+            for a in node.names:
+                found[a.asname or a.name] = (_resolve(module, node.level, node.module), a.name)
+    return found
+
+
+def _package_functions():
+    """(module key, "function" or "Class.method") -> (ast node, that module's relative imports, see _imports) for every module-level
+    function and every method of a module-level class of every module of relation_detr_amd, subpackages included."""
+    out = {}
+    for module, path in _package_files()[0].items():
+        with open(path) as f:
             tree = ast.parse(f.read())
-        imported = {a.asname or a.name: node.module for node in tree.body if isinstance(node, ast.ImportFrom) and node.level == 1
-                    and node.module for a in node.names}
+        imported = _imports(tree, module)
         for node in tree.body:
             if isinstance(node, (ast.FunctionDef, ast.AsyncFunctionDef)):
                 out[(module, node.name)] = (node, imported)
@@ -80,6 +112,15 @@ def _package_functions():
                     if isinstance(sub, (ast.FunctionDef, ast.AsyncFunctionDef)):
                         out[(module, f"{node.name}.{sub.name}")] = (sub, imported)
     return out
+
+
+def _split(key, modules=None):
+    """"backbones.epilogue._dense" -> ("backbones.epilogue", "_dense"): the longest module of the package that starts the key."""
+    modules = _package_files()[0] if modules is None else modules
+    for module in sorted(modules, key=len, reverse=True):
+        if key.startswith(module + "."):
+            return module, key[len(module) + 1:]
+    raise AssertionError(f"{key} names no module of the package")
 
 
 def _docstrings(node):
@@ -108,20 +149,26 @@ def _is_checked_entry(module, name):
     return (name in shadow.KERNEL_ENTRIES) if module == "ops" else (f"{module}.{name}" in shadow.TRAIN_ENTRIES)
 
 
+def _refers(node, imported, mod, module, name):
+    """Whether the body ``node`` of a function of module ``mod`` refers to function ``name`` of ``module``: the bare name inside the
+    module itself or where ``from .module import name`` brought it in (under any local name), or ``<alias>.name`` with ``<alias>`` a
+    local name of the module (``from . import ops``, ``from .. import neck as n``)."""
+    last = name                                                      # a "Class.method" is never referred to by a bare name
+    for sub in ast.walk(node):
+        if isinstance(sub, ast.Name):
+            if (mod == module and sub.id == last) or imported.get(sub.id) == (module, last):
+                return True
+        elif isinstance(sub, ast.Attribute) and sub.attr == last and isinstance(sub.value, ast.Name):
+            origin = imported.get(sub.value.id)
+            if origin is not None and ".".join(p for p in origin if p) == module:
+                return True
+    return False
+
+
 def _callers(functions, module, name):
-    """Every (module, function) of the package whose body refers to function ``name`` of ``module``: the bare name inside the module
-    itself or where ``from .module import name`` brought it in, or ``module.name`` anywhere."""
-    found = []
-    for (mod, fn), (node, imported) in functions.items():
-        if (mod, fn) == (module, name):
-            continue
-        for sub in ast.walk(node):
-            bare = isinstance(sub, ast.Name) and sub.id == name and (mod == module or imported.get(name) == module)
-            dotted = isinstance(sub, ast.Attribute) and sub.attr == name and isinstance(sub.value, ast.Name) and sub.value.id == module
-            if bare or dotted:
-                found.append((mod, fn))
-                break
-    return found
+    """Every (module, function) of the package whose body refers to function ``name`` of ``module`` (_refers)."""
+    return [(mod, fn) for (mod, fn), (node, imported) in functions.items()
+            if (mod, fn) != (module, name) and _refers(node, imported, mod, module, name)]
 
 
 def test_every_function_that_names_a_launching_symbol_is_a_checked_entry():
@@ -132,22 +179,22 @@ def test_every_function_that_names_a_launching_symbol_is_a_checked_entry():
     functions = _package_functions()
     inside = set(shadow.LAUNCH_INSIDE_ENTRY)
     assert {"rowtail.linear_ln_rows", "amp_train.ffn_pack_f32", "ffn_train._pack", "ops._packed_k256"} <= inside
-    assert not {k for k in inside if _is_checked_entry(*k.split(".", 1))}, "listed as launching inside an entry and as an entry"
-    stale = {k for k in inside if tuple(k.split(".", 1)) not in functions}
+    assert not {k for k in inside if _is_checked_entry(*_split(k))}, "listed as launching inside an entry and as an entry"
+    stale = {k for k in inside if _split(k) not in functions}
     assert not stale, f"LAUNCH_INSIDE_ENTRY names functions the package no longer defines: {sorted(stale)}"
     unchecked = {}
     for (module, name), (node, _) in functions.items():
         names = _launching_mentions(node)
         if names and not _is_checked_entry(module, name) and f"{module}.{name}" not in inside:
             unchecked[f"{module}.{name}"] = sorted(names)[:3]
-    modules = sorted({k.split(".", 1)[0] for k in unchecked})
+    modules = sorted({_split(k)[0] for k in unchecked})
     assert not unchecked, f"functions of modules {modules} name a launching rdetr_* symbol outside the shadow harness: {unchecked}"
-    idle = {k for k in inside if not _launching_mentions(functions[tuple(k.split(".", 1))][0])
+    idle = {k for k in inside if not _launching_mentions(functions[_split(k)][0])
             and not any(f"{m}.{f}" in inside for m, f in _called_listed(functions, k, inside))}
     assert not idle, f"LAUNCH_INSIDE_ENTRY lists functions that neither name a symbol nor call a listed function: {sorted(idle)}"
     loose = {}
     for key in sorted(inside):
-        module, name = key.split(".", 1)
+        module, name = _split(key)
         bad = [f"{m}.{f}" for m, f in _callers(functions, module, name) if not _is_checked_entry(m, f) and f"{m}.{f}" not in inside]
         if bad:
             loose[key] = bad
@@ -156,7 +203,7 @@ def test_every_function_that_names_a_launching_symbol_is_a_checked_entry():
 
 def _called_listed(functions, key, inside):
     """The listed functions that the listed function ``key`` itself calls (a wrapper around a packer is listed for that)."""
-    return [tuple(k.split(".", 1)) for k in inside if k != key and tuple(key.split(".", 1)) in _callers(functions, *k.split(".", 1))]
+    return [_split(k) for k in inside if k != key and _split(key) in _callers(functions, *_split(k))]
 
 
 def test_covered_elsewhere_names_files_that_exist():
@@ -179,3 +226,118 @@ def test_every_covered_elsewhere_switch_is_on_in_the_training_step():
     for test in (stack.test_shadow_all_training_routes_step, stack.test_training_routes_match_defaults_against_fp32):
         assert "TRAIN_SWITCHES" in inspect.getsource(test), test.__name__
     assert "dict.fromkeys(switches, True)" in inspect.getsource(stack._mid_training_step)
+
+
+# ------------------------------------------------------------------------------------------- the walk itself, and by-name bindings
+def test_the_walk_visits_every_file_of_the_package():
+    """The guard reads what is on disk: every .py below relation_detr_amd/, found a second way, is a module the walk visited, and the
+    walk opened the subpackages (a listing of the package's own folder alone sees none of them)."""
+    import pathlib
+    files, subpackages = _package_files()
+    package = pathlib.Path(ROOT, "relation_detr_amd")
+    on_disk = {str(p) for p in package.rglob("*.py") if "__pycache__" not in p.parts}
+    assert set(files.values()) == on_disk, sorted(set(files.values()) ^ on_disk)
+    assert len(subpackages) >= 2 and {"backbones", "frontend"} <= subpackages, subpackages
+    assert {"backbones.epilogue", "backbones.resnet", "frontend.images", "backbones.__init__", "ops", "__init__"} <= set(files)
+    modules = {m for m, _ in _package_functions()}
+    assert {"backbones.epilogue", "backbones.resnet", "frontend.images"} <= modules
+
+
+def test_every_module_that_names_a_launching_symbol_is_in_the_harness():
+    """Module by module, from the whole source (not only the function bodies): a module that names a launching rdetr_* symbol is ops,
+    a module of shadow.TRAIN_MODULES, or the home of a LAUNCH_INSIDE_ENTRY function (rowtail).  _lib is the binding table itself."""
+    files, _ = _package_files()
+    allowed = {"ops", "_lib"} | set(shadow.TRAIN_MODULES) | {_split(k, files)[0] for k in shadow.LAUNCH_INSIDE_ENTRY}
+    naming = {}
+    for module, path in files.items():
+        with open(path) as f:
+            tree = ast.parse(f.read())
+        skip = _docstrings(tree) | ({id(tree.body[0].value)} if tree.body and isinstance(tree.body[0], ast.Expr) else set())
+        names = {n for n in _launching_mentions(tree) if n in _lib.SIGNATURES or n.endswith("_")}
+        names -= {sub.value for sub in ast.walk(tree) if isinstance(sub, ast.Constant) and id(sub) in skip and isinstance(sub.value, str)}
+        if names:
+            naming[module] = sorted(names)[:3]
+    assert {"ops", "backbones.epilogue", "frontend.images", "neck", "rowtail"} <= set(naming), sorted(naming)
+    outside = {m: v for m, v in naming.items() if m not in allowed}
+    assert not outside, f"modules that name a launching rdetr_* symbol and are not in the shadow harness's module list: {outside}"
+    for short in shadow.TRAIN_MODULES:
+        assert short in files, f"shadow.TRAIN_MODULES names {short}, which is no module of the package"
+
+
+def _stub_library(monkeypatch):
+    """``_lib.load()`` answers with an object that has every symbol and launches nothing: the harness can be installed without the built
+    library and without a device."""
+    import types
+    stub = types.SimpleNamespace(**{name: (lambda *args: 0) for name in _lib.SIGNATURES})
+    monkeypatch.setattr(_lib, "load", lambda: stub)
+    return stub
+
+
+def _reached_entries(functions, module, name, seen=None):
+    """The checked entries of ``module`` that its function ``name`` reaches through bare names of that module (a class name stands for
+    all its methods), itself included when it is one."""
+    seen = set() if seen is None else seen
+    if (module, name) in seen or (module, name) not in functions:
+        return set()
+    seen.add((module, name))
+    if _is_checked_entry(module, name):
+        return {name}
+    node = functions[(module, name)][0]
+    used = {sub.id for sub in ast.walk(node) if isinstance(sub, ast.Name)}
+    found = set()
+    for (mod, fn) in functions:
+        if mod == module and fn.split(".")[0] in used:
+            found |= _reached_entries(functions, module, fn, seen)
+    return found
+
+
+def test_a_checked_entry_bound_by_name_is_patched_there_too(monkeypatch):
+    """``from .epilogue import stem_bn_relu_maxpool`` gives backbones/resnet.py its own reference to the function; a harness that
+    patched the defining module alone would leave that call outside itself.  From the source of every module: each ``from .x import
+    name`` (levels 1 and 2) of a checked entry must hold the entry's wrapper once ``Shadow`` stands; each one of a host-only function
+    of a harness module that reaches entries (``frozen_bn_act``) must hold the function itself, whose own globals then hold the
+    wrappers of the entries it reaches."""
+    functions = _package_functions()
+    files, _ = _package_files()
+    harness = {"ops"} | set(shadow.TRAIN_MODULES)
+    bindings = []                                                   # (importing module, local name, module, name, entries reached)
+    imports = {}
+    for module, path in files.items():
+        with open(path) as f:
+            imports[module] = _imports(ast.parse(f.read()), module)
+    for module, imported in imports.items():
+        for local, (origin, name) in imported.items():
+            while name in imports.get(f"{origin}.__init__", {}):    # a name a subpackage's __init__ re-exports: where that has it from
+                origin, name = imports[f"{origin}.__init__"][name]
+            if origin in harness and (origin, name) in functions:
+                reached = _reached_entries(functions, origin, name)
+                if reached:
+                    bindings.append((module, local, origin, name, reached))
+    found = {(m, l) for m, l, *_ in bindings}
+    assert {("backbones.resnet", "stem_bn_relu_maxpool"), ("backbones.resnet", "frozen_bn_act"), ("backbones.__init__", "frozen_bn_act_forward"),
+            ("backbones.__init__", "frozen_bn_act_backward"), ("frontend.__init__", "batch_images"), ("__init__", "batch_images")} <= found, found
+    _stub_library(monkeypatch)
+    sh = shadow.Shadow(monkeypatch)
+    assert not sh.errors
+    key_of = lambda origin, name: name if origin == "ops" else f"{origin}.{name}"                            # noqa: E731
+    wrong = []
+    for module, local, origin, name, reached in bindings:
+        holder = importlib.import_module("relation_detr_amd" + ("" if module == "__init__" else "." + module.removesuffix(".__init__")))
+        bound = getattr(holder, local)
+        if _is_checked_entry(origin, name):
+            if getattr(bound, "shadow_key", None) != key_of(origin, name):
+                wrong.append(f"{module}.{local} is not the wrapper of {key_of(origin, name)}")
+            continue
+        if hasattr(bound, "shadow_key"):
+            wrong.append(f"{module}.{local} is host-only and was wrapped")
+        for entry in reached:
+            target = bound.__globals__.get(entry.split(".")[0])
+            for part in entry.split(".")[1:]:                       # "Class.method": the wrapper sits on the class
+                target = getattr(target, part, None)
+            if getattr(target, "shadow_key", None) != key_of(origin, entry):
+                wrong.append(f"{module}.{local} reaches {origin}.{entry} through a global that is not its wrapper")
+    assert not wrong, wrong
+    # and the wrappers are one object per entry: the call counter of the entry sees the launches of every binding
+    from relation_detr_amd.backbones import epilogue, resnet
+    assert resnet.stem_bn_relu_maxpool is epilogue.stem_bn_relu_maxpool and resnet.frozen_bn_act is epilogue.frozen_bn_act
+    assert resnet.frozen_bn_act.__globals__["frozen_bn_act_forward"].shadow_key == "backbones.epilogue.frozen_bn_act_forward"

@@ -8,6 +8,11 @@ fp32 torch route as the "kernel", then one planted defect each.
 
 Shapes: FFN 37 rows x F = 64; LayerNorm 5 and 300 rows; attention B = 2, N = M = 37 with a block mask and one fully masked row;
 MSDA levels [(9, 7), (5, 4)], B = 2, one padded image.
+
+The last part does it for the entries in front of the neck (backbones.epilogue, frontend.images): fp32 torch operators and the
+float64 value rounded once to bf16 as the epilogue kernels, ``ImagePreprocessor.batch_torch`` as the front end; planes of 5 x 7
+(35 elements, off the 16-byte grid), channels-last with C = 12 (no multiple of 8), and the uint8 images of the GPU cases themselves,
+whose near-tie share is asserted here so that the GPU test cannot be ill-posed by its inputs.
 """
 import math
 
@@ -310,7 +315,7 @@ def _labels(bad):
 
 
 def test_new_entries_are_all_exercised_here():
-    new = {k for k in shadow.TRAIN_ENTRIES if k.split(".")[0] in ("amp_train", "neck", "denoising", "criterion", "optim")}
+    new = {k for k in shadow.TRAIN_ENTRIES if k.split(".")[0] in ("amp_train", "neck", "denoising", "criterion", "optim", "backbones", "frontend")}
     assert new == set(DETECTOR_CASES), (sorted(new - set(DETECTOR_CASES)), sorted(set(DETECTOR_CASES) - new))
 
 
@@ -791,3 +796,277 @@ def test_step_checker(step2):
     a, _ = run()
     a["coef"] = None                                                          # the reference then steps with the unclipped gradients
     assert "exp_avg" in _labels(_fails(key, a, None, "the clip coefficient applied where none was armed"))
+
+
+# ------------------------------------------------------------------------------------------------- the backbone's epilogues
+FWD, BWD, STEM, IMAGES = ("backbones.epilogue.frozen_bn_act_forward", "backbones.epilogue.frozen_bn_act_backward",
+                          "backbones.epilogue.stem_bn_relu_maxpool", "frontend.images.batch_images")
+POISON = 48.5                                                                    # what 0x42 bytes read as in bf16 (48.56 in fp32)
+
+
+def _epilogue_case(dtype, channels_last=False, C=6, seed=3):
+    g = torch.Generator().manual_seed(seed)
+    x, r, dy = (_rand(g, 2, C, 5, 7, dtype=dtype) for _ in range(3))
+    if channels_last:
+        x, r, dy = (t.contiguous(memory_format=torch.channels_last) for t in (x, r, dy))
+    s = (torch.rand(C, generator=g) + 0.5) * torch.where(torch.arange(C) % 3 == 1, -1.0, 1.0)          # every third channel negative
+    return x, r, dy, s, torch.randn(C, generator=g) * 0.5
+
+
+def _kernel_forward(x, s, h, r, relu):
+    """Within the bound by construction: the fp32 operator sequence; for bf16 the float64 value rounded once."""
+    from helpers import torch_bn_act
+    if x.dtype == F32:
+        return torch_bn_act(x, s, h, r, relu)
+    return torch_bn_act(x.double(), s.double(), h.double(), None if r is None else r.double(), relu).to(BF)
+
+
+def _kernel_backward(dy, mask_from, s, relu, want_dres):
+    masked = torch.where(mask_from <= 0, torch.zeros_like(dy), dy) if relu else dy
+    s4 = s.reshape(1, -1, 1, 1)
+    dx = masked * s4 if dy.dtype == F32 else (masked.double() * s4.double()).to(BF)
+    return dx, (masked.clone() if want_dres else None)
+
+
+@_case(FWD)
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["fp32", "bf16"])
+def test_frozen_bn_act_forward_checker(dtype, channels_last):
+    x, r, _, s, h = _epilogue_case(dtype, channels_last, C=12)
+    for res_in, relu in ((None, True), (r, True), (r, False), (r.float() if dtype == BF else r.to(BF), True)):
+        a = dict(x=x, scale=s, shift=h, residual=res_in, relu=relu, out=None)
+        used = None if res_in is None else res_in.to(dtype)
+        out = _kernel_forward(x, s, h, used, relu)
+        _passes(FWD, a, out)
+        _passes(FWD, dict(a, out=x.clone()), out)                                 # in place: the wrapper's copy of x is the operand
+        c = _cmp(FWD, a, out, "out")
+        idx = tuple(int(i) for i in (out.double().abs() == out.double().abs().max()).nonzero()[0])
+        bumped = out.clone()
+        if dtype == F32:
+            bumped[idx] = torch.nextafter(out[idx], out[idx] * 2)                 # exact: one ulp is over
+        else:
+            bumped[idx] = (c.ref[idx] + 2 * c.bound[idx] * (1 + 2.0 ** -6)).to(BF) + 0
+            assert abs(float(bumped[idx]) - float(c.ref[idx])) > float(c.bound[idx])
+        bad = _fails(FWD, a, bumped, "one element twice its bound off")
+        assert len(bad) == 1 and bad[0][1] == 1, bad
+        tail = out.clone()
+        tail[1, 4, 4, 4:] = POISON                                          # the last 3 of a plane's 35 elements never written
+        bad = _fails(FWD, a, tail, "one plane's tail left at the poison value")
+        assert bad[0][1] == 3 and "out[1, 4, 4, " in bad[0][0], bad
+        # channel c's constants applied to channel c + 1: what a channels-last kernel does that steps its constants by the wrong phase
+        rolled = _kernel_forward(x, s.roll(1), h.roll(1), used, relu)
+        assert "out" in _labels(_fails(FWD, a, rolled, "scale and shift of channel c applied to channel c + 1"))
+    assert x.is_contiguous(memory_format=torch.channels_last) == channels_last and x.shape[1] % 8
+
+
+@_case(BWD)
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["fp32", "bf16"])
+def test_frozen_bn_act_backward_checker(dtype):
+    x, r, dy, s, h = _epilogue_case(dtype)
+    y = _kernel_forward(x, s, h, r, True)
+    assert bool(((x <= 0) != (y <= 0)).any())                                      # the two masks differ: a negative scale, a residual
+    for relu, want in ((True, True), (True, False), (False, True)):
+        a = dict(dy=dy, y=y, scale=s, relu=relu, want_dres=want)
+        dx, dres = _kernel_backward(dy, y, s, relu, want)
+        _passes(BWD, a, (dx, dres))
+        if relu:
+            wrong = _kernel_backward(dy, x, s, True, want)
+            labels = _labels(_fails(BWD, a, wrong, "the ReLU mask taken from x instead of y"))
+            assert "dx" in labels and ("dres[" in labels) == want
+            stale = _kernel_backward(dy, torch.ones_like(y), s, True, want)         # a stale saved output: nothing masked
+            assert "dx" in _labels(_fails(BWD, a, stale, "no element masked"))
+        other = _kernel_backward(dy, y, s, relu, not want)
+        bad = _fails(BWD, a, (dx, other[1]), "dres returned where none was asked for" if not want else "no dres where one was asked for")
+        assert len(bad) == 1 and "dres_returned" in bad[0][0], bad
+        c = _cmp(BWD, a, (dx, dres), "dx")
+        idx = tuple(int(i) for i in dx.double().abs().flatten().argmax().reshape(1).new_tensor(
+            torch.unravel_index(dx.double().abs().argmax(), dx.shape)))
+        bumped = dx.clone()
+        if dtype == F32:
+            bumped[idx] = torch.nextafter(dx[idx], dx[idx] * 2)
+        else:
+            bumped[idx] = (c.ref[idx] * (1 + 2 * 2.0 ** -8 * (1 + 2.0 ** -6))).to(BF)
+            assert abs(float(bumped[idx]) - float(c.ref[idx])) > float(c.bound[idx])
+        bad = _fails(BWD, a, (bumped, dres), "one dx element twice its bound off")
+        assert len(bad) == 1 and bad[0][1] == 1 and "dx" in bad[0][0], bad
+        if want:
+            swapped = _fails(BWD, a, (dres * s.reshape(1, -1, 1, 1).to(dtype), dx), "dres routed to the wrong operand")
+            assert "dres[" in _labels(swapped)
+            tail = dres.clone()
+            tail[0, 2, 4, 4:] = POISON
+            assert "dres[0, 2, 4, " in _labels(_fails(BWD, a, (dx, tail), "one plane's tail of dres left at the poison value"))
+
+
+@_case(STEM)
+@pytest.mark.parametrize("channels_last", [False, True], ids=["nchw", "nhwc"])
+@pytest.mark.parametrize("dtype", [F32, BF], ids=["fp32", "bf16"])
+def test_stem_pool_checker(dtype, channels_last):
+    from helpers import torch_stem
+    g = torch.Generator().manual_seed(5)
+    C = 12
+    x = _rand(g, 2, C, 9, 13, dtype=dtype)
+    x = x.contiguous(memory_format=torch.channels_last) if channels_last else x
+    s, h = (torch.rand(C, generator=g) + 0.5) * torch.where(torch.arange(C) % 3 == 1, -1.0, 1.0), torch.randn(C, generator=g) * 0.5
+    kernel = lambda x, s, h: torch_stem(x, s, h) if dtype == F32 else torch_stem(x.double(), s.double(), h.double()).to(BF)   # noqa: E731
+    a = dict(x=x, scale=s, shift=h)
+    out = kernel(x, s, h)
+    assert tuple(out.shape) == (2, C, 5, 7)
+    _passes(STEM, a, out)
+    c = _cmp(STEM, a, out, "out")
+    idx = tuple(int(i) for i in torch.unravel_index(out.double().argmax(), out.shape))
+    bumped = out.clone()
+    if dtype == F32:
+        bumped[idx] = torch.nextafter(out[idx], out[idx] * 2)
+    else:
+        bumped[idx] = (c.ref[idx] + 2 * c.bound[idx] * (1 + 2.0 ** -6)).to(BF)
+        assert abs(float(bumped[idx]) - float(c.ref[idx])) > float(c.bound[idx])
+    bad = _fails(STEM, a, bumped, "one pooled element twice its bound off")
+    assert len(bad) == 1 and bad[0][1] == 1, bad
+    tail = out.clone()
+    tail[1, 7, 4, 4:] = POISON
+    assert _fails(STEM, a, tail, "one plane's tail left at the poison value")[0][1] == 3
+    assert "out" in _labels(_fails(STEM, a, kernel(x, s.roll(1), h.roll(1)), "scale and shift of channel c applied to channel c + 1"))
+    # every input negative, scale and shift positive, and so negative that relu gives 0 everywhere: the result is +0.  A kernel that
+    # reads the padding as an INPUT of 0 puts relu(0 * s + h) = h into every window at the border
+    neg = (-x.float().abs() - 4.0).to(dtype)
+    sp, hp = s.abs(), h.abs() + 0.25
+    a = dict(x=neg, scale=sp, shift=hp)
+    out = kernel(neg, sp, hp)
+    assert not out.double().any()
+    _passes(STEM, a, out)
+    padded = torch.nn.functional.pad(neg.double(), (1, 1, 1, 1))
+    leaky = torch.nn.functional.max_pool2d(torch.relu(padded * sp.double().reshape(1, -1, 1, 1) + hp.double().reshape(1, -1, 1, 1)), 3, 2, 0)
+    bad = _fails(STEM, a, leaky.to(dtype), "a pooled window that reads the padding as 0")
+    assert bad[0][1] == 2 * C * (5 * 7 - 3 * 5), bad                                # every window on the border of the 5 x 7 result
+
+
+# ------------------------------------------------------------------------------------------------- the image front end
+def _front_args(images, pre, **change):
+    return dict(dict(images=images, sizes=pre.target_sizes(images), size_divisible=pre.size_divisible, mean=pre.mean, std=pre.std,
+                     normalize=not pre.training, dtype=pre.dtype, channels_last=pre.channels_last), **change)
+
+
+@pytest.fixture(scope="module")
+def uint8_batch():
+    """The uint8 images of the GPU cases (f), through the torch route."""
+    from helpers import DETECTOR_BATCH, DETECTOR_RESIZE, detector_uint8_images
+    from relation_detr_amd.frontend import ImagePreprocessor
+    images = detector_uint8_images()
+    pre = ImagePreprocessor(*DETECTOR_RESIZE, fused=False).eval()
+    batch = pre.batch_torch(images)
+    assert tuple(batch.tensors.shape) == (3, 3) + DETECTOR_BATCH
+    return images, pre, batch
+
+
+@_case(IMAGES)
+def test_batch_images_checker_on_the_gpu_cases_uint8_images(uint8_batch):
+    from test_images_host import NEAR_TIE_SHARE
+    images, pre, batch = uint8_batch
+    a = _front_args(images, pre)
+    assert a["sizes"] == [(150, 213), (56, 224), (150, 184)]
+    assert 56 * 224 < 0.5 * 160 * 224                                               # the middle image: most of its slot is padding
+    _passes(IMAGES, a, batch)
+    share = _cmp(IMAGES, a, batch, "near_tie_share")
+    valid = sum(3 * oh * ow for oh, ow in a["sizes"])
+    print(f"near ties: {int(share.got)} of {valid} valid values, the cap is {NEAR_TIE_SHARE * valid:.0f}")
+    assert share.gate and float(share.bound) == NEAR_TIE_SHARE * valid and float(share.got) <= float(share.bound)
+    assert NEAR_TIE_SHARE == 0.02
+    # bf16 and channels-last: the rounding of the same values
+    other = batch._replace(tensors=batch.tensors.to(BF).contiguous(memory_format=torch.channels_last))
+    _passes(IMAGES, dict(a, dtype=BF, channels_last=True), other)
+    assert "batch_dtype" in _labels(_fails(IMAGES, a, other, "a bf16 batch where fp32 was asked for"))
+
+    def with_tensors(fn):
+        t = batch.tensors.clone()
+        fn(t)
+        return batch._replace(tensors=t)
+
+    def bump(t):
+        t[0, 1, 17, 100] = torch.nextafter(t[0, 1, 17, 100], t.new_tensor(10.0))
+    bad = _fails(IMAGES, a, with_tensors(bump), "one value one ulp off")
+    assert len(bad) == 1 and bad[0][1] == 1 and "image0" in bad[0][0], bad
+    shifted = batch._replace(mask=torch.roll(batch.mask, 1, 2))
+    assert "mask" in _labels(_fails(IMAGES, a, shifted, "the mask shifted by one pixel"))
+    shifted = batch._replace(mask=torch.roll(batch.mask, 1, 1))
+    assert "mask" in _labels(_fails(IMAGES, a, shifted, "the mask shifted by one row"))
+
+    def dirty_padding(t):
+        t[1, 2, 159, 223] = -0.0                                                   # the padding is +0 to the bit
+    bad = _fails(IMAGES, a, with_tensors(dirty_padding), "a padding element that is -0")
+    assert len(bad) == 1 and "padding_bits[1, 2, 159, 223]" in bad[0][0], bad
+
+    def poisoned_padding(t):
+        t[1, :, 56:, :] = POISON
+    assert "padding_bits" in _labels(_fails(IMAGES, a, with_tensors(poisoned_padding), "the padding region not written"))
+    swapped = batch._replace(tensors=batch.tensors[[1, 0, 2]], mask=batch.mask[[1, 0, 2]])
+    labels = _labels(_fails(IMAGES, a, swapped, "images 0 and 1 in each other's batch slot"))
+    assert "mask" in labels and "image0" in labels and "image1" in labels
+    values_only = batch._replace(tensors=batch.tensors[[2, 1, 0]])                  # images 0 and 2 have the same height: the values alone
+    labels = _labels(_fails(IMAGES, a, values_only, "the values of image 2 in slot 0"))
+    assert "image0" in labels and "image2" in labels
+    sizes = batch._replace(image_sizes=batch.original_sizes)
+    assert "image_sizes" in _labels(_fails(IMAGES, a, sizes, "the original sizes as the resized ones"))
+    # too many near ties: the call fails as ill-posed although every value is acceptable
+    flat = [torch.full((3, 40, 60), 128, dtype=torch.uint8) for _ in range(2)]
+    flat[0][:, ::2] = 127                                                          # rows of 127 and 128: a 2 x downscale lands on 127.5
+    a2 = _front_args(flat, pre, sizes=[(20, 60), (40, 60)])
+    from relation_detr_amd.frontend import ImagePreprocessor
+    res = ImagePreprocessor(fused=False).eval().batch_torch([flat[0][:, :20], flat[1]])       # the layout alone; the gate is what is looked at
+    gate = _cmp(IMAGES, a2, res, "near_tie_share")
+    assert float(gate.got) > float(gate.bound)
+
+
+def test_batch_images_checker_float_sources_and_the_copy_path():
+    from helpers import detector_float_images
+    from relation_detr_amd.frontend import ImagePreprocessor
+    from test_images_host import resize64
+    images = detector_float_images()
+    pre = ImagePreprocessor(150, 224, fused=False).train()                        # training mode: batched only
+    batch = pre.batch_torch(images)
+    a = _front_args(images, pre)
+    assert a["normalize"] is False and a["sizes"] == [(160, 200), (131, 224), (50, 70)] and tuple(batch.tensors.shape) == (3, 3, 160, 224)
+    _passes(IMAGES, a, batch)
+    t = batch.tensors.clone()
+    t[2, 0, 49, 69] = torch.nextafter(t[2, 0, 49, 69], t.new_tensor(10.0))
+    bad = _fails(IMAGES, a, batch._replace(tensors=t), "one copied value one ulp off")
+    assert len(bad) == 1 and "image2[0, 49, 69]" in bad[0][0], bad
+    _passes(IMAGES, dict(a, dtype=BF), batch._replace(tensors=batch.tensors.to(BF)))
+    # eval mode, float sources in [0, 1], resized: the float64 filter, normalised, rounded once
+    g = torch.Generator().manual_seed(7)
+    sources = [torch.rand(3, 45, 70, generator=g), torch.rand(3, 64, 64, generator=g)]
+    pre = ImagePreprocessor(fused=False).eval()
+    sizes = [(37, 61), (64, 64)]                                                   # one resized, one normalised in place
+    a = _front_args(sources, pre, sizes=sizes)
+    mean, std = torch.tensor(pre.mean, dtype=F64).view(3, 1, 1), torch.tensor(pre.std, dtype=F64).view(3, 1, 1)
+    out = torch.zeros(2, 3, 64, 64)
+    out[0, :, :37, :61] = ((torch.from_numpy(resize64(sources[0].numpy(), 37, 61)) - mean) / std).float()
+    out[1] = sources[1].clone().sub_(mean.float()).div_(std.float())
+    mask = torch.ones(2, 64, 64, dtype=torch.bool)
+    mask[0, :37, :61], mask[1] = False, False
+    from relation_detr_amd.frontend import ImageBatch
+    res = ImageBatch(out, mask, torch.tensor(sizes), torch.tensor([[45, 70], [64, 64]]))
+    _passes(IMAGES, a, res)
+    _passes(IMAGES, dict(a, dtype=BF), res._replace(tensors=out.to(BF)))
+    c = _cmp(IMAGES, a, res, "image0")
+    off = out.clone()
+    off[0, 1, 5, 9] = (c.ref[1, 5, 9] + 2 * c.bound[1, 5, 9]).float()
+    bad = _fails(IMAGES, a, res._replace(tensors=off), "one resized float value twice its bound off")
+    assert len(bad) == 1 and bad[0][1] == 1 and "image0[1, 5, 9]" in bad[0][0], bad
+    off16 = out.to(BF)
+    off16[0, 1, 5, 9] = torch.nextafter(off16[0, 1, 5, 9].float(), torch.tensor(10.0)).to(BF) + 2.0 ** -6
+    assert "image0[1, 5, 9]" in _labels(_fails(IMAGES, dict(a, dtype=BF), res._replace(tensors=off16), "one bf16 value two steps off"))
+
+
+def test_batch_images_checker_applies_where_the_kernel_takes_the_batch(monkeypatch, uint8_batch):
+    from relation_detr_amd.frontend import images as fimages
+    images, pre, _ = uint8_batch
+    applies = shadow.TRAIN_ENTRIES[IMAGES].applies
+    a = _front_args(images, pre)
+    assert fimages._kernel_takes(images, a["sizes"], 32, True) == "a tensor that is not on a ROCm device" and not applies(a)
+    seen = []
+    monkeypatch.setattr(fimages, "_kernel_takes", lambda *args: seen.append(args) or None)
+    assert applies(a) and applies(dict(a, sizes=None)) and applies(dict(a, images=torch.stack([images[0], images[0]]), sizes=None))
+    assert seen[0] == (images, a["sizes"], 32, True) and seen[1][1] == [(211, 300), (100, 400), (333, 410)] and len(seen[2][0]) == 2
+    monkeypatch.setattr(fimages, "_kernel_takes", lambda *args: "a downscale beyond 8")
+    assert not applies(a)
+    assert not applies(dict(a, sizes=a["sizes"][:2])) and not applies(dict(a, dtype=torch.float16))   # batch_images raises before the kernel
