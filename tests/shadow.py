@@ -146,10 +146,39 @@ tests/test_gpu_dirty_shapes.py runs the harness at small ragged shapes with ever
 and 0x42 first (tests/dirty.py); profiles/r26/ has those report tables.  Two bounds that its training step exceeded on clean memory
 changed their FORM there, in the unit test and here together, for a scale the earlier form lacked: the dk and dv of the attention
 backwards (attention_grad_rounding) and the log-sum-exp of the attention forward that generates its bias (boxes_lse_bound).
+
+Where a call WRITES (``Shadow(monkeypatch, writes=True, guard=None)``; off by default, every test above runs as it did).  Everything
+above checks what an entry returns; none of it notices a kernel that also writes memory it does not own.  With ``writes=True``
+every checked call adds ONE MORE RECORD under the same op (``Record.kind == "writes"``; it fails the op like any bad record, and
+the report gets a "writes" column), from three comparisons:
+  operand bits    every tensor argument -- and every tensor inside a list, tuple or dict argument, the parameters of a module
+                  argument, the parameters, gradients and state of an optimizer -- that the entry's write set does not name is
+                  bit-identical to its copy from before the call.  Compared through an integer view of the element size: a NaN
+                  equals itself, -0.0 differs from +0.0, a NaN with another payload differs.  An operand that overlaps a declared
+                  one BY THE BYTE RANGE its elements span counts as written (``frozen_bn_act_forward(x, ..., out=x)``).
+  outside a view  the whole storage of every declared operand is copied before the call; afterwards every byte of it that the
+                  operand's elements do not address is unchanged: the other columns of ``tokens_from_levels(out=buffer[..., :d])``,
+                  the rows around ``assign_match(out=match_dev[at:...])``.  Whole storages are copied, which is why this is opt-in
+                  and stays with the small shapes of tests/test_gpu_write_sets.py.
+  bands           with ``guard`` (the installed tests/guard.py), after each entry the bands of the buffers allocated inside it and of
+                  the storages of its tensor operands; ``finish_bands()`` (``assert_ok`` calls it) checks every band once more
+                  when the case ends, and damage in a buffer that was clean when its own entry returned is an error against
+                  "a later launch", with the entry the buffer was allocated in.  The guard steps aside for the harness's own
+                  allocations (copies, masks, the float64 references).
+The ``WRITES`` rule: the table names, for EVERY checked entry, the parameters the call may write -- ``out``, ``scores`` of
+``bias_softmax_``, ``x`` of ``zero_masked_rows_``, a dict key by its dotted name (``class_head.out``) -- and most entries get ``()``;
+no wildcards; an entry without a rule is an error.  The two FusedAdamW methods, whose operands are not arguments, have a callable
+that returns the allowed tensors from the snapshot.  The ``out`` that the two attention backwards REQUIRE is the saved forward
+output, an operand: it is not in their write sets.  tests/test_shadow_complete.py holds the table complete.
+What this cannot see: a write farther from an allocation than one band (2 MiB, the largest row tile of csrc/ times its widest row:
+tests/guard.py has the derivation); a write into the payload of a tensor that is neither an operand of the call nor guarded (the
+weights of a network built before the guard, torch's own results); a write that stores the value that was there; and memory that
+does not come from a covered allocator.  profiles/r29/ has the tables of the composed cases: no entry wrote outside its set.
 """
 from __future__ import annotations
 
 import collections
+import contextlib
 import dataclasses
 import inspect
 import math
@@ -216,6 +245,8 @@ class Record:
     failing: int
     checked: int
     where: str
+    kind: str = "values"                     # "writes": the record Shadow(writes=True) adds per call (failing / checked in elements of
+                                             # operands, bytes outside an out= view and bytes of guard bands)
 
 
 def _compare(c: Cmp):
@@ -1622,6 +1653,150 @@ LAUNCH_INSIDE_ENTRY = frozenset({
 })
 
 
+# ------------------------------------------------------------------------------------------------------------ write sets
+# For every checked entry, the parameters the call is ALLOWED to write (``Shadow(writes=True)``); every other tensor operand must
+# come back bit-identical.  A dotted name is a key of a dict parameter ("class_head.out": ``class_head["out"]``, where the caller may
+# hand in the destination).  No wildcards; tests/test_shadow_complete.py holds that the keys are exactly the checked entries, that
+# every name is a parameter and that every parameter called ``out`` is declared.  The two FusedAdamW methods take their operands
+# from the optimizer: a callable (the snapshot dictionary, which holds ``self`` as before the call) -> the tensors it may write.
+def _adamw_clip_writes(a):
+    """The clip reads the gradients and arms a coefficient in a workspace of its own: it may write no parameter, gradient or state."""
+    return []
+
+
+def _adamw_step_writes(a):
+    """Parameter, exp_avg, exp_avg_sq and step of every parameter that has a gradient."""
+    opt, out = a["self"], []
+    for group in opt.param_groups:
+        for p in group["params"]:
+            if p.grad is not None:
+                out.append(p)
+                out += [v for v in (opt.state.get(p) or {}).values() if torch.is_tensor(v)]
+    return out
+
+
+WRITES: Dict[str, object] = {
+    "ms_deform_attn_forward": (), "ms_deform_attn_forward_fused": (), "value_to_head_major": (), "value_proj_head_major": (),
+    "encoder_proj": (),
+    "linear_k256": ("out",), "ffn_k256": ("out",), "ffn_ln_k256": ("out",),
+    "linear_ln_k256": ("out", "extra.out_plus_pos"),
+    "add_layer_norm": ("out",),
+    "relation_bias": (),
+    "bias_softmax_": ("scores",),
+    "relation_attention": (), "relation_attention_boxes": (), "_relation_attention_train": (), "_relation_attention_backward": (),
+    "relation_bias_backward": (), "ms_deform_attn_backward": (), "ms_deform_attn_backward_fused": (),
+    "box_refine": (), "sine_pos_embed": (),
+    "zero_masked_rows_": ("x",),
+    "row_max": (),
+    "box_head_k256": ("class_head.out",),
+    "query_pos_k256": ("in_proj.qk", "in_proj.v"),
+    "topk": (), "detections_from_topk": (), "scaled_pos": (), "decoder_reference": (), "pyramid_points": (),
+    "tokens_from_levels": ("out",),
+    "ffn_train.ffn_k256_train": (), "ffn_train.ffn_k256_backward": (),
+    "ln_train.add_layer_norm_train": (), "ln_train.add_layer_norm_backward": (),
+    "attn_rel_train._relation_attention_boxes_train": (), "attn_rel_train._relation_attention_boxes_backward": (),
+    "msda_train_hm.ms_deform_attn_backward_fused_hm": ("grad_producer_out",),
+    "msda_train_hm.grad_value_from_head_major": ("out",),
+    "amp_train.add_layer_norm_mixed_train": (), "amp_train.add_layer_norm_mixed_backward": (),
+    "amp_train.ffn_mixed_train": (), "amp_train.ffn_mixed_backward": (),
+    "neck.group_norm_levels_forward": (), "neck.group_norm_levels_backward": (), "neck._masks_and_counts": (), "neck._sine_pos_packed": (),
+    "denoising.cdn_noise": (), "denoising.denoising_mask": (), "denoising.cdn_queries_forward": (), "denoising.cdn_embed_backward": (),
+    "criterion.match_cost": ("out",),
+    "criterion.assign_match": ("out",),
+    "criterion.set_loss_forward": (),
+    "optim.FusedAdamW._clip_fused": _adamw_clip_writes,
+    "optim.FusedAdamW._step_fused": _adamw_step_writes,
+    "backbones.epilogue.frozen_bn_act_forward": ("out",),
+    "backbones.epilogue.frozen_bn_act_backward": (), "backbones.epilogue.stem_bn_relu_maxpool": (),
+    "frontend.images.batch_images": (),
+}
+
+
+def operand_tensors(x, path=""):
+    """-> [(path, tensor)] of every tensor reachable from an argument: tensors, and those inside lists, tuples (a Noise too) and
+    dicts; the parameters and buffers of a module (``layers`` of box_head_k256 are nn.Linear); the parameters, their gradients and
+    the state of an optimizer (``self`` of the FusedAdamW methods)."""
+    if torch.is_tensor(x):
+        return [(path, x)] if x.layout == torch.strided else []
+    found = []
+    if isinstance(x, dict):
+        for k, v in x.items():
+            found += operand_tensors(v, f"{path}.{k}" if path else str(k))
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            found += operand_tensors(v, f"{path}[{i}]")
+    elif isinstance(x, torch.nn.Module):
+        for k, v in list(x.named_parameters()) + list(x.named_buffers()):
+            found.append((f"{path}.{k}", v))
+    elif isinstance(x, torch.optim.Optimizer):
+        i = 0
+        for group in x.param_groups:
+            for p in group["params"]:
+                found.append((f"{path}.param[{i}]", p))
+                if p.grad is not None:
+                    found += operand_tensors(p.grad, f"{path}.param[{i}].grad")
+                found += operand_tensors({k: v for k, v in (x.state.get(p) or {}).items()}, f"{path}.state[{i}]")
+                i += 1
+    return found
+
+
+def _declared(paths, operands):
+    """The operands a tuple of WRITES names: "out" names the argument and whatever it holds, "extra.out_plus_pos" one key."""
+    names = tuple(paths)
+    return [(p, t) for p, t in operands if any(p == n or p.startswith(n + ".") or p.startswith(n + "[") for n in names)]
+
+
+def byte_range(t):
+    """[lo, hi): the addresses the elements of ``t`` span (non-negative strides, as torch's are)."""
+    lo = t.data_ptr()
+    n = 0 if t.numel() == 0 else 1 + sum((s - 1) * st for s, st in zip(t.shape, t.stride()))
+    return lo, lo + n * t.element_size()
+
+
+def _overlaps(a, b):
+    (alo, ahi), (blo, bhi) = byte_range(a), byte_range(b)
+    return a.device == b.device and alo < bhi and blo < ahi
+
+
+_INT_OF_SIZE = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def int_bits(t):
+    """The elements of ``t`` as integers of the same size, so that a NaN equals itself and -0.0 differs from +0.0."""
+    t = t.detach()
+    if t.dtype == torch.bool:
+        return t.view(torch.uint8)
+    if t.is_complex():
+        t = torch.view_as_real(t)
+    return t if not t.is_floating_point() else t.view(_INT_OF_SIZE[t.element_size()])
+
+
+def storage_bytes(t):
+    """The whole storage ``t`` lives in, as a uint8 tensor (no copy)."""
+    return torch.Tensor.set_(torch.tensor([], dtype=torch.uint8, device=t.device), t.untyped_storage())
+
+
+def addressed_bytes(t, n):
+    """uint8 [n]: 1 at every byte of ``t``'s storage (of n bytes) that an element of ``t`` occupies."""
+    mask = torch.zeros(n, dtype=torch.uint8, device=t.device)
+    item = t.element_size()
+    if t.numel() and all(st > 0 or s == 1 for s, st in zip(t.shape, t.stride())):
+        mask.as_strided(tuple(t.shape) + (item,), tuple(s * item for s in t.stride()) + (1,), t.storage_offset() * item).fill_(1)
+    elif t.numel():                                            # an expanded view: the range its elements span
+        lo = t.storage_offset() * item
+        mask[lo:lo + byte_range(t)[1] - byte_range(t)[0]].fill_(1)
+    return mask
+
+
+@dataclasses.dataclass
+class _WriteWatch:
+    """What ``Shadow(writes=True)`` holds between the copies before a call and the comparison after it."""
+    kept: list                    # (path, tensor, copy): operands that must come back bit-identical
+    views: list                   # (storage bytes, copy of them, [(path, tensor)]): the storages of the declared operands
+    operands: list                # (path, tensor), all of them
+    mark: int                     # guard allocations before the call
+
+
 # ----------------------------------------------------------------------------------------------------------------- harness
 def patch_targets():
     """(owner, attribute, key, entries, host-only set) of every function the harness classifies: the functions of ops, and of every
@@ -1662,12 +1837,21 @@ def _copy(x):
 
 
 class Shadow:
-    """``Shadow(monkeypatch, fault=None, check=True)``; ``fault(name, call, bound_args, result, rerun) -> result`` may replace a
-    kernel's result before the check (the harness's own fault-injection test).  ``check=False`` installs only the counting
-    tripwires at the C boundary (``launches``): no wrapper, no reference, no error for a launch outside an entry."""
+    """``Shadow(monkeypatch, fault=None, check=True, writes=False, guard=None)``; ``fault(name, call, bound_args, result, rerun) ->
+    result`` may replace a kernel's result before the check (the harness's own fault-injection test), or write where the call
+    should not have.  ``check=False`` installs only the counting tripwires at the C boundary (``launches``): no wrapper, no
+    reference, no error for a launch outside an entry.  ``writes=True`` adds the write-set record of the module docstring to every
+    call; ``guard``: the installed tests/guard.py ``Guard`` whose bands it checks (needs ``writes=True``)."""
 
-    def __init__(self, monkeypatch, fault: Optional[Callable] = None, check: bool = True):
+    def __init__(self, monkeypatch, fault: Optional[Callable] = None, check: bool = True, writes: bool = False, guard=None):
         from relation_detr_amd import _lib
+        if guard is not None and not writes:
+            raise ValueError("Shadow(guard=...) needs writes=True: the bands are checked by the write-set record")
+        self.writes, self.guard = bool(writes), guard
+        # comparisons made: "operand_bits" (elements), "outside_view" and "bands" (bytes); "declared": the destinations handed in
+        self.write_checks: collections.Counter = collections.Counter()
+        self._bands_reported: set = set()
+        self._bands_done = False
         self.records: List[Record] = []
         self.calls: collections.Counter = collections.Counter()
         self.checked: collections.Counter = collections.Counter()
@@ -1720,20 +1904,28 @@ class Shadow:
             call = self.calls[name]
             self.calls[name] += 1
             copies = snapshot(bound.arguments) if snapshot is not None else {k: _copy(v) for k, v in bound.arguments.items()}
+            watch = self._watch(name, bound.arguments, copies if snapshot is not None else bound.arguments) if self.writes else None
             self.depth += 1
+            if self.guard is not None:
+                self.guard.active.append(name)
             try:
                 result = fn(*args, **kwargs)
                 if self.fault is not None:
                     result = self.fault(name, call, bound.arguments, result, fn)
             finally:
                 self.depth -= 1
+                if self.guard is not None:
+                    self.guard.active.pop()
+            if watch is not None:
+                with torch.no_grad(), self._paused():
+                    self._record_writes(name, call, watch)
             # the references are torch's own float64 operators, some of which have no deterministic variant (grid_sample's
             # backward): a step run under torch.use_deterministic_algorithms(True) is for the kernels, not for them
             strict, warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()
             torch.use_deterministic_algorithms(False)
             try:
                 # autocast off: the fp32 torch routes that give e32 must run in fp32 (float64 is never autocast)
-                with torch.no_grad(), torch.autocast("cuda", enabled=False):
+                with torch.no_grad(), torch.autocast("cuda", enabled=False), self._paused():
                     self._record(name, call, checker(copies, result))
             finally:
                 torch.use_deterministic_algorithms(strict, warn_only=warn)
@@ -1751,6 +1943,109 @@ class Shadow:
         self.checked[name] += checked
         self.records.append(Record(name, call, worst, failing, checked, where))
 
+    # ------------------------------------------------------------------------------------------------------- write sets
+    def _paused(self):
+        """The guard steps aside for the harness's own allocations (copies, masks, float64 references): no kernel writes them."""
+        return self.guard.pause() if self.guard is not None else contextlib.nullcontext()
+
+    def _watch(self, name, arguments, snapshot_arguments) -> _WriteWatch:
+        """Before the call: a copy of every operand that must come back unchanged, and of the whole storage of every declared one."""
+        with torch.no_grad(), self._paused():
+            operands = [(p, t) for k, v in arguments.items() for p, t in operand_tensors(v, k)]
+            rule = WRITES.get(name)
+            if rule is None:
+                self.errors.append(f"`{name}` has no WRITES entry")
+                rule = ()
+            declared = [("allowed", t) for t in rule(snapshot_arguments)] if callable(rule) else _declared(rule, operands)
+            written = {id(t) for _, t in declared}
+            self.write_checks["declared"] += len(declared)      # destinations handed in: without one there is no view to look outside of
+            kept, seen = [], set()
+            for p, t in operands:
+                if id(t) in written or id(t) in seen or t.numel() == 0 or any(_overlaps(t, d) for _, d in declared):
+                    continue                                   # frozen_bn_act_forward(x, ..., out=x): x is written
+                seen.add(id(t))
+                kept.append((p, t, t.detach().clone()))
+            views = {}
+            for p, t in declared:
+                if t.numel():
+                    key = (t.device, t.untyped_storage().data_ptr())
+                    if key not in views:
+                        raw = storage_bytes(t)
+                        views[key] = (raw, raw.clone(), [])
+                    views[key][2].append((p, t))
+            return _WriteWatch(kept, list(views.values()), operands, len(self.guard.allocations) if self.guard is not None else 0)
+
+    def _record_writes(self, name, call, w: _WriteWatch):
+        """After the call: one more record under the same op.  failing = changed elements of operands that are not in the write set
+        + changed bytes of a declared operand's storage that its elements do not address + changed bytes of guard bands."""
+        counts, labels = [], []
+        checked = 0
+        for p, t, before in w.kept:
+            counts.append((int_bits(t) != int_bits(before)).sum())
+            labels.append(("operand_bits", p, t, before))
+            checked += t.numel()
+            self.write_checks["operand_bits"] += t.numel()
+        for raw, before, members in w.views:
+            inside = torch.zeros(raw.numel(), dtype=torch.uint8, device=raw.device)
+            for _, t in members:
+                inside |= addressed_bytes(t, raw.numel())
+            outside = int(raw.numel()) - int(inside.sum())
+            counts.append(((raw != before) & (inside == 0)).sum())
+            labels.append(("outside_view", "/".join(p for p, _ in members), raw, torch.where(inside == 0, before, raw)))
+            checked += outside
+            self.write_checks["outside_view"] += outside
+        bad, failing, where = [], 0, ""
+        by_device: Dict[torch.device, List[int]] = {}
+        for i, c in enumerate(counts):
+            by_device.setdefault(c.device, []).append(i)
+        for idx in by_device.values():                                           # one read back per device
+            for i, v in zip(idx, torch.stack([counts[i] for i in idx]).tolist()):
+                if v:
+                    bad.append((i, int(v)))
+        for i, v in sorted(bad):
+            kind, p, now, before = labels[i]
+            failing += v
+            if kind == "operand_bits":
+                flat = int(torch.nonzero((int_bits(now) != int_bits(before)).reshape(-1))[0])
+                where = where or f"operand `{p}` is not in the write set and changed in {v} elements, the first at flat index {flat}"
+            else:
+                first = int(torch.nonzero(now != before)[0])
+                where = where or f"{v} bytes of the storage of `{p}` changed outside the view, the first at storage byte {first}"
+        if self.guard is not None:
+            mine = self.guard.allocations[w.mark:]
+            seen = {a.index for a in mine}
+            for _, t in w.operands:
+                a = self.guard.of(t)
+                if a is not None and a.index not in seen:
+                    seen.add(a.index)
+                    mine.append(a)
+            n = self.guard.band_bytes(mine)
+            checked += n
+            self.write_checks["bands"] += n
+            for d in self.guard.check(mine):
+                if (d.index, d.side) in self._bands_reported:
+                    continue
+                self._bands_reported.add((d.index, d.side))
+                failing += d.changed
+                where = where or str(d)
+        self.records.append(Record(name, call, math.inf if failing else 0.0, failing, checked, "writes: " + (where or "clean"), "writes"))
+
+    def finish_bands(self) -> List[str]:
+        """Once, when the case ends: every band of the guard again.  Damage in a buffer that was clean when its own entry returned
+        is an error against "a later launch", with the allocation's entry named."""
+        if self.guard is None or self._bands_done:
+            return []
+        self._bands_done = True
+        found = []
+        n = self.guard.band_bytes()
+        self.write_checks["bands"] += n
+        for d in self.guard.check():
+            if (d.index, d.side) not in self._bands_reported:
+                self._bands_reported.add((d.index, d.side))
+                found.append(f"a later launch wrote into the {d}")
+        self.errors += found
+        return found
+
     # ---------------------------------------------------------------------------------------------------------- results
     def called(self) -> set:
         return {r.op for r in self.records}
@@ -1762,10 +2057,18 @@ class Shadow:
         by = collections.OrderedDict()
         for r in sorted(self.records, key=lambda r: r.op):
             by.setdefault(r.op, []).append(r)
-        lines = [f"shadow checks: {title}", f"{'op':34s} {'calls':>6s} {'elements checked':>17s} {'max err/bound':>14s}  worst at"]
-        for op, rs in by.items():
+        writes = f" {'writes: checked / bad':>24s}" if self.writes else ""
+        lines = [f"shadow checks: {title}", f"{'op':34s} {'calls':>6s} {'elements checked':>17s} {'max err/bound':>14s}{writes}  worst at"]
+        for op, both in by.items():
+            rs, ws = [r for r in both if r.kind == "values"], [r for r in both if r.kind == "writes"]
             w = max(rs, key=lambda r: r.ratio)
-            lines.append(f"{op:34s} {len(rs):6d} {sum(r.checked for r in rs):17d} {w.ratio:14.4f}  call {w.call}: {w.where}")
+            column = f" {sum(r.checked for r in ws):15d} / {sum(r.failing for r in ws):<6d}" if self.writes else ""
+            lines.append(f"{op:34s} {len(rs):6d} {sum(r.checked for r in rs):17d} {w.ratio:14.4f}{column}  call {w.call}: {w.where}")
+            for r in ws:
+                if r.failing:
+                    lines.append(f"{'':34s} call {r.call}: {r.where}")
+        if self.writes:
+            lines.append("write checks: " + ", ".join(f"{k} {v}" for k, v in sorted(self.write_checks.items())))
         for e in sorted(set(self.errors)):
             lines.append("ERROR " + e)
         text = "\n".join(lines)
@@ -1773,6 +2076,7 @@ class Shadow:
         return text
 
     def assert_ok(self, expected_ops=None):
+        self.finish_bands()
         bad = self.failures()
         msgs = [f"{r.op} call {r.call}: {r.failing} elements over bound, worst ratio {r.ratio:.3g} at {r.where}" for r in bad[:20]]
         assert not self.errors, sorted(set(self.errors))

@@ -41,7 +41,11 @@ Training steps:
       torch.autocast(bfloat16), the front end's batch and every epilogue output of the ResNet-50 (5 x 7 planes at layer4) allocated
       under the pattern; the routes pinned by the launch counts the module gives (52 epilogues, 42 backwards, one stem pool)
 
-With ``RDETR_SHADOW_REPORTS=<directory>`` every case writes its report table there (profiles/r26/; T4: profiles/r28/)."""
+With ``RDETR_SHADOW_REPORTS=<directory>`` every case writes its report table there (profiles/r26/; T4: profiles/r28/).
+
+Every case is a builder (``eval_case``, ``t1_case`` ... ``t4_case``) that takes ``install(monkeypatch, pattern)``, what prepares the
+scratch memory before the harness stands, and the prefix of its report file: here ``dirty.poison``; tests/test_gpu_write_sets.py runs
+the same builders on guarded allocations (tests/guard.py), where the poison must not be installed."""
 import time
 
 import pytest
@@ -107,27 +111,27 @@ def ragged_pyramid(batch, shapes, dtype, seed=11):
     return feats, masks, pos
 
 
-def finish(sh, poison, title, name, started):
+def finish(sh, poison, title, name, started, prefix="dirty"):
     """The end of every case: the report, then no error, no failing record, every ratio below 1."""
     torch.cuda.synchronize()
     wall = time.perf_counter() - started
     text = sh.report(f"{title}; scratch memory 0x{poison.byte:02X} ({poison.fills} allocations, {poison.bytes / 2 ** 20:.1f} MiB filled); "
                      f"{wall:.2f} s under the harness")
     print("C launches: " + ", ".join(f"{k} x{v}" for k, v in sorted(sh.launches.items())))
-    _write_report(f"dirty_{name}_0x{poison.byte:02X}.txt", text, sh)
+    _write_report(f"{prefix}_{name}_0x{poison.byte:02X}.txt", text, sh)
     assert poison.fills > 0, "the poison saw no allocation"
     assert not sh.errors, sorted(set(sh.errors))
 
 
-def eval_case(monkeypatch, pattern, name, shapes, batch, dtype, queries, hybrid=1500):
+def eval_case(monkeypatch, pattern, name, shapes, batch, dtype, queries, hybrid=1500, install=dirty.poison, prefix="dirty"):
     net = network(queries, len(shapes), hybrid, dtype).eval()
     feats, masks, pos = ragged_pyramid(batch, shapes, dtype)
-    poison = dirty.poison(monkeypatch, pattern)
+    poison = install(monkeypatch, pattern)
     sh = shadow.Shadow(monkeypatch)
     started = time.perf_counter()
     det = _eval_run(net, feats, masks, pos, groups=1)
     dtype_name = "bf16" if dtype == BF16 else "fp32"
-    finish(sh, poison, f"{name}: eval, {dtype_name}, B = {batch}, {queries} queries, levels {shapes}", f"{name}_{dtype_name}", started)
+    finish(sh, poison, f"{name}: eval, {dtype_name}, B = {batch}, {queries} queries, levels {shapes}", f"{name}_{dtype_name}", started, prefix)
     assert det.shape == (batch, 300, 6) and bool(torch.isfinite(det).all())
     sh.assert_ok(EVAL_BF16_OPS_SMALL[name] if dtype == BF16 else EVAL_FP32_OPS)
     assert not sh.errors and max(_ratio_table(sh).values()) < 1.0
@@ -141,16 +145,20 @@ EVAL_BF16_OPS_SMALL = {"E1": EVAL_BF16_OPS, "E3": EVAL_BF16_OPS, "E2": EVAL_BF16
                        "E4": (EVAL_BF16_OPS - {"ffn_k256", "encoder_proj"}) | {"zero_masked_rows_"}}
 
 
-@PATTERNS
-def test_e1_resident_gather_odd_batch(monkeypatch, pattern):
-    sh = eval_case(monkeypatch, pattern, "E1", A, 3, BF16, 300)
+def e1_case(monkeypatch, pattern, **how):
+    sh = eval_case(monkeypatch, pattern, "E1", A, 3, BF16, 300, **how)
     assert sh.launches[RESIDENT] == E_LAYERS and sh.launches["rdetr_ffn_k256_bf16"] == E_LAYERS
     assert sh.launches["rdetr_encoder_proj_k256_bf16"] == E_LAYERS
+    return sh
 
 
 @PATTERNS
-def test_e2_below_the_row_threshold_301_queries(monkeypatch, pattern):
-    sh = eval_case(monkeypatch, pattern, "E2", A, 2, BF16, 301)
+def test_e1_resident_gather_odd_batch(monkeypatch, pattern):
+    e1_case(monkeypatch, pattern)
+
+
+def e2_case(monkeypatch, pattern, **how):
+    sh = eval_case(monkeypatch, pattern, "E2", A, 2, BF16, 301, **how)
     assert not sh.launches[RESIDENT] and sh.launches[QUERY_RUN] >= E_LAYERS
     assert sum(sh.launches[s] for s in HEAD_MAJOR) == E_LAYERS                               # S >= 4096: the head-major value
     assert not sh.launches["rdetr_ffn_k256_bf16"] and not sh.launches["rdetr_ffn_ln_k256_bf16"]   # the library GEMMs
@@ -159,44 +167,63 @@ def test_e2_below_the_row_threshold_301_queries(monkeypatch, pattern):
     assert sh.launches["rdetr_relation_attention_boxes_bf16"] == D_LAYERS - 1 and sh.launches["rdetr_relation_attention_bf16"] == 1
     assert not sh.launches["rdetr_relation_bias_ws_f32"] and not sh.launches["rdetr_relation_bias_f32"]
     assert not sh.launches["rdetr_bias_softmax_f32"]
+    return sh
+
+
+@PATTERNS
+def test_e2_below_the_row_threshold_301_queries(monkeypatch, pattern):
+    e2_case(monkeypatch, pattern)
+
+
+def e3_case(monkeypatch, pattern, **how):
+    sh = eval_case(monkeypatch, pattern, "E3", C, 2, BF16, 300, **how)
+    assert sh.launches[QUERY_RUN] >= E_LAYERS and not sh.launches[RESIDENT]
+    assert sh.launches["rdetr_ffn_k256_bf16"] == E_LAYERS
+    return sh
 
 
 @PATTERNS
 def test_e3_five_levels(monkeypatch, pattern):
-    sh = eval_case(monkeypatch, pattern, "E3", C, 2, BF16, 300)
-    assert sh.launches[QUERY_RUN] >= E_LAYERS and not sh.launches[RESIDENT]
-    assert sh.launches["rdetr_ffn_k256_bf16"] == E_LAYERS
+    e3_case(monkeypatch, pattern)
+
+
+def e4_case(monkeypatch, pattern, dtype, **how):
+    sh = eval_case(monkeypatch, pattern, "E4", D, 1, dtype, 77, hybrid=700, **how)
+    assert not any(sh.launches[s] for s in HEAD_MAJOR) and not sh.launches[RESIDENT]          # S < 4096: [B,S,H,D]
+    assert sh.launches["rdetr_topk"] == 2                        # 77 of 1,462 proposals, 300 of 77 x 91 scores: one launch each
+    gathers = [s for s in sh.launches if s.startswith("rdetr_msda_forward_fused") and s.endswith("_bf16" if dtype == BF16 else "_f32")]
+    assert sum(sh.launches[s] for s in gathers) == E_LAYERS + D_LAYERS
+    return sh
 
 
 @PATTERNS
 @pytest.mark.parametrize("dtype", [BF16, F32], ids=["bf16", "fp32"])
 def test_e4_short_pyramid_77_queries(monkeypatch, pattern, dtype):
-    sh = eval_case(monkeypatch, pattern, "E4", D, 1, dtype, 77, hybrid=700)
-    assert not any(sh.launches[s] for s in HEAD_MAJOR) and not sh.launches[RESIDENT]          # S < 4096: [B,S,H,D]
-    assert sh.launches["rdetr_topk"] == 2                        # 77 of 1,462 proposals, 300 of 77 x 91 scores: one launch each
-    gathers = [s for s in sh.launches if s.startswith("rdetr_msda_forward_fused") and s.endswith("_bf16" if dtype == BF16 else "_f32")]
-    assert sum(sh.launches[s] for s in gathers) == E_LAYERS + D_LAYERS
+    e4_case(monkeypatch, pattern, dtype)
+
+
+def e5_case(monkeypatch, pattern, **how):
+    sh = eval_case(monkeypatch, pattern, "E5", A, 1, F32, 300, **how)
+    assert sh.launches["rdetr_msda_forward_fused_f32"] + sh.launches["rdetr_msda_forward_fused_ex_f32"] == E_LAYERS + D_LAYERS
+    assert sh.launches["rdetr_bias_softmax_f32"] == D_LAYERS and sh.launches["rdetr_relation_bias_ws_f32"] == D_LAYERS - 1
+    assert not any(v for k, v in sh.launches.items() if k.endswith("_bf16"))
+    return sh
 
 
 @PATTERNS
 def test_e5_fp32_entries(monkeypatch, pattern):
-    sh = eval_case(monkeypatch, pattern, "E5", A, 1, F32, 300)
-    assert sh.launches["rdetr_msda_forward_fused_f32"] + sh.launches["rdetr_msda_forward_fused_ex_f32"] == E_LAYERS + D_LAYERS
-    assert sh.launches["rdetr_bias_softmax_f32"] == D_LAYERS and sh.launches["rdetr_relation_bias_ws_f32"] == D_LAYERS - 1
-    assert not any(v for k, v in sh.launches.items() if k.endswith("_bf16"))
+    e5_case(monkeypatch, pattern)
 
 
 # ------------------------------------------------------------------------------------------------------------- training steps
-@PATTERNS
-@pytest.mark.parametrize("deterministic", [False, True], ids=["atomic", "deterministic"])
-def test_t1_all_training_routes(monkeypatch, pattern, deterministic):
+def t1_case(monkeypatch, pattern, deterministic, install=dirty.poison, prefix="dirty"):
     from relation_detr_amd import options
     batch, groups, per_group, queries = 3, 2, 13, 301
     net = options.apply(network(queries).train(), **dict.fromkeys(TRAIN_SWITCHES, True))
     feats, masks, pos = ragged_pyramid(batch, A, BF16)
     label, box, mask = _dn_inputs(batch, groups, per_group, queries, torch.Generator().manual_seed(5))
     assert (groups * per_group + queries) % 8 and (groups * per_group + queries) % 16
-    poison = dirty.poison(monkeypatch, pattern)
+    poison = install(monkeypatch, pattern)
     sh = shadow.Shadow(monkeypatch)
     was, started = torch.are_deterministic_algorithms_enabled(), time.perf_counter()
     try:
@@ -206,25 +233,35 @@ def test_t1_all_training_routes(monkeypatch, pattern, deterministic):
     finally:
         torch.use_deterministic_algorithms(was)
     mode = "deterministic" if deterministic else "atomic"
-    finish(sh, poison, f"T1: bf16 training step, all six switches ({mode}), A, B = 3, 26 denoising + 301 matching queries", f"T1_{mode}", started)
+    finish(sh, poison, f"T1: bf16 training step, all six switches ({mode}), A, B = 3, 26 denoising + 301 matching queries", f"T1_{mode}", started, prefix)
     assert_all_training_routes(sh, net)
     assert sh.launches["rdetr_msda_backward_fused_hm_bf16"] == E_LAYERS                      # msda_train_head_major
     assert sh.launches["rdetr_relation_attention_boxes_train_bf16"] == sh.launches["rdetr_relation_attention_boxes_backward_bf16"] == D_LAYERS - 1
+    return sh
 
 
 @PATTERNS
-def test_t2_mixed_precision_detector_two_steps(monkeypatch, pattern):
+@pytest.mark.parametrize("deterministic", [False, True], ids=["atomic", "deterministic"])
+def test_t1_all_training_routes(monkeypatch, pattern, deterministic):
+    t1_case(monkeypatch, pattern, deterministic)
+
+
+def t2_case(monkeypatch, pattern, install=dirty.poison, prefix="dirty"):
     inputs = mixed_inputs(batch=3, maps=M, counts=(17, 0, 1), hard=(1,))
     rows, cols = torch.arange(8, device=DEV) * 488 // 8, torch.arange(13, device=DEV) * 792 // 13
     assert int((~inputs[1][1][rows][:, cols]).sum()) == 2            # the coarsest level's view of the middle image: 2 x 1 valid pixels
-    poison = dirty.poison(monkeypatch, pattern)
+    poison = install(monkeypatch, pattern)
     mixed_two_steps(monkeypatch, inputs, M, f"T2: mixed-precision detector, two steps, M, B = 3, boxes 17 / 0 / 1; scratch memory 0x{pattern:02X}",
-                    f"dirty_T2_0x{pattern:02X}.txt")
+                    f"{prefix}_T2_0x{pattern:02X}.txt")
     assert poison.fills > 0
 
 
 @PATTERNS
-def test_t3_fp32_detector_step(monkeypatch, pattern):
+def test_t2_mixed_precision_detector_two_steps(monkeypatch, pattern):
+    t2_case(monkeypatch, pattern)
+
+
+def t3_case(monkeypatch, pattern, install=dirty.poison, prefix="dirty"):
     g = torch.Generator().manual_seed(29)
     maps = ((13, 21), (7, 11), (4, 6))
     feats = [torch.randn(3, c, h, w, generator=g).to(DEV) for c, (h, w) in zip((16, 24, 40), maps)]
@@ -237,18 +274,27 @@ def test_t3_fp32_detector_step(monkeypatch, pattern):
     targets = [{"labels": torch.randint(0, 11, (n,), generator=g).to(DEV),
                 "boxes": torch.cat((0.15 + 0.7 * torch.rand(n, 2, generator=g), 0.05 + 0.25 * torch.rand(n, 2, generator=g)), -1).to(DEV)}
                for n in counts]
-    poison = dirty.poison(monkeypatch, pattern)
+    poison = install(monkeypatch, pattern)
     fp32_step(monkeypatch, (feats, mask.to(DEV), targets), f"T3: fp32 detector step, three images, maps {maps}; scratch memory 0x{pattern:02X}",
-              f"dirty_T3_0x{pattern:02X}.txt")
+              f"{prefix}_T3_0x{pattern:02X}.txt")
+    assert poison.fills > 0
+
+
+@PATTERNS
+def test_t3_fp32_detector_step(monkeypatch, pattern):
+    t3_case(monkeypatch, pattern)
+
+
+def t4_case(monkeypatch, pattern, install=dirty.poison, prefix="dirty"):
+    poison = install(monkeypatch, pattern)
+    started = time.perf_counter()
+    sh, model = image_steps(monkeypatch, 1, autocast=True)
+    print(f"T4 under the harness: {time.perf_counter() - started:.1f} s")
+    check_image_case(sh, model, f"T4: mixed-precision detector step from three float images, R50 backbone; scratch memory 0x{pattern:02X}",
+                     f"{prefix}_T4_0x{pattern:02X}.txt", IMAGES_MIXED_OPS, 1, 1, "_bf16")
     assert poison.fills > 0
 
 
 @PATTERNS
 def test_t4_mixed_precision_detector_step_from_images(monkeypatch, pattern):
-    poison = dirty.poison(monkeypatch, pattern)
-    started = time.perf_counter()
-    sh, model = image_steps(monkeypatch, 1, autocast=True)
-    print(f"T4 under the harness: {time.perf_counter() - started:.1f} s")
-    check_image_case(sh, model, f"T4: mixed-precision detector step from three float images, R50 backbone; scratch memory 0x{pattern:02X}",
-                     f"dirty_T4_0x{pattern:02X}.txt", IMAGES_MIXED_OPS, 1, 1, "_bf16")
-    assert poison.fills > 0
+    t4_case(monkeypatch, pattern)

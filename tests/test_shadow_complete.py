@@ -341,3 +341,48 @@ def test_a_checked_entry_bound_by_name_is_patched_there_too(monkeypatch):
     from relation_detr_amd.backbones import epilogue, resnet
     assert resnet.stem_bn_relu_maxpool is epilogue.stem_bn_relu_maxpool and resnet.frozen_bn_act is epilogue.frozen_bn_act
     assert resnet.frozen_bn_act.__globals__["frozen_bn_act_forward"].shadow_key == "backbones.epilogue.frozen_bn_act_forward"
+
+
+# ------------------------------------------------------------------------------------------------------------ write sets
+def _entry_functions():
+    """{key: the function} of every checked entry, as the harness finds them."""
+    return {key: getattr(owner, attr) for owner, attr, key, entries, _ in shadow.patch_targets() if key in entries}
+
+
+def test_every_checked_entry_has_a_write_set_and_no_other_key_does():
+    entries = set(shadow.KERNEL_ENTRIES) | set(shadow.TRAIN_ENTRIES)
+    assert set(shadow.WRITES) == entries, (sorted(entries - set(shadow.WRITES)), sorted(set(shadow.WRITES) - entries))
+    assert set(_entry_functions()) == entries
+    for key, rule in shadow.WRITES.items():
+        assert callable(rule) or (isinstance(rule, tuple) and all(isinstance(n, str) and n and "*" not in n for n in rule)), key
+    # callables only where the operands are not arguments: the two launching methods of the optimizer
+    assert {k for k, rule in shadow.WRITES.items() if callable(rule)} == {"optim.FusedAdamW._clip_fused", "optim.FusedAdamW._step_fused"}
+    assert all(getattr(shadow.TRAIN_ENTRIES[k], "snapshot", None) is not None for k, rule in shadow.WRITES.items() if callable(rule))
+
+
+def test_every_name_of_a_write_set_is_a_parameter_and_every_out_is_declared():
+    functions = _entry_functions()
+    for key, rule in shadow.WRITES.items():
+        params = inspect.signature(functions[key]).parameters
+        if callable(rule):
+            assert list(params) [:1] == ["self"], key
+            continue
+        for name in rule:
+            assert name.split(".")[0] in params, f"{key}: `{name}` is no parameter of {list(params)}"
+        # a destination: a parameter called out (or ..._out) that may be left out.  The `out` the two attention backwards REQUIRE is
+        # the saved forward output, an operand they read: it must come back unchanged and is held to that below
+        outs = [n for n, p in params.items() if (n == "out" or n.endswith("_out")) and p.default is None]
+        assert set(outs) <= set(rule), f"{key}: takes {outs}, declares {rule}"
+        saved = [n for n, p in params.items() if n == "out" and p.default is inspect.Parameter.empty]
+        assert not set(saved) & set(rule), f"{key}: the saved forward output is read-only"
+    assert {k for k, f in functions.items() if inspect.signature(f).parameters.get("out", None) is not None
+            and inspect.signature(f).parameters["out"].default is inspect.Parameter.empty} == {
+        "_relation_attention_backward", "attn_rel_train._relation_attention_boxes_backward"}
+    declared = {k for k, rule in shadow.WRITES.items() if rule and not callable(rule)}
+    assert {"add_layer_norm", "linear_k256", "ffn_k256", "ffn_ln_k256", "linear_ln_k256", "tokens_from_levels", "criterion.assign_match",
+            "msda_train_hm.ms_deform_attn_backward_fused_hm", "backbones.epilogue.frozen_bn_act_forward", "bias_softmax_",
+            "zero_masked_rows_"} <= declared
+    # a function whose name ends in an underscore works in place: its first parameter is declared
+    for key, fn in functions.items():
+        if key.endswith("_") and not callable(shadow.WRITES[key]):
+            assert next(iter(inspect.signature(fn).parameters)) in shadow.WRITES[key], key
