@@ -14,15 +14,31 @@ reference's ``bf16 * fp32`` promotion returns fp32 maps (the neck's documented d
 """
 from __future__ import annotations
 
+import functools
 from typing import Callable, Dict, List, Optional, Sequence, Tuple, Type, Union
 
 import torch
 from torch import Tensor, nn
 from torch.nn.modules.batchnorm import _BatchNorm
 
+from .. import derived
 from .epilogue import frozen_bn_act, stem_bn_relu_maxpool
 
 _FUSED_DTYPES = (torch.float32, torch.bfloat16)
+
+# FrozenBatchNorm2d's folded (scale, shift) pair: sources are the module's four buffers
+_SCALE_SHIFT = derived.DerivedCache(kind="frozen_bn_scale_shift")
+
+
+def _scale_shift(eps, weight, bias, running_mean, running_var):
+    w, b, rm, rv = (t.detach().float() for t in (weight, bias, running_mean, running_var))
+    scale = w * (rv + eps).rsqrt()
+    return scale, b - rm * scale
+
+
+def _fill_scale_shift(eps, pair, *buffers):
+    for dst, src in zip(pair, _scale_shift(eps, *buffers)):
+        dst.copy_(src)
 
 
 class FrozenBatchNorm2d(nn.Module):
@@ -36,7 +52,6 @@ class FrozenBatchNorm2d(nn.Module):
         self.register_buffer("bias", torch.zeros(num_features))
         self.register_buffer("running_mean", torch.zeros(num_features))
         self.register_buffer("running_var", torch.ones(num_features))
-        self._cache: Tuple[Optional[tuple], Optional[Tuple[Tensor, Tensor]]] = (None, None)
 
     def _load_from_state_dict(self, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
         state_dict.pop(prefix + "num_batches_tracked", None)
@@ -53,13 +68,13 @@ class FrozenBatchNorm2d(nn.Module):
         """The fp32 ``[C]`` pair ``forward`` multiplies and adds: ``w * (rv + eps).rsqrt()`` and ``b - rm * scale``, the same
         operations on the same device.  Computed once per state of the buffers (their ``_version``, storage and device)."""
         buffers = (self.weight, self.bias, self.running_mean, self.running_var)
-        key = tuple((t.data_ptr(), t._version, t.device, t.dtype) for t in buffers) + (self.eps,)
-        if self._cache[0] != key:
+        eps = self.eps
+
+        def build():
             with torch.no_grad():
-                w, b, rm, rv = (t.detach().float() for t in buffers)
-                scale = w * (rv + self.eps).rsqrt()
-                self._cache = (key, (scale, b - rm * scale))
-        return self._cache[1]
+                return _scale_shift(eps, *buffers)
+        fill = functools.partial(_fill_scale_shift, eps) if derived.active() is not None else None      # only a ledger keeps it
+        return _SCALE_SHIFT.get(buffers, build, fill, extra=eps)
 
     def __repr__(self) -> str:
         return f"{self.__class__.__name__}({self.weight.shape[0]}, eps={self.eps})"

@@ -17,7 +17,7 @@ from typing import Callable, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, derived
 
 
 class ImageGroups:
@@ -78,16 +78,35 @@ class GraphedCall:
         (from another thread) while some GraphedCall is being built raises instead of racing it;
       * each instance owns a private memory pool (torch's default for a new CUDAGraph); the tensors it returns live there and
         are overwritten by its next replay -- two instances never share buffers;
-      * replays of DIFFERENT instances may overlap on different streams once both are built."""
+      * replays of DIFFERENT instances may overlap on different streams once both are built.
+
+    Weights and the copies derived from them (derived.py).  The captured kernels read the weights at
+    their captured addresses, and the package's derived copies of them (fragment-order packs, merged / batched projections,
+    fp32 copies, folded batch-norm pairs) and level tables at theirs.  The warm-up and the capture record every such copy in
+    ``self.ledger``:
+      * C1, eager: independent of any graph, the next eager forward after a change torch signals (version bump, new address of
+        any source -- biases and buffers included --, new tensor object, new dtype or device) uses freshly derived data;
+      * C2, pinning: while this object lives, no device tensor its warm-up or capture obtained from one of those caches is
+        freed, whatever the caches evict or rebuild for eager use;
+      * C3, replay: before each replay the ledger is walked on the host.  A source that changed where it stands (in-place op,
+        ``load_state_dict``, an optimizer step: same address, shape, dtype, device) has its copy rebuilt INTO the pinned
+        buffer on the replaying stream, so the replay equals an eager forward of a freshly built net with the same state.  A
+        source that moved (``p.data = t``, ``net.to(dtype)``, ``load_state_dict(assign=True)``) or died raises RdetrError
+        naming the tensor, before anything is launched: build a new GraphedCall.  ``check_weights=False`` skips the walk for
+        callers who freeze their weights (the behaviour before the ledger existed: a changed weight is then NOT noticed);
+      * C4, unsignalled writes: a write through ``.data`` (``p.data.mul_()``) bumps no version and is invisible to the walk.
+        After one, call ``refresh_weights()`` (rebuilds every pinned copy in place) and ``derived.drop_all()`` for eager use."""
 
     _build_lock = threading.Lock()
 
-    def __init__(self, fn: Callable, example_inputs: Sequence[torch.Tensor], warmup: int = 3):
+    def __init__(self, fn: Callable, example_inputs: Sequence[torch.Tensor], warmup: int = 3, check_weights: bool = True):
         if not example_inputs or not all(t.is_cuda for t in example_inputs):
             raise _lib.RdetrError("GraphedCall needs device tensors (there is no CPU path)")
         _lib.load()
         self._fn = fn
         self._inputs = list(example_inputs)             # the captured objects: replay reads these buffers
+        self.check_weights = bool(check_weights)
+        self.ledger = derived.Ledger()                  # every derived copy / level table the captured kernels read
         if torch.cuda.is_current_stream_capturing():
             raise _lib.RdetrError("GraphedCall cannot be built inside another capture")
         if not GraphedCall._build_lock.acquire(blocking=False):
@@ -97,7 +116,8 @@ class GraphedCall:
             torch.cuda.synchronize()                    # nothing of this process in flight: earlier graphs' replays have drained
             side = torch.cuda.Stream(device=self._inputs[0].device)
             side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side), torch.no_grad():  # warm-up outside capture: host-side caches, lazy handles, autotuning
+            with torch.cuda.stream(side), torch.no_grad(), derived.recording(self.ledger):  # warm-up outside capture: host-side
+                                                        # caches, lazy handles, autotuning
                 for _ in range(max(1, warmup)):
                     fn(*self._inputs)
             torch.cuda.current_stream().wait_stream(side)
@@ -105,9 +125,10 @@ class GraphedCall:
             self._graph = torch.cuda.CUDAGraph()
             # thread_local: other threads of the process (the RCCL watchdog of an initialised process group polls events)
             # must not invalidate the capture
-            with torch.cuda.graph(self._graph, capture_error_mode="thread_local"), torch.no_grad():
+            with torch.cuda.graph(self._graph, capture_error_mode="thread_local"), torch.no_grad(), derived.recording(self.ledger):
                 self._outputs = fn(*self._inputs)
             torch.cuda.synchronize()
+            self.ledger.name_sources(_modules_of(fn))
         finally:
             GraphedCall._build_lock.release()
 
@@ -117,9 +138,40 @@ class GraphedCall:
         if GraphedCall._build_lock.locked():
             raise _lib.RdetrError("a GraphedCall is being built on another thread: replays must wait for it (device idle during capture)")
         for dst, src in zip(self._inputs, inputs):
+            if src is not dst and (src.shape != dst.shape or src.dtype != dst.dtype):
+                raise _lib.RdetrError("GraphedCall: input shape / dtype differs from the captured one")
+        if self.check_weights:
+            self.ledger.refresh()                       # raises before anything is launched; rebuilds on the replaying stream
+        for dst, src in zip(self._inputs, inputs):
             if src is not dst:
-                if src.shape != dst.shape or src.dtype != dst.dtype:
-                    raise _lib.RdetrError("GraphedCall: input shape / dtype differs from the captured one")
                 dst.copy_(src, non_blocking=True)
         self._graph.replay()
         return self._outputs
+
+    def refresh_weights(self) -> int:
+        """Rebuild EVERY derived copy this graph pinned from its current source, in place, on the current stream -- the remedy
+        after a write torch does not signal (``p.data.mul_()``).  Returns the number of copies rebuilt."""
+        return self.ledger.refresh(force=True)
+
+
+def _modules_of(fn) -> list:
+    """The nn.Modules a callable closes over or is bound to (ImageGroups and functools.partial looked through): their parameter
+    names go into the ledger's error messages."""
+    found, seen, todo = [], set(), [fn]
+    while todo:
+        f = todo.pop()
+        if id(f) in seen:
+            continue
+        seen.add(id(f))
+        if isinstance(f, torch.nn.Module):
+            found.append(f)
+            continue
+        todo += [getattr(f, name) for name in ("__self__", "_fn", "func", "__wrapped__") if getattr(f, name, None) is not None]
+        for cell in getattr(f, "__closure__", None) or ():
+            try:
+                v = cell.cell_contents
+            except ValueError:
+                continue
+            if isinstance(v, torch.nn.Module) or callable(v):
+                todo.append(v)
+    return found

@@ -16,8 +16,16 @@ import warnings
 import torch
 from torch import Tensor, nn
 
-from . import amp_train, ln_train, msda_train_hm, ops, rowtail
+from . import amp_train, derived, ln_train, msda_train_hm, ops, rowtail
 from . import options as _options
+
+# [sampling_offsets ; attention_weights] as one projection, per module: sources are all four tensors (weights AND biases)
+_MERGED_QUERY = derived.DerivedCache(kind="merged_query_projection")
+
+
+def _fill_merged(merged, so_w, so_b, aw_w, aw_b):
+    torch.cat([so_w.detach(), aw_w.detach()], 0, out=merged[0])
+    torch.cat([so_b.detach(), aw_b.detach()], 0, out=merged[1])
 
 
 def sampling_locations(reference_points: Tensor, offsets: Tensor, spatial_shapes: Tensor, num_points: int) -> Tensor:
@@ -80,16 +88,14 @@ class MultiScaleDeformableAttention(nn.Module):
         one GEMM writes [rows, 2*H*L*P | H*L*P] and the kernel reads the two column slices in place.  Cached until a
         parameter changes (the separate nn.Linear modules stay the owners: state_dict keys are the reference's)."""
         so, aw = self.sampling_offsets, self.attention_weights
-        key = (so.weight._version, so.bias._version, aw.weight._version, aw.bias._version, so.weight.data_ptr(),
-               aw.weight.data_ptr(), so.weight.dtype, so.weight.device)
-        cache = getattr(self, "_merged_cache", None)
-        if cache is None or cache[0] != key:
+
+        def build():
             with torch.no_grad():
-                cache = (key, torch.cat([so.weight, aw.weight], 0).contiguous(), torch.cat([so.bias, aw.bias], 0).contiguous())
+                merged = (torch.cat([so.weight, aw.weight], 0).contiguous(), torch.cat([so.bias, aw.bias], 0).contiguous())
             if so.weight.is_cuda and not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(so.weight.device).synchronize()      # other streams (image groups) use it without an event
-            object.__setattr__(self, "_merged_cache", cache)
-        return cache[1], cache[2]
+            return merged
+        return _MERGED_QUERY.get((so.weight, so.bias, aw.weight, aw.bias), build, _fill_merged)
 
     def _projections(self, query: Tensor, value: Tensor, key_padding_mask, fill: bool = True, merged: bool = False,
                      want_value: bool = True):

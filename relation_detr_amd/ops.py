@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, rowtail
+from . import _lib, derived, rowtail
 
 
 _KEEP: "collections.deque" = collections.deque(maxlen=64)
@@ -54,21 +54,22 @@ def _require_contiguous(**named: torch.Tensor) -> None:
 # a recycled device address can never alias a stale entry): one D2H sync per new pyramid instead of
 # one per call (the reference syncs on every call, ms_deform_attn.py:313).
 _shape_cache: dict = {}
+derived.on_drop(_shape_cache.clear)
 
 
 def host_levels(spatial_shapes: torch.Tensor, level_start_index: torch.Tensor) -> Tuple[tuple, tuple]:
     key = (id(spatial_shapes), id(level_start_index))
+    # version AND address of the two tables: ``t.data = other`` keeps the object and its version and moves the data
+    state = (spatial_shapes._version, level_start_index._version, spatial_shapes.data_ptr(), level_start_index.data_ptr())
     hit = _shape_cache.get(key)
     if hit is not None:
         ref_s, ref_l, ver, levels = hit
-        if ref_s() is spatial_shapes and ref_l() is level_start_index and ver == (spatial_shapes._version,
-                                                                                 level_start_index._version):
+        if ref_s() is spatial_shapes and ref_l() is level_start_index and ver == state:
             return levels
     if len(_shape_cache) > 64:
         _shape_cache.clear()
     levels = (tuple(map(tuple, spatial_shapes.tolist())), tuple(level_start_index.tolist()))
-    _shape_cache[key] = (weakref.ref(spatial_shapes), weakref.ref(level_start_index),
-                         (spatial_shapes._version, level_start_index._version), levels)
+    _shape_cache[key] = (weakref.ref(spatial_shapes), weakref.ref(level_start_index), state, levels)
     return levels
 
 
@@ -91,6 +92,7 @@ MSDA_AUTO, MSDA_DIRECT, MSDA_WINDOW, MSDA_AUTO_PACKED = 0, 1, 2, 3     # RDETR_M
 
 
 _window_ok_cache: dict = {}
+derived.on_drop(_window_ok_cache.clear)
 
 
 def levels_window_ok(spatial_shapes: torch.Tensor, level_start_index: torch.Tensor, num_value: int) -> bool:
@@ -113,6 +115,7 @@ def levels_window_ok(spatial_shapes: torch.Tensor, level_start_index: torch.Tens
 
 
 _host_array_cache: dict = {}
+derived.on_drop(_host_array_cache.clear)
 
 
 def _host_level_arrays(spatial_shapes: torch.Tensor, level_start_index: torch.Tensor):
@@ -866,6 +869,9 @@ def relation_attention_boxes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
     tgt = tgt_boxes.detach().float().contiguous()
     # fp32 copies of the projection (the module holds it in the network dtype), kept until a parameter changes: converted per
     # call they were two small launches in every decoder layer's dependency chain
+    def fill_f32(copy, source):
+        copy.copy_(source.detach().reshape(copy.shape))
+
     def f32_copy(t, shape):
         def build():
             c = t.detach().float().reshape(shape).contiguous()
@@ -874,7 +880,7 @@ def relation_attention_boxes(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, 
             if not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(t.device).synchronize()      # other streams (image groups) pick it up without an event
             return c
-        return _REL_PROJ_F32.get((t,), build)
+        return _REL_PROJ_F32.get((t,), build, fill_f32)
     w = f32_copy(proj_weight, (num_heads, -1))
     pb = None if proj_bias is None else f32_copy(proj_bias, (-1,))
     out = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
@@ -959,14 +965,16 @@ def row_max(x: torch.Tensor) -> torch.Tensor:
 
 def _packed_k256(weight: torch.Tensor) -> torch.Tensor:
     """[256, 256] bf16 weight in MFMA-fragment order (rdetr_linear_pack_k256_bf16), cached until the tensor changes or dies."""
+    def fill(packed, source):
+        _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(source.data_ptr(), packed.data_ptr(), _stream_ptr(source)), "rdetr_linear_pack_k256_bf16")
+
     def build():
         packed = torch.empty(256 * 256, dtype=torch.bfloat16, device=weight.device)
-        st = _lib.load().rdetr_linear_pack_k256_bf16(weight.data_ptr(), packed.data_ptr(), _stream_ptr(weight))
-        _lib.check(st, "rdetr_linear_pack_k256_bf16")
+        fill(packed, weight)
         if not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream(weight.device).synchronize()
         return packed
-    return _LINEAR_PACKED.get((weight,), build)
+    return _LINEAR_PACKED.get((weight,), build, fill, "linear_packed.k256")
 
 
 def box_head_k256_supported(x: torch.Tensor, layers) -> bool:
@@ -1018,15 +1026,18 @@ def box_head_k256(xa: torch.Tensor, xb: Optional[torch.Tensor], layers, referenc
             cls = torch.empty(*xa.shape[:-1], C, dtype=torch.bfloat16, device=xa.device)
         _, _, ldc = _rows_view(cls, "box_head_k256")
 
-        def build():                                     # [C, 256] zero-padded to [256, 256], in fragment order
-            padded = torch.zeros(256, 256, dtype=torch.bfloat16, device=wc.device)
-            padded[:C].copy_(wc.detach())
+        def fill(packed, source):                        # [C, 256] zero-padded to [256, 256], in fragment order
+            padded = torch.zeros(256, 256, dtype=torch.bfloat16, device=source.device)
+            padded[:source.shape[0]].copy_(source.detach())
+            _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(padded.data_ptr(), packed.data_ptr(), _stream_ptr(padded)), "rdetr_linear_pack_k256_bf16")
+
+        def build():
             packed = torch.empty(256 * 256, dtype=torch.bfloat16, device=wc.device)
-            _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(padded.data_ptr(), packed.data_ptr(), _stream_ptr(wc)), "rdetr_linear_pack_k256_bf16")
+            fill(packed, wc)
             if not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(wc.device).synchronize()
             return packed
-        pwc = _LINEAR_PACKED.get((wc,), build)
+        pwc = _LINEAR_PACKED.get((wc,), build, fill, "linear_packed.class_weight")
         bcc = bc.detach().contiguous()
         st = _lib.load().rdetr_box_head_cls_k256_bf16(
             xa.data_ptr(), lda, None if xb is None else xb.data_ptr(), ldb, pw1.data_ptr(), _cptr(layers[0].bias),
@@ -1057,18 +1068,18 @@ def query_pos_k256_supported(emb: torch.Tensor, query: torch.Tensor, head_layers
 
 def _packed_k_halves(weight: torch.Tensor):
     """The two K halves of a [256, 512] bf16 weight, each in fragment order; cached until the tensor changes or dies."""
+    def fill(halves, source):
+        for h, packed in enumerate(halves):
+            half = source.detach()[:, 256 * h:256 * (h + 1)].contiguous()
+            _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(half.data_ptr(), packed.data_ptr(), _stream_ptr(half)), "rdetr_linear_pack_k256_bf16")
+
     def build():
-        halves = []
-        for h in range(2):
-            w = weight.detach()[:, 256 * h:256 * (h + 1)].contiguous()
-            packed = torch.empty(256 * 256, dtype=torch.bfloat16, device=weight.device)
-            st = _lib.load().rdetr_linear_pack_k256_bf16(w.data_ptr(), packed.data_ptr(), _stream_ptr(weight))
-            _lib.check(st, "rdetr_linear_pack_k256_bf16")
-            halves.append(packed)
+        halves = tuple(torch.empty(256 * 256, dtype=torch.bfloat16, device=weight.device) for _ in range(2))
+        fill(halves, weight)
         if not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream(weight.device).synchronize()
-        return tuple(halves)
-    return _LINEAR_PACKED.get((weight,), build)
+        return halves
+    return _LINEAR_PACKED.get((weight,), build, fill, "linear_packed.k_halves")
 
 
 def query_pos_k256(emb: torch.Tensor, query: torch.Tensor, head_layers, scale_layers=None, in_proj: Optional[dict] = None):
@@ -1117,17 +1128,18 @@ def query_pos_k256(emb: torch.Tensor, query: torch.Tensor, head_layers, scale_la
     pos = torch.empty(*query.shape, dtype=torch.bfloat16, device=query.device)
     qpp = torch.empty_like(pos)
     if in_proj is not None:
-        def build():                                     # Wq, Wk, Wv: three [256, 256] row blocks, each in fragment order
-            blocks = []
-            for i in range(3):
-                blk = w.detach()[256 * i:256 * (i + 1)].contiguous()
-                packed = torch.empty(256 * 256, dtype=torch.bfloat16, device=w.device)
-                _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(blk.data_ptr(), packed.data_ptr(), _stream_ptr(w)), "rdetr_linear_pack_k256_bf16")
-                blocks.append(packed)
+        def fill(blocks, source):                        # Wq, Wk, Wv: three [256, 256] row blocks, each in fragment order
+            for i, packed in enumerate(blocks):
+                blk = source.detach()[256 * i:256 * (i + 1)].contiguous()
+                _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(blk.data_ptr(), packed.data_ptr(), _stream_ptr(blk)), "rdetr_linear_pack_k256_bf16")
+
+        def build():
+            blocks = tuple(torch.empty(256 * 256, dtype=torch.bfloat16, device=w.device) for _ in range(3))
+            fill(blocks, w)
             if not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(w.device).synchronize()
-            return tuple(blocks)
-        pq, pk, pv = _LINEAR_PACKED.get((w,), build)
+            return blocks
+        pq, pk, pv = _LINEAR_PACKED.get((w,), build, fill, "linear_packed.in_proj")
         bias = b.detach().contiguous()
         (qk, ldqk), (v, ldv) = (d if d is not None else (torch.empty(*query.shape[:-1], n, dtype=torch.bfloat16, device=query.device), n)
                                 for d, n in zip(dst, (512, 256)))
@@ -1163,18 +1175,20 @@ def encoder_proj_supported(x: torch.Tensor, xq: torch.Tensor, wv: torch.Tensor, 
 
 def _packed_query_proj(wq: torch.Tensor) -> torch.Tensor:
     """[384 | 480, 256] merged query-projection weight -> two packed [256, 256] blocks (zero rows up to 512); cached."""
-    def build():
-        full = torch.zeros(512, 256, dtype=torch.bfloat16, device=wq.device)
-        full[:wq.shape[0]].copy_(wq.detach())
-        packed = torch.empty(2 * 256 * 256, dtype=torch.bfloat16, device=wq.device)
+    def fill(packed, source):
+        full = torch.zeros(512, 256, dtype=torch.bfloat16, device=source.device)
+        full[:source.shape[0]].copy_(source.detach())
         for blk in range(2):
-            st = _lib.load().rdetr_linear_pack_k256_bf16(full[256 * blk:256 * (blk + 1)].data_ptr(), packed.data_ptr() + blk * 256 * 256 * 2,
-                                                         _stream_ptr(wq))
-            _lib.check(st, "rdetr_linear_pack_k256_bf16")
+            rows = full[256 * blk:256 * (blk + 1)]
+            _lib.check(_lib.load().rdetr_linear_pack_k256_bf16(rows.data_ptr(), packed.data_ptr() + blk * 256 * 256 * 2, _stream_ptr(rows)), "rdetr_linear_pack_k256_bf16")
+
+    def build():
+        packed = torch.empty(2 * 256 * 256, dtype=torch.bfloat16, device=wq.device)
+        fill(packed, wq)
         if not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream(wq.device).synchronize()
         return packed
-    return _LINEAR_PACKED.get((wq,), build)
+    return _LINEAR_PACKED.get((wq,), build, fill, "linear_packed.query_proj")
 
 
 def encoder_proj(x: torch.Tensor, xq: torch.Tensor, wv: torch.Tensor, bv: Optional[torch.Tensor], wq: torch.Tensor,
@@ -1427,57 +1441,31 @@ def ffn_k256_supported(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor) -> b
             and F <= 4096 and w2.is_contiguous() and w2.data_ptr() % 16 == 0)
 
 
-class _PackedWeightCache:
-    """Packed (fragment-order) copies of weight tensors, tied to the tensor OBJECTS: an entry holds weak references to its
-    source tensors and is only a hit while every reference still resolves to the very tensor passed in and the versions
-    match.  A freed model whose storage address is recycled by the caching allocator for another model's weights (same
-    `data_ptr()`, same `_version` after an identical build sequence) can therefore never alias a stale packed copy --
-    the pattern `host_levels` uses for the shape tables.
-    Lifetime: a packed copy lives exactly as long as its source tensors.  The cache holds the ONLY reference to a copy whose
-    address a captured HIP graph may have baked in (relation_detr_amd/graph.py replays kernels that read it), so an entry is
-    never evicted while its sources are alive -- only entries whose sources are gone are pruned (every `prune_every` misses);
-    the dictionary simply grows with the number of live weight tensors (a size cap with `clear()` freed copies
-    that live graphs of a second network still read)."""
-
-    def __init__(self, prune_every: int = 64):
-        self._entries: dict = {}
-        self._prune_every = prune_every
-        self._misses = 0
-
-    def get(self, tensors, build):
-        key = tuple(id(t) for t in tensors)
-        ver = tuple((t._version, tuple(t.shape), t.data_ptr(), t.device) for t in tensors)
-        hit = self._entries.get(key)
-        if hit is not None:
-            refs, hver, packed = hit
-            if hver == ver and all(r() is t for r, t in zip(refs, tensors)):
-                return packed
-        self._misses += 1
-        if self._misses % self._prune_every == 0:       # drop the entries whose tensors are gone; live ones are never evicted
-            self._entries = {k: v for k, v in self._entries.items() if all(r() is not None for r in v[0])}
-        packed = build()
-        self._entries[key] = (tuple(weakref.ref(t) for t in tensors), ver, packed)
-        return packed
-
-    def __len__(self):
-        return len(self._entries)
+_PackedWeightCache = derived.DerivedCache     # the identity-keyed cache class (derived.py); every weight-derived copy goes through it
 
 
-_FFN_PACKED = _PackedWeightCache()        # (w1, w2) -> the fragment-order copy of a layer's two weight matrices
+# In-place rebuilds of the derived copies: every packer below hands its cache a ``fill(derived, *sources)`` that writes the copy of
+# the CURRENT sources into the buffers a captured graph reads, on the current stream (derived.Ledger.refresh), and runs the same
+# function on fresh buffers in ``build``.  The fills are nested functions that take the sources as ARGUMENTS and name no variable of
+# the enclosing call: a ledger that keeps one must hold no source tensor.
+_FFN_PACKED = _PackedWeightCache(kind="ffn_packed")        # (w1, w2) -> the fragment-order copy of a layer's two weight matrices
 
 
 def ffn_k256_packed_weights(w1: torch.Tensor, w2: torch.Tensor) -> torch.Tensor:
     """The (w1, w2) pair re-ordered for `ffn_k256` (rdetr_ffn_k256_pack_bf16); cached until either tensor changes or dies."""
+    def fill(packed, a, b):
+        st = _lib.load().rdetr_ffn_k256_pack_bf16(a.data_ptr(), b.data_ptr(), a.shape[0], packed.data_ptr(), _stream_ptr(a))
+        _lib.check(st, "rdetr_ffn_k256_pack_bf16")
+
     def build():
         F = w1.shape[0]
         packed = torch.empty(2 * 256 * F, dtype=torch.bfloat16, device=w1.device)
-        st = _lib.load().rdetr_ffn_k256_pack_bf16(w1.data_ptr(), w2.data_ptr(), F, packed.data_ptr(), _stream_ptr(w1))
-        _lib.check(st, "rdetr_ffn_k256_pack_bf16")
+        fill(packed, w1, w2)
         if not torch.cuda.is_current_stream_capturing():
             # once per weight update: other streams (image groups) pick the cached tensor up without an event of their own
             torch.cuda.current_stream(w1.device).synchronize()
         return packed
-    return _FFN_PACKED.get((w1, w2), build)
+    return _FFN_PACKED.get((w1, w2), build, fill)
 
 
 def ffn_k256(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
@@ -1545,8 +1533,8 @@ def ffn_ln_k256(x: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.T
 # K halves of a [256, 512] weight (_packed_k_halves), the three row blocks of an in_proj_weight [768, 256] (query_pos_k256) or a class
 # weight [C, 256] zero-padded to one block (box_head_k256).  The shapes tell the users apart -- each packs only the shape it checks
 # for, and a [256, 256] class weight gives the same single block either way -- so one tensor never gets two kinds of entry.
-_LINEAR_PACKED = _PackedWeightCache()
-_REL_PROJ_F32 = _PackedWeightCache()      # (pos_proj weight | bias,) -> fp32 copy
+_LINEAR_PACKED = _PackedWeightCache(kind="linear_packed")
+_REL_PROJ_F32 = _PackedWeightCache(kind="rel_proj_f32")      # (pos_proj weight | bias,) -> fp32 copy
 
 
 def linear_ln_k256_supported(x: torch.Tensor, weight: torch.Tensor, residual: torch.Tensor) -> bool:
@@ -1590,13 +1578,7 @@ def linear_ln_k256(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     if orows != rows or ldo % 8 or out.data_ptr() % 16:
         raise _lib.RdetrError("linear_ln_k256: out rows must be 16-byte aligned")
     lib = _lib.load()
-    def build():
-        packed = torch.empty(256 * 256, dtype=torch.bfloat16, device=weight.device)
-        _lib.check(lib.rdetr_linear_pack_k256_bf16(weight.data_ptr(), packed.data_ptr(), _stream_ptr(weight)), "rdetr_linear_pack_k256_bf16")
-        if not torch.cuda.is_current_stream_capturing():
-            torch.cuda.current_stream(weight.device).synchronize()
-        return packed
-    packed_w = _LINEAR_PACKED.get((weight,), build)
+    packed_w = _packed_k256(weight)
     st = lib.rdetr_linear_ln_k256_bf16(x.data_ptr(), ldx, packed_w.data_ptr(), None if bias is None else _cptr(bias),
                                        residual.data_ptr(), ldr, _cptr(gamma), _cptr(beta),
                                        float(eps), rows, out.data_ptr(), ldo, _stream_ptr(x))

@@ -23,11 +23,20 @@ import torch
 from torch import Tensor, nn
 from torch.nn import functional as F
 
-from . import amp_train, ffn_train, ln_train, ops, rowtail
+from . import amp_train, derived, ffn_train, ln_train, ops, rowtail
 from . import options as _options
 from .ms_deform_attn import MultiScaleDeformableAttention
 from .relation import PositionRelationEmbedding
 from .self_attn import RelationSelfAttention
+
+# the decoder layers' cross-attention value projections as one [layers*C, C] GEMM operand: sources are every layer's weight AND bias
+_VALUE_PROJ = derived.DerivedCache(kind="value_projection_batched")
+
+
+def _fill_value_proj(both, *sources):
+    n = len(sources) // 2
+    torch.cat([t.detach() for t in sources[:n]], 0, out=both[0])
+    torch.cat([t.detach() for t in sources[n:]], 0, out=both[1])
 
 
 def inverse_sigmoid(x: Tensor, eps: float = 1e-3) -> Tensor:
@@ -336,17 +345,18 @@ class RelationTransformerDecoder(nn.Module):
         the chain.  The weights stay owned by the
         layers' nn.Linear modules (state_dict keys unchanged); the concatenation is cached until one of them changes."""
         projs = [layer.cross_attn.value_proj for layer in self.layers]
-        key = tuple((p.weight._version, p.bias._version, p.weight.data_ptr(), p.weight.dtype) for p in projs)
-        cache = getattr(self, "_value_proj_cache", None)
-        if cache is None or cache[0] != key:
+        n = len(projs)
+
+        def build():
             with torch.no_grad():
-                cache = (key, torch.cat([p.weight for p in projs], 0).contiguous(), torch.cat([p.bias for p in projs], 0).contiguous())
+                both = (torch.cat([p.weight for p in projs], 0).contiguous(), torch.cat([p.bias for p in projs], 0).contiguous())
             if value.is_cuda and not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(value.device).synchronize()         # other streams (image groups) use it without an event
-            object.__setattr__(self, "_value_proj_cache", cache)
+            return both
+        weight, bias = _VALUE_PROJ.get([p.weight for p in projs] + [p.bias for p in projs], build, _fill_value_proj)
         B, S, C = value.shape
         v2 = value if value.is_contiguous() else value.contiguous()
-        return F.linear(v2.view(B * S, C), cache[1], cache[2]).view(B, S, len(projs) * C)
+        return F.linear(v2.view(B * S, C), weight, bias).view(B, S, n * C)
 
     def forward(self, query, reference_points, value, spatial_shapes, level_start_index, valid_ratios,
                 key_padding_mask=None, attn_mask=None, skip_relation=False):
@@ -508,6 +518,7 @@ class RelationTransformer(nn.Module):
     # tables, each pixel's centre / level size / level index and the proposal sizes.  Nothing in `forward` then reads a
     # device tensor back or uploads a host one, so the whole eval forward can be captured in a HIP graph (graph.py).
     _geometry_cache: dict = {}
+    derived.on_drop(_geometry_cache.clear)
 
     @classmethod
     def level_geometry(cls, level_hw: Sequence[tuple], device) -> dict:
@@ -527,10 +538,13 @@ class RelationTransformer(nn.Module):
             geo = dict(shapes=shapes, start=start, centre=torch.cat(centre), size=torch.cat(size), index=torch.cat(index),
                        proposal_wh=torch.cat(prop))
             if len(cls._geometry_cache) > 16:
-                cls._geometry_cache.clear()
+                cls._geometry_cache.clear()                           # bounded for eager use; a graph that read an entry pinned it
             if torch.device(device).type == "cuda" and not torch.cuda.is_current_stream_capturing():
                 torch.cuda.current_stream(device).synchronize()       # built once; other streams (image groups) read it
             cls._geometry_cache[key] = geo
+        # a captured graph has these addresses baked in (index tables: garbage there is an out-of-range gather), so a recording
+        # ledger keeps them alive past the clear() above.  No source tensor: nothing to refresh.
+        derived.pin("level_geometry", geo.values())
         return geo
 
     @classmethod
