@@ -978,6 +978,35 @@ typedef struct rdetr_image_desc {
 int rdetr_image_batch(const rdetr_image_desc *images, int B, int src_is_u8, int Hp, int Wp, const float *mean, const float *std,
                       int normalize, int out_bf16, int channels_last, void *out, void *mask, void *stream);
 
+/* The training augmentation's geometry (transforms/presets.py: RandomHorizontalFlip -> RandomShortestSize [-> RandomSizeCrop ->
+ * RandomShortestSize]) with the same taps, rounding and tail, one launch:  per image  window(resize(flip(src), (rh, rw))).
+ *
+ * flip = 1: column x of the image that is resized is source column w - 1 - x; the taps are summed in the flipped image's column
+ * order, so the fp32 sum is the one torch forms on image.flip(-1).  (rh, rw): the size of the virtual resized image, == (h, w) for
+ * none.  (top, left, oh, ow): the window of it that is produced, 0 <= top, top + oh <= rh, 0 <= left, left + ow <= rw; only tiles
+ * of the window are computed and only the source rows its rows touch are filtered.
+ *
+ * out_mode RDETR_IMAGE_OUT_BATCH: the tail of rdetr_image_batch -- window pixel (y, x) of image b at out[b, :, y, x], everything
+ *   at or behind (oh, ow) +0 with mask 1; Hp, Wp, mean, std, normalize, out_bf16, channels_last, out and mask as there.
+ * out_mode RDETR_IMAGE_OUT_U8: uint8 sources only; q = rint(v) is stored as uint8, planar, at dst[c * dst_channel_stride + y *
+ *   dst_row_stride + x]: the intermediate of the crop branch.  No padding and no mask: Hp, Wp, mean, std, normalize, out_bf16,
+ *   channels_last, out and mask are not read.  dst is 16-byte aligned, both strides multiples of 16, dst_row_stride >= ow rounded up
+ *   to 16: whole 16-byte pieces are stored, so columns ow .. roundup(ow, 16) - 1 of every row are written too (as 0).
+ *
+ * Status codes as rdetr_image_batch, and: RDETR_ERR_INVALID_ARG for a window outside the virtual image, a flip or out_mode outside
+ * {0, 1}; RDETR_ERR_UNSUPPORTED for h > RDETR_IMAGE_MAX_DOWNSCALE * rh (or w, rw), fp32 sources in U8 mode, a dst off the rules above. */
+#define RDETR_IMAGE_OUT_BATCH 0
+#define RDETR_IMAGE_OUT_U8 1
+typedef struct rdetr_image_window_desc {
+    const void *src;
+    long long row_stride, channel_stride;
+    int h, w, flip, rh, rw, top, left, oh, ow;
+    void *dst;
+    long long dst_row_stride, dst_channel_stride;
+} rdetr_image_window_desc;
+int rdetr_augment_image_batch(const rdetr_image_window_desc *images, int B, int src_is_u8, int out_mode, int Hp, int Wp, const float *mean,
+                              const float *std, int normalize, int out_bf16, int channels_last, void *out, void *mask, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * The ResNet backbone's epilogues (csrc/backbone.hip; models/bricks/misc.py: FrozenBatchNorm2d, models/backbones/resnet.py): what
  * follows each library convolution, in one read and one write.

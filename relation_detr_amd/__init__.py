@@ -21,7 +21,8 @@ from .detector import RelationDETR, RelationDETRHead, RelationDETRWithBackbone, 
 from .neck import (ChannelMapper, GroupNormLevelsFunction, PositionEmbeddingSine, PyramidBuilder, group_norm_levels, pyramid_masks,
                    pyramid_sine_pos)
 from .optim import FusedAdamW, relation_param_groups, train_step
-from .frontend import ImageBatch, ImagePreprocessor, batch_images, resized_size
+from .frontend import (DetrAugment, DetrChoice, ImageBatch, ImagePreprocessor, batch_images, detr_plan, resized_size, sample_detr_choices,
+                       shortest_size, transform_targets)
 from .backbones import FrozenBatchNorm2d, ResNet, ResNetBackbone
 
 __all__ = [
@@ -40,5 +41,6 @@ __all__ = [
     "ChannelMapper", "PositionEmbeddingSine", "PyramidBuilder", "RelationDETR", "GroupNormLevelsFunction", "group_norm_levels",
     "pyramid_masks", "pyramid_sine_pos",
     "ImageBatch", "ImagePreprocessor", "batch_images", "resized_size", "RelationDETRWithBackbone",
+    "DetrAugment", "DetrChoice", "detr_plan", "sample_detr_choices", "shortest_size", "transform_targets",
     "FrozenBatchNorm2d", "ResNet", "ResNetBackbone", "relation_detr_r50",
 ]

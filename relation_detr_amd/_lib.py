@@ -128,6 +128,7 @@ SIGNATURES = {
     "rdetr_pyramid_sine_pos_f32": [_vp, _vp] + [_c_int] * 3 + [_vp, _c_int] + [_c_float] * 3 + [_vp, _vp],
     "rdetr_pyramid_sine_pos_bf16": [_vp, _vp] + [_c_int] * 3 + [_vp, _c_int] + [_c_float] * 3 + [_vp, _vp],
     "rdetr_image_batch": [_vp] + [_c_int] * 4 + [_vp, _vp] + [_c_int] * 3 + [_vp, _vp, _vp],
+    "rdetr_augment_image_batch": [_vp] + [_c_int] * 5 + [_vp, _vp] + [_c_int] * 3 + [_vp, _vp, _vp],
     "rdetr_frozen_bn_act_f32": [_vp] * 4 + [_c_int] * 6 + [_vp, _vp],
     "rdetr_frozen_bn_act_bf16": [_vp] * 4 + [_c_int] * 6 + [_vp, _vp],
     "rdetr_frozen_bn_act_backward_f32": [_vp] * 3 + [_c_int] * 6 + [_vp, _vp, _vp],

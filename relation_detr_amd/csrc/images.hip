@@ -254,6 +254,211 @@ int launch_image_batch(const ImageTable &tab, int B, int Hp, int Wp, const float
     return launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The augmentation's geometry: window(resize(flip(src), (rh, rw))) per image, the tile kinds, taps and tail of the kernel above.
+//   flip      the taps are those of the flipped image; tap i of column x is read at source column w - 1 - (lo + i), so a wave still
+//             reads one contiguous run, its lanes in descending address order, and the fp32 sum runs in the flipped image's order.
+//             The copy tile loads the lane's run as the same vectors and reverses it in registers.
+//   window    tile (x0, y0) of the window is tile (left + x0, top + y0) of the virtual image: the tap tables are built for those
+//             columns and rows, so only the source rows that the window's rows touch are filtered.
+//   kToU8     the rounded values of the tile go through LDS as bytes and leave as 16-byte stores, 192 of the 256 lanes one each.
+struct WindowTable {
+    rdetr_image_window_desc img[RDETR_IMAGE_MAX_IMAGES];
+};
+
+template <typename S, typename O, bool kToU8>
+__global__ __launch_bounds__(16 * kTileW / (16 / (int)sizeof(O))) void image_window_kernel(WindowTable tab, int Hp, int Wp, float m0, float m1,
+                                                                                           float m2, float d0, float d1, float d2, int normalize,
+                                                                                           int channels_last, int rows_cap, O *__restrict__ out,
+                                                                                           unsigned char *__restrict__ mask)
+{
+    constexpr int PX = 16 / (int)sizeof(O);
+    constexpr int LX = kTileW / PX;
+    constexpr int THREADS = LX * kTileH;
+    constexpr bool kU8 = sizeof(S) == 1;
+    static_assert(!kToU8 || (kU8 && PX == 4), "the uint8 destination: uint8 sources, four pixels per lane");
+    extern __shared__ __attribute__((aligned(16))) float s_rows[];
+    __shared__ float s_norm[kU8 && !kToU8 ? 3 * 256 : 1];
+    __shared__ __attribute__((aligned(16))) unsigned int s_q[kToU8 ? 3 * kTileH * kTileW / 4 : 4];
+    __shared__ float s_xw[kMaxTaps * kTileW], s_yw[kMaxTaps * kTileH];
+    __shared__ int s_xlo[kTileW], s_xn[kTileW], s_ylo[kTileH], s_yn[kTileH];
+
+    const int tid = threadIdx.x, b = blockIdx.z;
+    const int x0 = blockIdx.x * kTileW, y0 = blockIdx.y * kTileH;
+    const rdetr_image_window_desc im = tab.img[b];
+    const S *src = static_cast<const S *>(im.src);
+    const int lx = tid % LX, ly = tid / LX;
+    const int x = x0 + lx * PX, y = y0 + ly;            // the lane's first pixel, in the window
+    const float mean[3] = {m0, m1, m2}, stdv[3] = {d0, d1, d2};
+
+    float v[3][PX];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int p = 0; p < PX; ++p) v[c][p] = 0.0f;
+    const bool tile_padding = y0 >= im.oh || x0 >= im.ow;        // uniform over the workgroup
+    if (kToU8 && tile_padding) return;                          // the uint8 destination has no padding
+    const bool lane_inside = y < im.oh && x < im.ow;
+    const int valid = lane_inside ? min(PX, im.ow - x) : 0;
+
+    if (!tile_padding) {
+        if (kU8 && !kToU8) {
+            for (int i = tid; i < 3 * 256; i += THREADS) {
+                const int c = i >> 8;
+                const float mc = c == 0 ? m0 : (c == 1 ? m1 : m2), dc = c == 0 ? d0 : (c == 1 ? d1 : d2);
+                s_norm[i] = ((float)(i & 255) / 255.0f - mc) / dc;
+            }
+        }
+        if (im.rh == im.h && im.rw == im.w) {
+            if (lane_inside) {
+                const long long row = (long long)(im.top + y) * im.row_stride;
+                const int vx = im.left + x;                     // the lane's first column of the (flipped) image
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const S *p = src + c * im.channel_stride + row;
+                    if (!im.flip) {
+                        load_pixels<PX>(p + vx, valid, v[c]);
+                    } else if (valid == PX) {                   // columns w - 1 - vx down to w - PX - vx: one run, reversed
+                        float t[PX];
+                        load_pixels<PX>(p + (im.w - PX - vx), PX, t);
+#pragma unroll
+                        for (int k = 0; k < PX; ++k) v[c][k] = t[PX - 1 - k];
+                    } else {
+#pragma unroll
+                        for (int k = 0; k < PX; ++k) v[c][k] = k < valid ? as_f32(p[im.w - 1 - vx - k]) : 0.0f;
+                    }
+                }
+            }
+            if (kU8) __syncthreads();
+        } else {
+            const int nx = min(kTileW, im.ow - x0), ny = min(kTileH, im.oh - y0);
+            if (tid < nx)
+                filter_taps(im.left + x0 + tid, im.w, im.rw, &s_xlo[tid], &s_xn[tid], &s_xw[tid], kTileW);
+            else if (tid >= kTileW && tid < kTileW + ny)
+                filter_taps(im.top + y0 + tid - kTileW, im.h, im.rh, &s_ylo[tid - kTileW], &s_yn[tid - kTileW], &s_yw[tid - kTileW], kTileH);
+            __syncthreads();
+            const int r0 = s_ylo[0];
+            const int rows = min(s_ylo[ny - 1] + s_yn[ny - 1] - r0, rows_cap);
+            {
+                const int col = tid & (kTileW - 1);
+                if (col < nx) {
+                    const int n = s_xn[col];
+                    const int step = im.flip ? -1 : 1;
+                    const int first_col = im.flip ? im.w - 1 - s_xlo[col] : s_xlo[col];
+                    float w[kRegTaps];
+#pragma unroll
+                    for (int i = 0; i < kRegTaps; ++i) w[i] = i < n ? s_xw[i * kTileW + col] : 0.0f;
+                    for (int c = 0; c < 3; ++c) {
+                        const S *p = src + c * im.channel_stride + (long long)r0 * im.row_stride + first_col;
+                        for (int r = tid / kTileW; r < rows; r += THREADS / kTileW) {
+                            const S *q = p + (long long)r * im.row_stride;
+                            float acc = 0.0f;
+#pragma unroll
+                            for (int i = 0; i < kRegTaps; ++i) acc = fmaf(w[i], as_f32(q[step * max(min(i, n - 1), 0)]), acc);
+                            for (int i = kRegTaps; i < n; ++i) acc = fmaf(s_xw[i * kTileW + col], as_f32(q[step * i]), acc);
+                            s_rows[(c * rows + r) * kTileW + col] = acc;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (lane_inside) {
+                const int first = s_ylo[ly] - r0, n = s_yn[ly];
+                for (int j = 0; j < n && first + j < rows; ++j) {
+                    const float wy = s_yw[j * kTileH + ly];
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const float *t = &s_rows[(c * rows + first + j) * kTileW + lx * PX];
+#pragma unroll
+                        for (int p = 0; p < PX; p += 4) {
+                            const f32x4 u = *reinterpret_cast<const f32x4 *>(t + p);
+                            v[c][p] = fmaf(wy, u.x, v[c][p]);
+                            v[c][p + 1] = fmaf(wy, u.y, v[c][p + 1]);
+                            v[c][p + 2] = fmaf(wy, u.z, v[c][p + 2]);
+                            v[c][p + 3] = fmaf(wy, u.w, v[c][p + 3]);
+                        }
+                    }
+                }
+                if (kU8) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c)
+#pragma unroll
+                        for (int p = 0; p < PX; ++p) v[c][p] = fminf(fmaxf(rintf(v[c][p]), 0.0f), 255.0f);
+                }
+            }
+        }
+        if (kToU8) {
+            // bytes of the tile through LDS; columns at or behind ow hold 0.  A piece starts inside the row stride (the host checked
+            // dst_row_stride >= ow rounded up to 16), so the stores stay inside the destination's rows.
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                unsigned int word = 0u;
+#pragma unroll
+                for (int p = 0; p < PX; ++p) word |= (p < valid ? (unsigned int)v[c][p] : 0u) << (8 * p);
+                s_q[(c * kTileH + ly) * (kTileW / 4) + lx] = word;
+            }
+            __syncthreads();
+            if (tid < 3 * kTileH * (kTileW / 16)) {
+                const int c = tid / (kTileH * (kTileW / 16)), row = tid / (kTileW / 16) % kTileH, piece = tid % (kTileW / 16);
+                const int yy = y0 + row, xx = x0 + piece * 16;
+                if (yy < im.oh && xx < im.ow) {
+                    unsigned char *d = static_cast<unsigned char *>(im.dst) + c * im.dst_channel_stride + (long long)yy * im.dst_row_stride + xx;
+                    *reinterpret_cast<u32x4 *>(d) = *reinterpret_cast<const u32x4 *>(&s_q[(c * kTileH + row) * (kTileW / 4) + piece * 4]);
+                }
+            }
+            return;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int p = 0; p < PX; ++p) {
+                float r = v[c][p];
+                if (kU8)
+                    r = s_norm[c * 256 + (p < valid ? (int)r : 0)];
+                else if (normalize)
+                    r = (r - mean[c]) / stdv[c];
+                v[c][p] = p < valid ? r : 0.0f;
+            }
+    }
+
+    if (y >= Hp || x >= Wp) return;
+    if (channels_last) {
+        float e[3 * PX];
+#pragma unroll
+        for (int p = 0; p < PX; ++p)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[p * 3 + c] = v[c][p];
+        O *o = out + (((long long)b * Hp + y) * Wp + x) * 3;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) store16(o + k * PX, e + k * PX);
+    } else {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) store16(out + (((long long)b * 3 + c) * Hp + y) * Wp + x, v[c]);
+    }
+    unsigned int m[PX / 4];
+#pragma unroll
+    for (int k = 0; k < PX / 4; ++k)
+        m[k] = (4 * k < valid ? 0u : 1u) | (4 * k + 1 < valid ? 0u : 1u << 8) | (4 * k + 2 < valid ? 0u : 1u << 16) | (4 * k + 3 < valid ? 0u : 1u << 24);
+    unsigned int *mo = reinterpret_cast<unsigned int *>(mask + ((long long)b * Hp + y) * Wp + x);
+#pragma unroll
+    for (int k = 0; k < PX / 4; ++k) mo[k] = m[k];
+}
+
+template <typename S, typename O, bool kToU8>
+int launch_image_window(const WindowTable &tab, int B, int Hp, int Wp, const float *mean, const float *stdv, int normalize, int channels_last,
+                        int rows_cap, void *out, void *mask, hipStream_t stream)
+{
+    constexpr int threads = 16 * kTileW / (16 / (int)sizeof(O));
+    const dim3 grid((unsigned)((Wp + kTileW - 1) / kTileW), (unsigned)((Hp + kTileH - 1) / kTileH), (unsigned)B);
+    const size_t lds = (size_t)3 * rows_cap * kTileW * sizeof(float);
+    if (ensure_dynamic_lds<image_window_kernel<S, O, kToU8>>(3 * patch_rows_cap(RDETR_IMAGE_MAX_DOWNSCALE, 1) * kTileW * (int)sizeof(float)) !=
+        RDETR_OK)
+        return RDETR_ERR_LAUNCH;
+    hipLaunchKernelGGL((image_window_kernel<S, O, kToU8>), grid, dim3(threads), lds, stream, tab, Hp, Wp, mean[0], mean[1], mean[2], stdv[0],
+                       stdv[1], stdv[2], normalize, channels_last, rows_cap, static_cast<O *>(out), static_cast<unsigned char *>(mask));
+    return launch_status();
+}
+
 }  // namespace
 }  // namespace rdetr
 
@@ -293,4 +498,65 @@ extern "C" int rdetr_image_batch(const rdetr_image_desc *images, int B, int src_
                         : launch_image_batch<unsigned char, float>(tab, B, Hp, Wp, m, d, normalize, channels_last, rows_cap, out, mask, s);
     return out_bf16 ? launch_image_batch<float, unsigned short>(tab, B, Hp, Wp, m, d, normalize, channels_last, rows_cap, out, mask, s)
                     : launch_image_batch<float, float>(tab, B, Hp, Wp, m, d, normalize, channels_last, rows_cap, out, mask, s);
+}
+
+extern "C" int rdetr_augment_image_batch(const rdetr_image_window_desc *images, int B, int src_is_u8, int out_mode, int Hp, int Wp,
+                                         const float *mean, const float *std, int normalize, int out_bf16, int channels_last, void *out,
+                                         void *mask, void *stream)
+{
+    using namespace rdetr;
+    if (out_mode != RDETR_IMAGE_OUT_BATCH && out_mode != RDETR_IMAGE_OUT_U8) return RDETR_ERR_INVALID_ARG;
+    const bool to_u8 = out_mode == RDETR_IMAGE_OUT_U8;
+    if (B < 0 || (src_is_u8 & ~1)) return RDETR_ERR_INVALID_ARG;
+    if (!to_u8) {
+        if (Hp <= 0 || Wp <= 0 || !out || !mask) return RDETR_ERR_INVALID_ARG;
+        if ((normalize | out_bf16 | channels_last) & ~1) return RDETR_ERR_INVALID_ARG;
+        if (normalize && (!mean || !std || std[0] == 0.0f || std[1] == 0.0f || std[2] == 0.0f)) return RDETR_ERR_INVALID_ARG;
+    }
+    if (B > 0 && !images) return RDETR_ERR_INVALID_ARG;
+    int grid_h = 1, grid_w = 1;                         // U8 mode: the largest window
+    for (int i = 0; i < B; ++i) {
+        const rdetr_image_window_desc &im = images[i];
+        if (!im.src || im.h <= 0 || im.w <= 0 || im.rh <= 0 || im.rw <= 0 || im.oh <= 0 || im.ow <= 0 || im.row_stride < 0 ||
+            im.channel_stride < 0 || (im.flip & ~1))
+            return RDETR_ERR_INVALID_ARG;
+        if (im.top < 0 || im.left < 0 || (long long)im.top + im.oh > im.rh || (long long)im.left + im.ow > im.rw) return RDETR_ERR_INVALID_ARG;
+        if (to_u8) {
+            if (!im.dst || im.dst_row_stride < 0 || im.dst_channel_stride < 0) return RDETR_ERR_INVALID_ARG;
+            grid_h = grid_h > im.oh ? grid_h : im.oh;
+            grid_w = grid_w > im.ow ? grid_w : im.ow;
+        } else if (im.oh > Hp || im.ow > Wp) {
+            return RDETR_ERR_INVALID_ARG;
+        }
+    }
+    if (B > RDETR_IMAGE_MAX_IMAGES) return RDETR_ERR_UNSUPPORTED;
+    if (to_u8) {
+        if (!src_is_u8 || grid_h > (1 << 20) || grid_w > (1 << 20)) return RDETR_ERR_UNSUPPORTED;
+    } else {
+        if (Wp % 8 != 0 || Hp > (1 << 20) || Wp > (1 << 20) || !aligned_to(out, 16) || !aligned_to(mask, 8)) return RDETR_ERR_UNSUPPORTED;
+        if (src_is_u8 && !normalize) return RDETR_ERR_UNSUPPORTED;
+    }
+    WindowTable tab = {};
+    int rows_cap = 1;
+    for (int i = 0; i < B; ++i) {
+        const rdetr_image_window_desc &im = images[i];
+        if (!src_is_u8 && !aligned_to(im.src, 4)) return RDETR_ERR_UNSUPPORTED;
+        if ((long long)im.h > (long long)RDETR_IMAGE_MAX_DOWNSCALE * im.rh || (long long)im.w > (long long)RDETR_IMAGE_MAX_DOWNSCALE * im.rw)
+            return RDETR_ERR_UNSUPPORTED;
+        if (to_u8 && (!aligned_to(im.dst, 16) || im.dst_row_stride % 16 != 0 || im.dst_channel_stride % 16 != 0 ||
+                      im.dst_row_stride < ((long long)im.ow + 15) / 16 * 16))
+            return RDETR_ERR_UNSUPPORTED;
+        if (im.h != im.rh || im.w != im.rw) rows_cap = rows_cap > patch_rows_cap(im.h, im.rh) ? rows_cap : patch_rows_cap(im.h, im.rh);
+        tab.img[i] = im;
+    }
+    if (B == 0) return RDETR_OK;
+    static const float zero[3] = {0.0f, 0.0f, 0.0f}, one[3] = {1.0f, 1.0f, 1.0f};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (to_u8) return launch_image_window<unsigned char, float, true>(tab, B, grid_h, grid_w, zero, one, 0, 0, rows_cap, nullptr, nullptr, s);
+    const float *m = normalize ? mean : zero, *d = normalize ? std : one;
+    if (src_is_u8)
+        return out_bf16 ? launch_image_window<unsigned char, unsigned short, false>(tab, B, Hp, Wp, m, d, normalize, channels_last, rows_cap, out, mask, s)
+                        : launch_image_window<unsigned char, float, false>(tab, B, Hp, Wp, m, d, normalize, channels_last, rows_cap, out, mask, s);
+    return out_bf16 ? launch_image_window<float, unsigned short, false>(tab, B, Hp, Wp, m, d, normalize, channels_last, rows_cap, out, mask, s)
+                    : launch_image_window<float, float, false>(tab, B, Hp, Wp, m, d, normalize, channels_last, rows_cap, out, mask, s);
 }

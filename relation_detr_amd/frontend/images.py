@@ -3,7 +3,7 @@
 ``construct_mask`` -> ``prepare_targets``).
 
 ``batch_images`` is the fused call: csrc/images.hip resizes, rounds, normalises, pads and writes the mask in one launch per
-``MAX_IMAGES`` images.  ``ImagePreprocessor`` is the module with the two routes the neck's modules have: ``forward_torch`` restates the
+``MAX_IMAGES`` images; with ``plans`` it also flips, crops and resizes twice, the training augmentation's geometry (frontend/augment.py).  ``ImagePreprocessor`` is the module with the two routes the neck's modules have: ``forward_torch`` restates the
 reference's operator sequence on any device, ``forward_fused`` is the kernel.
 
 Two things that are easy to restate wrongly:
@@ -48,6 +48,34 @@ class _ImageDesc(ctypes.Structure):                    # rdetr_image_desc
                 ("h", ctypes.c_int), ("w", ctypes.c_int), ("oh", ctypes.c_int), ("ow", ctypes.c_int)]
 
 
+class _WindowDesc(ctypes.Structure):                   # rdetr_image_window_desc
+    _fields_ = [("src", ctypes.c_void_p), ("row_stride", ctypes.c_longlong), ("channel_stride", ctypes.c_longlong),
+                ("h", ctypes.c_int), ("w", ctypes.c_int), ("flip", ctypes.c_int), ("rh", ctypes.c_int), ("rw", ctypes.c_int),
+                ("top", ctypes.c_int), ("left", ctypes.c_int), ("oh", ctypes.c_int), ("ow", ctypes.c_int),
+                ("dst", ctypes.c_void_p), ("dst_row_stride", ctypes.c_longlong), ("dst_channel_stride", ctypes.c_longlong)]
+
+    @staticmethod
+    def stages(h: int, w: int, size: Tuple[int, int], plan):
+        """One image's plan ``(flip, first, crop)`` -> ``(scratch, batch)``, the launches that run it.  Each is a tuple ``(vt, vl, sh, sw,
+        flip, rh, rw, top, left, oh, ow)``: the launch reads the ``sh x sw`` view at ``(vt, vl)`` of its source (in the flipped image's
+        coordinates), flips it, resizes it to ``(rh, rw)`` and produces the ``oh x ow`` window at ``(top, left)``.  ``scratch`` is None,
+        or the U8 launch whose window becomes the source of ``batch``.  A crop with no first resize is a view of the source; a crop
+        whose second resize is the identity is a window of one launch."""
+        oh, ow = int(size[0]), int(size[1])
+        if plan is None:
+            return None, (0, 0, h, w, 0, oh, ow, 0, 0, oh, ow)
+        flip, first, crop = plan
+        flip = int(bool(flip))
+        if first is None:
+            top, left, ch, cw = (0, 0, h, w) if crop is None else (int(v) for v in crop)
+            return None, (top, left, ch, cw, flip, oh, ow, 0, 0, oh, ow)
+        rh1, rw1 = int(first[0]), int(first[1])
+        top, left, ch, cw = (0, 0, rh1, rw1) if crop is None else (int(v) for v in crop)
+        if (ch, cw) == (oh, ow):
+            return None, (0, 0, h, w, flip, rh1, rw1, top, left, oh, ow)
+        return (0, 0, h, w, flip, rh1, rw1, top, left, ch, cw), (0, 0, ch, cw, 0, oh, ow, 0, 0, oh, ow)
+
+
 def resized_size(h: int, w: int, min_size: int, max_size: Optional[int] = None) -> Tuple[int, int]:
     """``EvalResize.forward``'s output size.  The reference computes it on 0-dim tensors, so in float32, and ``number / tensor`` is
     torch's ``tensor.reciprocal() * number``: ``r = (1 / min(h, w)) * min_size``, each step rounded to float32, likewise
@@ -70,8 +98,10 @@ def batched_size(sizes: Sequence[Tuple[int, int]], size_divisible: int) -> Tuple
     return (int(math.ceil(float(hp) / size_divisible) * size_divisible), int(math.ceil(float(wp) / size_divisible) * size_divisible))
 
 
-def _kernel_takes(images: Sequence[Tensor], sizes: Sequence[Tuple[int, int]], size_divisible: int, normalize: bool) -> Optional[str]:
-    """None when csrc/images.hip takes the batch, else the reason it does not."""
+def _kernel_takes(images: Sequence[Tensor], sizes: Sequence[Tuple[int, int]], size_divisible: int, normalize: bool,
+                  plans: Optional[Sequence] = None) -> Optional[str]:
+    """None when csrc/images.hip takes the batch, else the reason it does not.  With ``plans`` both launches' downscales and the
+    windows are checked."""
     if len(images) == 0:
         return "an empty list"
     first = images[0]
@@ -90,11 +120,26 @@ def _kernel_takes(images: Sequence[Tensor], sizes: Sequence[Tuple[int, int]], si
         return f"dtype {first.dtype}"
     if first.dtype == torch.uint8 and not normalize:
         return "uint8 images without normalisation"
-    for im, (oh, ow) in zip(images, sizes):
+    if plans is not None and len(plans) != len(images):
+        return "a list of plans that is not one per image"
+    for k, (im, (oh, ow)) in enumerate(zip(images, sizes)):
         if oh <= 0 or ow <= 0:
             return "an empty resized image"
-        if im.shape[1] > MAX_DOWNSCALE * oh or im.shape[2] > MAX_DOWNSCALE * ow:
-            return f"a downscale beyond {MAX_DOWNSCALE}"
+        H, W = int(im.shape[1]), int(im.shape[2])
+        scratch, batch = _WindowDesc.stages(H, W, (oh, ow), None if plans is None else plans[k])
+        if scratch is not None and first.dtype != torch.uint8:
+            return "a resize, crop, resize plan on float images"
+        for stage in (scratch, batch):
+            if stage is None:
+                continue
+            vt, vl, sh, sw, _, rh, rw, top, left, wh, ww = stage
+            if sh <= 0 or sw <= 0 or vt < 0 or vl < 0 or vt + sh > H or vl + sw > W:
+                return "a crop outside the image"
+            if rh <= 0 or rw <= 0 or wh <= 0 or ww <= 0 or top < 0 or left < 0 or top + wh > rh or left + ww > rw:
+                return "a crop outside the resized image"
+            if sh > MAX_DOWNSCALE * rh or sw > MAX_DOWNSCALE * rw:
+                return f"a downscale beyond {MAX_DOWNSCALE}"
+            H, W = wh, ww                                       # the scratch is the next launch's source
     if batched_size(sizes, size_divisible)[1] % 8:
         return "a batch width that is no multiple of 8"
     return None
@@ -102,12 +147,18 @@ def _kernel_takes(images: Sequence[Tensor], sizes: Sequence[Tuple[int, int]], si
 
 def batch_images(images: Sequence[Tensor], sizes: Optional[Sequence[Tuple[int, int]]] = None, size_divisible: int = 32,
                  mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD, normalize: bool = True,
-                 dtype: torch.dtype = torch.float32, channels_last: bool = False) -> ImageBatch:
+                 dtype: torch.dtype = torch.float32, channels_last: bool = False, *, plans: Optional[Sequence] = None) -> ImageBatch:
     """The fused front end on device tensors.  ``images``: [3, h_i, w_i] uint8 or float32 (values in [0, 1]), rows contiguous (a
     crop of a larger tensor is fine).  ``sizes``: the (oh_i, ow_i) to resize to, None for no resize.  uint8 images are resized,
     rounded, divided by 255 and normalised; float32 images are resized and normalised, or with ``normalize=False`` only copied.
     The batch is ``dtype`` (float32 or bfloat16), NCHW-contiguous or channels-last.  Raises where the kernel does not take the batch;
-    ``ImagePreprocessor`` is what falls back to the torch route."""
+    ``ImagePreprocessor`` is what falls back to the torch route.
+
+    ``plans``: per image None or ``(flip, first, crop)``, the geometry of the training augmentation: flip horizontally, resize to
+    ``first = (rh1, rw1)`` (uint8 images: rounded to uint8), crop ``(top, left, ch, cw)``, resize to ``sizes[i]``; ``first`` and ``crop``
+    may each be None.  Images that resize twice go through one launch per ``MAX_IMAGES`` of them that writes the crop of the first
+    resize as uint8 into scratch memory allocated here; then one launch per ``MAX_IMAGES`` images writes the batch.  ``plans=None``
+    is the call as it always was."""
     images = list(images.unbind(0)) if isinstance(images, Tensor) else list(images)
     original = [(int(im.shape[-2]), int(im.shape[-1])) for im in images]
     sizes = original if sizes is None else [(int(s[0]), int(s[1])) for s in sizes]
@@ -115,7 +166,7 @@ def batch_images(images: Sequence[Tensor], sizes: Optional[Sequence[Tuple[int, i
         raise ValueError("batch_images: one size per image")
     if dtype not in _OUT_DTYPES:
         raise ValueError(f"batch_images: dtype {dtype}; the batch is float32 or bfloat16")
-    reason = _kernel_takes(images, sizes, size_divisible, normalize)
+    reason = _kernel_takes(images, sizes, size_divisible, normalize, plans)
     if reason is not None:
         raise _lib.RdetrError(f"batch_images: the kernel does not take {reason}; ImagePreprocessor(fused=False) is the torch route")
     lib = _lib.load()
@@ -126,6 +177,39 @@ def batch_images(images: Sequence[Tensor], sizes: Optional[Sequence[Tuple[int, i
     mask = torch.empty((B, Hp, Wp), dtype=torch.bool, device=device)
     c_mean, c_std = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
     stream = torch.cuda.current_stream(device).cuda_stream
+    if plans is not None:
+        u8 = int(images[0].dtype == torch.uint8)
+        descs, twice, scratch_bytes = [], [], 0
+        for im, size, plan in zip(images, sizes, plans):
+            scratch, batch = _WindowDesc.stages(int(im.shape[1]), int(im.shape[2]), size, plan)
+            vt, vl, _, sw, flip = (scratch or batch)[:5]
+            col = int(im.shape[2]) - vl - sw if flip else vl                  # the view's first column in the source as it lies
+            src = im.data_ptr() + (vt * im.stride(1) + col) * im.element_size()
+            if scratch is None:
+                descs.append(_WindowDesc(src, im.stride(1), im.stride(0), *batch[2:], None, 0, 0))
+                continue
+            ch, cw = scratch[9:]
+            ld = (cw + 15) // 16 * 16                                          # rows of whole 16-byte pieces
+            twice.append((_WindowDesc(src, im.stride(1), im.stride(0), *scratch[2:], None, ld, ch * ld), len(descs), scratch_bytes))
+            descs.append(_WindowDesc(None, ld, ch * ld, *batch[2:], None, 0, 0))
+            scratch_bytes += 3 * ch * ld
+        if twice:
+            memory = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
+            for d, k, at in twice:
+                d.dst = descs[k].src = memory.data_ptr() + at
+            for first in range(0, len(twice), MAX_IMAGES):
+                n = min(MAX_IMAGES, len(twice) - first)
+                table = (_WindowDesc * n)(*[d for d, _, _ in twice[first:first + n]])
+                _lib.check(lib.rdetr_augment_image_batch(table, n, 1, 1, 0, 0, None, None, 0, 0, 0, None, None, stream),
+                           "rdetr_augment_image_batch")
+        for first in range(0, B, MAX_IMAGES):
+            n = min(MAX_IMAGES, B - first)
+            table = (_WindowDesc * n)(*descs[first:first + n])
+            _lib.check(lib.rdetr_augment_image_batch(table, n, u8, 0, Hp, Wp, c_mean, c_std, int(normalize), int(dtype == torch.bfloat16),
+                                                     int(channels_last), out[first:first + n].data_ptr(), mask[first:first + n].data_ptr(),
+                                                     stream), "rdetr_augment_image_batch")
+        return ImageBatch(out, mask, torch.tensor(sizes, dtype=torch.int64).reshape(B, 2),
+                          torch.tensor(original, dtype=torch.int64).reshape(B, 2))
     for first in range(0, B, MAX_IMAGES):
         n = min(MAX_IMAGES, B - first)
         table = (_ImageDesc * n)()
@@ -169,7 +253,8 @@ class ImagePreprocessor(nn.Module):
     """``forward(images, targets=None) -> (ImageBatch, targets)``, ``DETRDetector.preprocess``.
 
     Eval mode: every image is resized to ``resized_size(h, w, min, max)`` when ``min_size`` / ``max_size`` are given, converted to
-    float (uint8: / 255) and normalised.  Training mode: the images arrive augmented, float and normalised and are only batched.
+    float (uint8: / 255) and normalised.  Training mode: the images arrive augmented, float and normalised and are only batched
+    (``augment.DetrAugment`` is the preprocessor that takes decoded images and augments them itself).
     Both modes pad to the batch's largest size rounded up to ``size_divisible`` and build the mask.  Targets, when given, are
     checked and their boxes go from xyxy pixels to cxcywh normalised by ``image_sizes``; they stay torch (a few boxes).
 
