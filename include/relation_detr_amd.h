@@ -360,6 +360,30 @@ int rdetr_relation_attention_bf16(const uint16_t *q, const uint16_t *k, const ui
                                   const float *bias, const uint8_t *bool_mask, int B, int H, int D, int N, int M,
                                   float scale, uint16_t *out, int ldo, void *stream);
 
+/* Swin's shifted-window attention between the qkv and the proj GEMM of a block, one launch (csrc/attn_win.hip; forward only):
+ *   out = softmax(Q K^T * scale + relative position bias [+ shift mask]) V    per (image, window, head)
+ * Replaces models/backbones/swin.py:133-221 around that product: pad, roll, window partition, the qkv permute, the
+ * [B*nW, heads, N, N] scores, bias add, mask add, softmax, P V, window reverse, roll back, unpad.
+ *   q, k, v   bf16 [B, H*W, ..] of the UNPADDED map, head h at columns h*D .. h*D+D-1; ldq / ldk / ldv = row stride in elements
+ *             (the three column blocks of the qkv GEMM's [B, H*W, 3C] output can be passed as they are); 16-byte aligned,
+ *             ld % 8 == 0, ld >= heads * D
+ *   k_pad, v_pad   bf16 [heads * D] or NULL: k and v of a padding token (a source position outside H x W once the map is
+ *             padded to a multiple of the window) = the qkv linear's bias row, zeros when NULL.  Padding tokens take part as
+ *             keys; their own outputs are not stored.  16-byte aligned
+ *   table     [(2 wh - 1)(2 ww - 1), heads], fp32 (table_bf16 = 0) or bf16 (1): relative_position_bias_table as it is; the
+ *             kernel computes (ri - rj + wh - 1)(2 ww - 1) + (ci - cj + ww - 1) itself
+ *   sh, sw    the EFFECTIVE shift (0 in a dimension whose window is >= the padded size): the rolled-frame position (y, x) is the
+ *             token of source position ((y + sh) % pH, (x + sw) % pW); with sh + sw > 0, -100 is added between tokens of
+ *             different regions (3 hr + wr; hr = 0 below pH - wh, 1 below pH - sh, else 2)
+ *   out       bf16 [B, H*W, ..] with row stride ldo, written at the token's SOURCE row (un-windowed, un-rolled, unpadded);
+ *             16-byte aligned, ldo % 8 == 0
+ * D = 32 and wh * ww <= 144 only (RDETR_ERR_UNSUPPORTED otherwise); wh * ww == 0 or a shift >= its window is
+ * RDETR_ERR_INVALID_ARG; B == 0 or H * W == 0 is a no-op. */
+int rdetr_window_attention_bf16(const uint16_t *q, const uint16_t *k, const uint16_t *v, int ldq, int ldk, int ldv,
+                                const uint16_t *k_pad, const uint16_t *v_pad, const void *table, int table_bf16, int B,
+                                int heads, int D, int H, int W, int wh, int ww, int sh, int sw, float scale,
+                                uint16_t *out, int ldo, void *stream);
+
 /* Training forward: the same kernel and the same out bits as rdetr_relation_attention_bf16, plus the per-row log-sum-exp
  *   lse   fp32 [B*H, N], LOG2 domain: lse[bh * N + n] = log2(sum_m exp2((s * scale + bias) * log2(e))) (-inf for a fully masked
  *         row); natural log = lse * ln(2).  rdetr_relation_attention_backward_bf16 takes it as written.

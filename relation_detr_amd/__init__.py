@@ -17,13 +17,14 @@ from .amp_train import AddLayerNormMixedFunction, FeedForwardMixedFunction
 from .msda_train_hm import MultiScaleDeformableAttnHeadMajorFunction, grad_value_from_head_major, ms_deform_attn_backward_fused_hm
 from .criterion import RelationCriterion, SetLossFunction, assign_match, hungarian_match, match_cost, set_loss
 from .denoising import CdnQueryFunction, GenerateCDNQueries, cdn_noise, cdn_queries, denoising_mask
-from .detector import RelationDETR, RelationDETRHead, RelationDETRWithBackbone, relation_detr_r50
+from .detector import RelationDETR, RelationDETRHead, RelationDETRWithBackbone, relation_detr_r50, relation_detr_swin_l
 from .neck import (ChannelMapper, GroupNormLevelsFunction, PositionEmbeddingSine, PyramidBuilder, group_norm_levels, pyramid_masks,
                    pyramid_sine_pos)
 from .optim import FusedAdamW, relation_param_groups, train_step
 from .frontend import (DetrAugment, DetrChoice, ImageBatch, ImagePreprocessor, batch_images, detr_plan, resized_size, sample_detr_choices,
                        shortest_size, transform_targets)
-from .backbones import FrozenBatchNorm2d, ResNet, ResNetBackbone
+from .backbones import (FrozenBatchNorm2d, PatchMerging, ResNet, ResNetBackbone, ShiftedWindowAttention, SwinTransformer,
+                        SwinTransformerBackbone, SwinTransformerBlock)
 
 __all__ = [
     "MultiScaleDeformableAttention", "PositionRelationEmbedding", "PositionRelationEncoder", "box_rel_encoding",
@@ -43,4 +44,5 @@ __all__ = [
     "ImageBatch", "ImagePreprocessor", "batch_images", "resized_size", "RelationDETRWithBackbone",
     "DetrAugment", "DetrChoice", "detr_plan", "sample_detr_choices", "shortest_size", "transform_targets",
     "FrozenBatchNorm2d", "ResNet", "ResNetBackbone", "relation_detr_r50",
+    "PatchMerging", "ShiftedWindowAttention", "SwinTransformerBlock", "SwinTransformer", "SwinTransformerBackbone", "relation_detr_swin_l",
 ]

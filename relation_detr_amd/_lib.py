@@ -48,6 +48,7 @@ SIGNATURES = {
     "rdetr_relation_bias_backward_f32": [_vp] * 4 + [_c_int] * 5 + [_c_float] * 3 + [_vp] * 4,
     "rdetr_bias_softmax_f32": [_vp] * 3 + [_c_int] * 3 + [_vp],
     "rdetr_relation_attention_bf16": [_vp] * 3 + [_c_int] * 3 + [_vp, _vp] + [_c_int] * 5 + [_c_float, _vp, _c_int, _vp],
+    "rdetr_window_attention_bf16": [_vp] * 3 + [_c_int] * 3 + [_vp] * 3 + [_c_int] * 10 + [_c_float, _vp, _c_int, _vp],
     "rdetr_relation_attention_train_bf16": [_vp] * 3 + [_c_int] * 3 + [_vp, _vp] + [_c_int] * 5 + [_c_float, _vp, _c_int, _vp, _vp],
     "rdetr_relation_attention_backward_workspace_bytes": [_c_int] * 3,
     "rdetr_relation_attention_backward_bf16": [_vp] * 3 + [_c_int] * 3 + [_vp, _c_int, _vp, _vp, _c_int, _vp, _vp] + [_c_int] * 5

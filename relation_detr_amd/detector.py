@@ -140,3 +140,32 @@ def relation_detr_r50(num_classes: int = 91, weights=None, num_queries: int = 90
         GenerateCDNQueries(num_queries=num_queries, num_classes=num_classes, label_embed_dim=embed_dim, denoising_nums=denoising_nums,
                            fused=fused),
         ImagePreprocessor(min_size, max_size, fused=fused), num_select)
+
+
+def relation_detr_swin_l(num_classes: int = 91, weights=None, num_queries: int = 900, hybrid_num_proposals: int = 1500, hybrid_assign: int = 6,
+                         enc_layers: int = 6, dec_layers: int = 6, d_ffn: int = 2048, denoising_nums: int = 100, min_size: int = 800,
+                         max_size: int = 1333, num_select: int = 300, fused: bool = True, arch: str = "swin_l", backbone_kwargs=None,
+                         **transformer_kwargs) -> RelationDETRWithBackbone:
+    """``configs/relation_detr/relation_detr_swin_l_800_1333.py`` from this package's parts: ``SwinTransformerBackbone("swin_l",
+    return_indices=(1, 2, 3), freeze_indices=(0,))``, and behind it what ``relation_detr_r50`` assembles: the four-level
+    ``ChannelMapper`` to 256 channels, the sine position encoding, the 6 + 6 layer transformer, the hybrid criterion, 100 denoising
+    pairs and the 800 / 1333 front end.  ``weights``: the backbone's state dict or a local path (``SwinTransformerBackbone``'s
+    argument).  ``arch`` and ``backbone_kwargs`` (entries of the architecture: ``embed_dim``, ``depths``, ``num_heads``, ...) and the
+    size arguments are there for reduced models; ``transformer_kwargs`` go to ``build_relation_transformer``."""
+    from .backbones import SwinTransformerBackbone
+    from .frontend import ImagePreprocessor
+    from .neck import ChannelMapper, PositionEmbeddingSine
+    from .transformer import build_relation_transformer
+    embed_dim, levels = 256, 4
+    backbone = SwinTransformerBackbone(arch, weights=weights, return_indices=(1, 2, 3), freeze_indices=(0,), fused=fused,
+                                       **(backbone_kwargs or {}))
+    transformer = build_relation_transformer(num_classes=num_classes, embed_dim=embed_dim, d_ffn=d_ffn, num_levels=levels,
+                                             enc_layers=enc_layers, dec_layers=dec_layers, num_queries=num_queries,
+                                             hybrid_num_proposals=hybrid_num_proposals, **transformer_kwargs)
+    return RelationDETRWithBackbone(
+        backbone, ChannelMapper(backbone.num_channels, embed_dim, levels, fused=fused),
+        PositionEmbeddingSine(embed_dim // 2, 10000, True, offset=-0.5, fused=fused), transformer,
+        RelationCriterion(num_classes, hybrid_assign=hybrid_assign, fused=fused),
+        GenerateCDNQueries(num_queries=num_queries, num_classes=num_classes, label_embed_dim=embed_dim, denoising_nums=denoising_nums,
+                           fused=fused),
+        ImagePreprocessor(min_size, max_size, fused=fused), num_select)

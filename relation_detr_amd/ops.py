@@ -679,11 +679,14 @@ def _attention_rows(t: torch.Tensor, n: int):
     return t, t.stride(1)
 
 
-def _attention_operands(name: str, q, k, v, num_heads: int, bias=None, mask=None, boxes=None, proj=None, num_pos_feats: int = 0):
+def _attention_operands(name: str, q, k, v, num_heads: int, bias=None, mask=None, boxes=None, proj=None, num_pos_feats: int = 0, *,
+                        window=None):
     """The operand preparation every operator of the attention family starts with (the caller has checked the device): dtype and
     shape checks of q [B,N,C], k / v [B,M,C] bf16, of the fp32 bias [B*H,N,M], the bool mask [N,M], ``boxes`` = (src [B,N,4],
     tgt [B,M,4]) and ``proj`` = (weight [H, 4F], bias [H] | None); q, k, v as the kernels take them
-    -> ((B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), the mask as uint8 | None)."""
+    -> ((B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), the mask as uint8 | None).
+    ``window`` = (H, W, wh, ww, sh, sw) (the windowed mode of ``relation_attention``): N == M == H * W, ``bias`` is the relative
+    position bias table [(2wh-1)(2ww-1), heads], fp32 or bf16, and there is no mask."""
     if q.dtype != torch.bfloat16 or k.dtype != torch.bfloat16 or v.dtype != torch.bfloat16:
         raise _lib.RdetrError(f"{name}: q, k, v must be bfloat16")
     if q.dim() != 3 or k.dim() != 3 or v.dim() != 3:
@@ -692,6 +695,20 @@ def _attention_operands(name: str, q, k, v, num_heads: int, bias=None, mask=None
     M = k.shape[1]
     if C % num_heads or k.shape != (B, M, C) or v.shape != (B, M, C):
         raise _lib.RdetrError(f"{name}: q [B,N,C], k / v [B,M,C] expected")
+    if window is not None:
+        if len(window) != 6 or any(int(x) != x for x in window):
+            raise _lib.RdetrError(f"{name}: window = (H, W, wh, ww, sh, sw), six integers")
+        H, W, wh, ww, sh, sw = (int(x) for x in window)
+        if min(H, W, sh, sw) < 0 or wh <= 0 or ww <= 0 or sh >= wh or sw >= ww:
+            raise _lib.RdetrError(f"{name}: window needs H, W >= 0, wh, ww > 0 and 0 <= shift < window, got {tuple(window)}")
+        if N != H * W or M != N:
+            raise _lib.RdetrError(f"{name}: the windowed mode needs N == M == H * W = {H * W}, got N = {N}, M = {M}")
+        if mask is not None:
+            raise _lib.RdetrError(f"{name}: the windowed mode takes no mask (the shift mask is the kernel's own)")
+        if bias is None or bias.dtype not in (torch.float32, torch.bfloat16) or tuple(bias.shape) != ((2 * wh - 1) * (2 * ww - 1), num_heads):
+            raise _lib.RdetrError(f"{name}: in the windowed mode bias is the relative position bias table "
+                                  f"[{(2 * wh - 1) * (2 * ww - 1)}, {num_heads}], float32 or bfloat16")
+        return (B, N, M, C, C // num_heads), _attention_rows(q, N), _attention_rows(k, M), _attention_rows(v, M), None
     if bias is not None and (bias.dtype != torch.float32 or bias.numel() != B * num_heads * N * M
                              or bias.dim() not in (3, 4) or tuple(bias.shape[-2:]) != (N, M)):
         raise _lib.RdetrError(f"{name}: bias must be float32 [B*H, N, M]")
@@ -730,11 +747,36 @@ def _attention_grad_buffers(name: str, B: int, N: int, M: int, C: int, device, p
 
 
 def relation_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, bias: Optional[torch.Tensor] = None,
-                       mask: Optional[torch.Tensor] = None, scale: Optional[float] = None) -> torch.Tensor:
+                       mask: Optional[torch.Tensor] = None, scale: Optional[float] = None, *, window=None, pad=None) -> torch.Tensor:
     """softmax(Q K^T * scale + bias) V per (image, head) in one kernel (bf16, head dim 32, inference).
     q [B,N,C], k / v [B,M,C] bf16 -- row-strided views are fine (last dim contiguous, image stride = rows * row stride);
-    bias fp32 [B*H,N,M] or None; mask bool [N,M] (True = excluded) or None -> [B,N,C] bf16."""
+    bias fp32 [B*H,N,M] or None; mask bool [N,M] (True = excluded) or None -> [B,N,C] bf16.
+
+    ``window = (H, W, wh, ww, sh, sw)`` selects Swin's shifted-window attention (csrc/attn_win.hip) on a map of H x W tokens,
+    N == M == H * W: the rows are windowed, rolled by the EFFECTIVE shift (``backbones.window.effective_shift``) and padded inside
+    the kernel, ``bias`` is the relative position bias table [(2wh-1)(2ww-1), heads] (fp32 or bf16), ``mask`` must be None (the
+    shift mask is generated), and ``pad = (k_pad, v_pad)``, bf16 [C] rows or None, are k and v of a padding token (the qkv
+    linear's bias; zeros when absent).  The result lies at the tokens' own rows.  Head dim 32, wh * ww <= 144."""
     _require_device(q, k, v, bias, mask)
+    if window is None and pad is not None:
+        raise _lib.RdetrError("relation_attention: pad belongs to the windowed mode (window=...)")
+    if window is not None:
+        (B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), _ = _attention_operands("relation_attention", q, k, v, num_heads, bias, mask,
+                                                                               window=window)
+        H, W, wh, ww, sh, sw = (int(x) for x in window)
+        k_pad, v_pad = (None, None) if pad is None else pad
+        _require_device(k_pad, v_pad)
+        for name, t in (("k_pad", k_pad), ("v_pad", v_pad)):
+            if t is not None and (t.dtype != torch.bfloat16 or t.numel() != C or not t.is_contiguous() or t.data_ptr() % 16):
+                raise _lib.RdetrError(f"relation_attention: {name} must be a contiguous, 16-byte aligned bfloat16 row of {C} values")
+        table = bias.contiguous()
+        res = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
+        st = _lib.load().rdetr_window_attention_bf16(
+            q.data_ptr(), k.data_ptr(), v.data_ptr(), ldq, ldk, ldv, None if k_pad is None else k_pad.data_ptr(),
+            None if v_pad is None else v_pad.data_ptr(), table.data_ptr(), int(table.dtype == torch.bfloat16), B, num_heads, D, H, W,
+            wh, ww, sh, sw, float(scale if scale is not None else D ** -0.5), res.data_ptr(), C, _stream_ptr(q))
+        _lib.check(st, "rdetr_window_attention_bf16")
+        return res
     (B, N, M, C, D), (q, ldq), (k, ldk), (v, ldv), mask_u8 = _attention_operands("relation_attention", q, k, v, num_heads, bias, mask)
     bias = None if bias is None else bias.contiguous()
     out = torch.empty(B, N, C, dtype=torch.bfloat16, device=q.device)
